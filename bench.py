@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — interval-queries/sec of the TIM encoder hot path (fwd+bwd) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--precision fp16|bf16|bf16x3|fp32] [--batch 64]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--precision fp16|bf16|bf16x3|fp32] [--batch 64] [--dump-outputs DIR]
 
 Workload (BASELINE.json configs[1] = SURVEY.md C2a): EPIC-100 audio-visual recognition,
 d_model 512 (E 1024), 6 layers, 8 heads, 50+50 feature tokens, 15 visual + 10 audio interval
@@ -193,7 +193,7 @@ def step_fn(model, batch, nv, na, R):
             g = torch.Generator(device="cpu").manual_seed(1)
             R[:] = [torch.randn(o.shape, generator=g).to(o.device) * 0.05 for o in outs]
         torch.autograd.backward(outs, R)
-        return
+        return {"cls": list(cls), "reg": list(reg), "feats": feats}
     te = model(batch["times"], "time_mlp")
     (verb, noun, action, audio), feats = model([batch["visual"], batch["audio"]], "encoder", te, nv, na)
     outs = [t for t in (verb, noun, action, audio, feats) if t is not None]
@@ -201,6 +201,7 @@ def step_fn(model, batch, nv, na, R):
         g = torch.Generator(device="cpu").manual_seed(1)
         R[:] = [torch.randn(o.shape, generator=g).to(o.device) * 0.05 for o in outs]
     torch.autograd.backward(outs, R)
+    return {"verb": verb, "noun": noun, "action": action, "audio": audio, "feats": feats}
 
 
 def gemm_roofline(model, cfg, B, nv, na, precision, reps=20):
@@ -509,6 +510,39 @@ def timed_steps(model, batch, nv, na, steps, warmup):
     return (time.perf_counter() - t0) / steps * 1e3
 
 
+DUMP_BUDGET_BYTES = 60 * 10 ** 6   # --dump-outputs: array data of all files together (64 MB is the limit; the .npy headers come on top)
+
+
+def _named_tensors(prefix, o):
+    """flatten what a step returned (a tensor, or lists / dicts of them; None = a head this configuration does not have)"""
+    if torch.is_tensor(o):
+        yield prefix, o
+    elif isinstance(o, dict):
+        for k, v in o.items():
+            yield from _named_tensors("%s_%s" % (prefix, k), v)
+    elif isinstance(o, (list, tuple)):
+        for i, v in enumerate(o):
+            yield from _named_tensors("%s_%d" % (prefix, i), v)
+
+
+def dump_outputs(dirname, step_out, model):
+    """--dump-outputs: what the last timed step handed its caller - the tensors it returned (out_*) and the gradient it left on
+    every parameter (grad.*) - as DIR/<name>.npy, float32 (integer outputs: float64).  The byte budget is split evenly over the
+    arrays; an array over its share is stored as a sample of its flattened elements at fixed positions (drawn from a generator
+    seeded with a constant, so they depend on nothing but the array's size): two builds run with the same arguments write files
+    that compare element by element."""
+    arrays = list(_named_tensors("out", step_out))
+    arrays += [("grad." + k, p.grad) for k, p in model.named_parameters() if p.grad is not None]
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays:
+        t = t.detach()
+        a = t.to(torch.float32 if t.is_floating_point() else torch.float64).cpu().numpy().ravel()
+        cap = DUMP_BUDGET_BYTES // len(arrays) // a.itemsize
+        if a.size > cap:
+            a = a[np.sort(np.random.RandomState(0).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -536,6 +570,9 @@ def main():
     ap.add_argument("--no-repeat", action="store_true", help="skip the four repeat sets of K steps behind the timed region")
     ap.add_argument("--no-per-shape", action="store_true", help="skip the isolated per-shape GEMM loop (profiling runs)")
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary blocks (parity sample, bf16 mode, C2b)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="behind the timed region, write what its last step computed (returned tensors + parameter gradients, rank 0) "
+                         "as DIR/<name>.npy: at most 64 MB, larger arrays as a fixed sample; same arguments -> same inputs")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -575,6 +612,10 @@ def main():
     if detection:
         nv, na = 399, 0          # the dense query pyramid the detection model generates (det tim.py:140-155)
     B = args.batch
+    # the dropout stream of a model is seeded from torch's generator when the model is built (tim_amd/functional.py: Runtime), and a
+    # fresh process seeds that generator as it likes: fixed here, so that two runs with the same arguments draw the same masks
+    # and compute the same step (--dump-outputs), like their weights, batch and cotangents, which have their own seeds
+    torch.manual_seed(0)
     model, sd_np = build_model(cfg, args.precision, dev, seed=0)
     model.train(not detection or args.det_train)   # C4 without --det-train: inference form with gradients (no GT targets needed)
     run_model = model
@@ -692,7 +733,8 @@ def main():
             from tim_amd import _lib as L
             L.call("timhip_gemm_timing_start", 512, 1.0e10)
             live = True
-        run_step()
+        step_out = None   # (the previous step's results go back to the allocator before the next step asks it for memory)
+        step_out = run_step()
     t_enqueue = time.perf_counter() - t0   # host time to ISSUE the K steps (the GPU may still be running them)
     barrier()
     dt = time.perf_counter() - t0
@@ -701,6 +743,9 @@ def main():
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
+    if args.dump_outputs and rank == 0:   # (before the repeat sets: a replayed graph writes every step's results to the same tensors)
+        dump_outputs(args.dump_outputs, step_out, model)
+    del step_out
     import ctypes as C
     from tim_amd import _lib as L
     ms_, fl_, n_ = C.c_double(0), C.c_double(0), C.c_int(0)
