@@ -24,6 +24,7 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--precision", default="bf16")
     ap.add_argument("--lr", type=float, default=2e-3)
+    ap.add_argument("--fused-optim", action="store_true", help="tim_amd.optim.FusedAdamW instead of torch.optim.AdamW")
     args = ap.parse_args(argv)
     dev = torch.device("cuda", 0)
     cfg = named_config("tiny")
@@ -34,7 +35,11 @@ def main(argv=None):
                 precision=args.precision)
     model.load_state_dict({k: torch.from_numpy(v) for k, v in synth.make_state_dict(cfg, seed=0).items()})
     model = model.to(dev).train()
-    opt = torch.optim.AdamW(model.parameters(), lr=args.lr, weight_decay=1e-4)
+    if args.fused_optim:
+        from tim_amd.optim import FusedAdamW
+        opt = FusedAdamW.for_model(model, lr=args.lr, weight_decay=1e-4)
+    else:
+        opt = torch.optim.AdamW(model.parameters(), lr=args.lr, weight_decay=1e-4)
     rs = np.random.RandomState(0)
     inp = {k: torch.from_numpy(v).to(dev) for k, v in synth.make_inputs(cfg, B, 0, 0, seed=5).items()}
     seg = lambda: torch.from_numpy(np.sort(rs.rand(B, ngt, 2), axis=-1).astype(np.float32)).to(dev)

@@ -57,6 +57,8 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--precision", default="bf16")
     ap.add_argument("--lr", type=float, default=1e-3)
+    ap.add_argument("--fused-optim", action="store_true",
+                    help="tim_amd.optim.FusedAdamW: clip, AdamW, non-finite skip and the operand-copy refresh as one device-side pass")
     args = ap.parse_args(argv)
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -77,7 +79,11 @@ def main(argv=None):
     if world > 1:
         from tim_amd.dp import DataParallel
         run = DataParallel(model)
-    opt = torch.optim.AdamW(model.parameters(), lr=args.lr, weight_decay=1e-4)
+    if args.fused_optim:
+        from tim_amd.optim import FusedAdamW
+        opt = FusedAdamW.for_model(model, lr=args.lr, weight_decay=1e-4, max_grad_norm=1.0)
+    else:
+        opt = torch.optim.AdamW(model.parameters(), lr=args.lr, weight_decay=1e-4)
     ds = synthetic_dataset(cfg, 4, 64, nv, na, dev, seed=rank)
     g = torch.Generator().manual_seed(rank)
     hist = []
@@ -96,6 +102,12 @@ def main(argv=None):
         loss = loss + 0.3 * losses.dense_relative_localization_loss_crossmodal(feats[:, :nf], feats[:, nf:], model, 8)
         opt.zero_grad(set_to_none=True)
         loss.backward()
+        if args.fused_optim:   # the clip, the inf / nan decision and the skip all happen on the device, inside the step
+            opt.step()
+            hist.append(loss.item())
+            if rank == 0 and (step % 5 == 0 or step == args.steps - 1):
+                print("step %3d  loss %.4f" % (step, hist[-1]), flush=True)
+            continue
         # non-finite guard (what GradScaler.step does in the reference loop, train.py:355-363): the fp16 mode's device-side
         # gradient scale never skips a step by itself, so the loop does - the clip already computes the norm
         gnorm = torch.nn.utils.clip_grad_norm_(model.parameters(), 1.0)

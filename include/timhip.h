@@ -203,6 +203,55 @@ typedef struct TimCastItem {
 } TimCastItem;
 int timhip_cast_weights(int precision, const TimCastItem* items, int n, void* stream);
 
+/* ---------------------------------------------------------------- optimizer step ---- */
+/* The tail of a training iteration - clip_grad_norm_ -> AdamW -> operand copies of the updated weights (the reference's
+ * recognition/scripts/train.py:351-363) - as device-side passes over a table of parameters.  Every scalar that changes from
+ * step to step lives in a STATE BLOCK in device memory (TIMHIP_OPT_STATE_WORDS 32-bit words, zero before the first step
+ * except the learning rate), never in a launch argument, so a captured step replays correctly:
+ *   [STEP]  uint32  updates applied so far (t of the bias corrections)          [LR]       float  learning rate (input)
+ *   [NORM]  float   total gradient norm of the latest step, before clipping     [COEF]     float  min(1, max_norm / (norm + 1e-6))
+ *   [FOUND_INF] uint32  1: the latest step was skipped                          [SKIPPED]  uint32 steps skipped so far
+ *   [BC1]   float   1 - beta1^t                                                 [BC2_SQRT] float  sqrt(1 - beta2^t)
+ * One step = timhip_optim_norm over every table that shares the clip, ONE timhip_optim_finish, timhip_optim_update per table. */
+enum { TIMHIP_OPT_STEP = 0, TIMHIP_OPT_LR = 1, TIMHIP_OPT_NORM = 2, TIMHIP_OPT_COEF = 3, TIMHIP_OPT_FOUND_INF = 4,
+       TIMHIP_OPT_SKIPPED = 5, TIMHIP_OPT_BC1 = 6, TIMHIP_OPT_BC2_SQRT = 7 };
+#define TIMHIP_OPT_STATE_WORDS 8
+
+typedef struct TimOptItem {
+  float* p;       /* fp32 master [rows, cols], contiguous (a 1-D tensor: rows = 1); any 4-byte aligned start */
+  const float* g; /* its gradient, same shape; read, never rescaled in memory (the clip lives in [COEF]) */
+  float* m;       /* exp_avg */
+  float* v;       /* exp_avg_sq */
+  void* plain;    /* operand-dtype copy [rows, ldp] of the updated master, or NULL; plain and tr are given together */
+  void* tr;       /* ... and its transpose [cols, ldt] (TimCastItem's meaning: 16-byte aligned, ldp / ldt multiples of 64) */
+  int32_t rows, cols, ldp, ldt;
+} TimOptItem;
+
+/* Number of partial sums (doubles) timhip_optim_norm writes for this table, or a TIMHIP_E* code (< 0).  items: HOST array,
+ * any length (the launches take it 48 items at a time in their kernel arguments). */
+int timhip_optim_norm_partials(const TimOptItem* items, int n);
+
+/* partials[0 .. timhip_optim_norm_partials(items, n)) = per-block sums of g^2 over the table.  No atomics: the result depends
+ * on the table alone. */
+int timhip_optim_norm(const TimOptItem* items, int n, double* partials, void* stream);
+
+/* One block finishes the step's scalars: norm = sqrt(sum of the partials, fixed order); found_inf = the norm is inf / nan, or
+ * any of the n_flags <= 32 device words flags[i] is non-zero (HOST array of device pointers: the out[4] words of the backward's
+ * timhip_grad_scale blocks); coef as above (max_norm <= 0: no clipping, the norm is still reported).  Then, for each of the
+ * n_states <= 8 state blocks (HOST array of device pointers; beta1 / beta2: HOST arrays, one pair per block): NORM, COEF,
+ * FOUND_INF are written, and either SKIPPED += 1 (found_inf) or STEP += 1 with BC1 / BC2_SQRT of the new step. */
+int timhip_optim_finish(const double* partials, int n_partials, const uint32_t* const* flags, int n_flags, float max_norm,
+                        float* const* states, const double* beta1, const double* beta2, int n_states, void* stream);
+
+/* AdamW on g * COEF, torch's arithmetic in fp32, with lr and the bias corrections read from `state`:
+ *   p *= 1 - lr * weight_decay;  m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g g;
+ *   p -= (lr / BC1) * m / (sqrt(v) / BC2_SQRT + eps)
+ * Returns at once, touching nothing, when state[FOUND_INF] is set.  Items with copies: the block that updates a 64 x 64 tile
+ * also writes plain[r, c] and tr[c, r] = the updated value in the operand dtype of `precision` - the bits timhip_cast_weights
+ * would produce from the updated master; padding columns (c >= cols, r >= rows) are left as they are. */
+int timhip_optim_update(int precision, const TimOptItem* items, int n, const float* state, double beta1, double beta2,
+                        double eps, double weight_decay, void* stream);
+
 /* ---------------------------------------------------------------- generic ops (also unit-test hooks) */
 typedef struct TimEpi {
   void* out0;

@@ -16,4 +16,10 @@ def __getattr__(name):  # lazy: importing the package must not require torch on 
     if name == "DetectionTIM":
         from .detection import TIM
         return TIM
+    if name == "FusedAdamW":
+        from .optim import FusedAdamW
+        return FusedAdamW
+    if name == "optim":
+        import importlib
+        return importlib.import_module(".optim", __name__)
     raise AttributeError(name)

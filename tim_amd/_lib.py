@@ -61,6 +61,16 @@ class TimCastItem(C.Structure):
     _fields_ = [("src", vp), ("plain", vp), ("tr", vp), ("rows", i32), ("cols", i32), ("ldp", i32), ("ldt", i32)]
 
 
+class TimOptItem(C.Structure):
+    _fields_ = [("p", vp), ("g", vp), ("m", vp), ("v", vp), ("plain", vp), ("tr", vp),
+                ("rows", i32), ("cols", i32), ("ldp", i32), ("ldt", i32)]
+
+
+# words of an optimizer state block (include/timhip.h: TIMHIP_OPT_*)
+OPT_STEP, OPT_LR, OPT_NORM, OPT_COEF, OPT_FOUND_INF, OPT_SKIPPED, OPT_BC1, OPT_BC2_SQRT = range(8)
+OPT_STATE_WORDS, OPT_MAX_FLAGS, OPT_MAX_STATES = 8, 32, 8
+
+
 class TimWgradItem(C.Structure):
     _fields_ = [("dY", vp), ("X", vp), ("dW", vp), ("db", vp), ("ldy", i32), ("ldx", i32), ("Nout", i32), ("Kout", i32)]
 
@@ -169,6 +179,10 @@ _SIGS = {
     "timhip_dp_reduce": (C.c_int, [i32, vp, i32, C.c_longlong, f32, vp, vp]),
     "timhip_split3_many": (C.c_int, [i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp]),
     "timhip_label_queries": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp]),
+    "timhip_optim_norm_partials": (C.c_int, [vp, i32]),
+    "timhip_optim_norm": (C.c_int, [vp, i32, vp, vp]),
+    "timhip_optim_finish": (C.c_int, [vp, i32, vp, i32, f32, vp, vp, vp, i32, vp]),
+    "timhip_optim_update": (C.c_int, [i32, vp, i32, vp, C.c_double, C.c_double, C.c_double, C.c_double, vp]),
     "timhip_smooth_one_hot": (C.c_int, [vp, i32, i32, C.c_int64, i32, f32, f32, vp, vp]),
 }
 

@@ -14,7 +14,8 @@ What makes the HIP path capturable:
   * dropout seeds are launch arguments, which a graph would freeze - `functional.graph_safe_dropout` moves the per-step part
     of the seed into a device word that a node of the graph advances (include/timhip.h: timhip_dropout_salt);
   * the operand-dtype weight copies are rebuilt by a cast kernel at the head of the captured step, so an optimizer update
-    between (or inside) replays is always picked up.
+    between (or inside) replays is always picked up; with `optimizer=` a `tim_amd.optim.FusedAdamW` the captured update
+    writes them itself and that cast is dropped.
 
 Usage (the shape of the reference's train loop, scripts/train.py:250-330):
 
@@ -61,9 +62,13 @@ class GraphedStep:
     warmup  eager runs on a side stream before capture (allocator warm-up, weight copies, gradient buckets)
     count_nodes  keep the captured hipGraph until it has been walked: `kernel_nodes` / `nodes` = the launches of one step,
             counted (hipGraphGetNodes + hipGraphNodeGetType), not assumed (bench.py's `launches_per_step`)
+    optimizer  a `tim_amd.optim.FusedAdamW` whose `step()` `fn` calls inside the capture: its learning rate is pushed to the
+            device before every replay (a scheduler's host-side write takes effect), the non-finite words of the captured
+            backward passes decide on the device whether a replayed update is skipped, and the captured update writes the
+            operand copies, so the cast at the head of the captured step is recorded only for what the update does not cover
     """
 
-    def __init__(self, model, fn, warmup=3, count_nodes=False):
+    def __init__(self, model, fn, warmup=3, count_nodes=False, optimizer=None):
         inner = model.module if hasattr(model, "module") else model
         if getattr(model, "active", False) and getattr(model, "collective", None) == "a2a":
             # all_to_all_single is send / receive pairs underneath; captured, they hang or crash hipStreamEndCapture on this
@@ -91,7 +96,14 @@ class GraphedStep:
             self.graph = torch.cuda.CUDAGraph(keep_graph=True) if count_nodes else torch.cuda.CUDAGraph()
         except TypeError:   # (a torch without keep_graph: no count)
             self.graph, count_nodes = torch.cuda.CUDAGraph(), False
-        self.rt.invalidate_weights()  # the cast of every weight is part of the captured step
+        self.optimizer = optimizer
+        if optimizer is None:
+            self.rt.invalidate_weights()  # the cast of every weight is part of the captured step
+        else:
+            if not hasattr(optimizer, "before_capture"):
+                raise TypeError("GraphedStep(optimizer=...) takes a tim_amd.optim.FusedAdamW; any other optimizer is simply "
+                                "called inside `fn` (capturable) or after the replay")
+            optimizer.before_capture(since=n_before)
         # With a process group alive, RCCL's watchdog thread polls the events of the warm-up steps' collectives while this thread
         # captures; under the default (global) capture mode that hipEventQuery is an error on the OTHER thread ("operation not
         # permitted when stream is capturing": the watchdog dies and takes the process with it - seen on a one-rank group,
@@ -126,7 +138,11 @@ class GraphedStep:
         self._grads = []
 
     def __call__(self):
+        if self.optimizer is not None:
+            self.optimizer.before_replay()
         self.graph.replay()
+        if self.optimizer is not None:
+            self.optimizer.after_replay()
         for p, g in self._grads:
             p.grad = g
         self.replays += 1

@@ -36,6 +36,7 @@ BUDGET = {
     # the fp16 fused backward (C2a / C3 / C4), with the kernel's own draws and with the keep-bits of round 6
     "attention_bwd2.hip": [(r"attn_bwd_rowsIDF16_Li128ELi4ELb1E", 0), (r"attn_bwd_rowsIDF16[_b]Li128ELi4ELb1ELb1ELb1E", 0)],
     "rowops.hip": [(r"ln_fwd8", 0), (r"ln_bwd_kernel", 0)],
+    "optim.hip": [(r"optim_norm_kernel", 0), (r"optim_update_kernel", 0)],   # streaming kernels: scratch traffic would share their HBM budget
 }
 
 
