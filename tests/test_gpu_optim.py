@@ -141,14 +141,19 @@ def test_operand_copies_are_written_with_cast_weights_bits(prec):
         _grads(ps, 40 + it)
         opt.step()
     for p in ps:
-        (ptr, ver), plain, tr = rt._wcache[id(p)]
-        assert (ptr, ver) == (p.data_ptr(), p._version)         # recorded as current: the next forward casts nothing
+        assert rt.copies.is_current(p)                          # recorded as current: the next forward casts nothing
+        plain, tr = _pair(rt, p)
         N, K = p.shape
         want = p.detach().to(rt.op_dtype)
         assert torch.equal(plain[:, :K], want) and torch.equal(tr[:, :N], want.t())
         assert not plain[:, K:].any() and not tr[:, N:].any()   # padding columns still zero
         fresh = F.Runtime(prec)                                 # ... and both are what timhip_cast_weights makes of the master
         assert torch.equal(fresh.weight(p), plain) and torch.equal(fresh.weight(p, True), tr)
+
+
+def _pair(rt, p):
+    """(plain, transposed) operand copies the runtime holds for `p`, as they are (no refresh)"""
+    return next((plain, tr) for q, plain, tr in rt.copies.pairs(p.device) if q is p)
 
 
 def _record_calls(monkeypatch):
@@ -273,8 +278,8 @@ def _opt_snapshot(model, opt):
     for n, p in model.named_parameters():
         if p in opt.state:
             out[n + ".m"], out[n + ".v"] = opt.state[p]["exp_avg"].clone(), opt.state[p]["exp_avg_sq"].clone()
-    for key, ent in model.rt._wcache.items():
-        out["plain%d" % key], out["tr%d" % key] = ent[1].clone(), ent[2].clone()
+    for q, plain, tr in model.rt.copies.pairs(torch.device(DEV)):
+        out["plain%d" % id(q)], out["tr%d" % id(q)] = plain.clone(), tr.clone()
     return out
 
 
@@ -306,7 +311,7 @@ def test_captured_optimizer_step_replays_bit_for_bit():
 
     def state(rt, ps, opt):
         out = [p.detach().clone() for p in ps] + [opt.state[p][k].clone() for p in ps for k in ("exp_avg", "exp_avg_sq")]
-        return out + [rt._wcache[id(p)][i].clone() for p in ps[:3] for i in (1, 2)]
+        return out + [t.clone() for p in ps[:3] for t in _pair(rt, p)]
 
     plan = [(1e-2, 21, False), (1e-2, 22, False), (3e-2, 23, False), (3e-2, 24, True), (3e-2, 25, False)]
 
@@ -348,8 +353,8 @@ def test_captured_optimizer_step_replays_bit_for_bit():
     assert int(opt2.skipped_steps) == 1 and int(opt.skipped_steps) == 1
     assert float(opt2.state_dict()["state"][0]["step"]) == 1 + 4
     for p in ps2[:3]:
-        ent = rt2._wcache[id(p)]
-        assert torch.equal(ent[1][:, :p.shape[1]], p.detach().half()) and torch.equal(ent[2][:, :p.shape[0]], p.detach().half().t())
+        plain, tr = _pair(rt2, p)
+        assert torch.equal(plain[:, :p.shape[1]], p.detach().half()) and torch.equal(tr[:, :p.shape[0]], p.detach().half().t())
 
 
 def test_graphed_step_with_the_fused_optimizer():
@@ -407,10 +412,9 @@ def test_graphed_step_with_the_fused_optimizer():
     d_large = (rep[3][name] - rep[2][name]).abs().max().item()
     assert d_large > 2.5 * d_small, (d_small, d_large)
     # the copies the captured update wrote are the casts of the masters it wrote
-    for key, ent in model.rt._wcache.items():
-        p = model.rt._wparams[key]()
+    for p, plain, tr in model.rt.copies.pairs(torch.device(DEV)):
         Nn, K = p.shape
-        assert torch.equal(ent[1][:, :K], p.detach().to(model.rt.op_dtype)) and torch.equal(ent[2][:, :Nn], p.detach().to(model.rt.op_dtype).t())
+        assert torch.equal(plain[:, :K], p.detach().to(model.rt.op_dtype)) and torch.equal(tr[:, :Nn], p.detach().to(model.rt.op_dtype).t())
     # a poisoned replay: nothing moves, one skipped step counted on the device; the next replay continues from the old count
     pois, opt_p, gs_p, model_p = run(True, [1e-3, 1e-3, 1e-3], poison_at=1)
     for n in pois[0]:

@@ -8,6 +8,7 @@ buffers, the current stream and autograd bookkeeping only.
 import ctypes as C
 import os
 import weakref
+from collections import namedtuple
 
 import torch
 
@@ -48,6 +49,171 @@ def graph_safe_dropout(dev, enable=True):
     return w
 
 
+class _Copy:
+    """one operand copy: `ver` = (data_ptr, _version) its parameter had when `bufs` were written; None = stale"""
+    __slots__ = ("ref", "ver", "bufs")
+
+    def __init__(self, p):
+        self.ref, self.ver, self.bufs = weakref.ref(p), None, None
+
+
+class OperandCopies:
+    """The operand-dtype working copies of a runtime's fp32 [N, K] weights, per kind keyed id(parameter).  kind None: the pair
+    (plain [N, ru(K)], transposed [K, ru(N)]), written together in one pass over the master (timhip_cast_weights); kind 0 / 1:
+    the split copy [N, 3 ru(K)] of that mode (`Runtime.weight_split`, timhip_split3_many).  A copy is CURRENT while its
+    parameter still has the storage address and version counter it was written from (same address and version = same contents
+    on the same device); everything else is stale and keeps its buffers for the refresh that follows."""
+
+    def __init__(self, rt):
+        self.rt = rt
+        self._ents = {None: {}, 0: {}, 1: {}}   # kind -> {id(param): _Copy}, in the order the runtime first saw them (= the order
+        #                                         of the items of a grouped refresh)
+
+    def get(self, p, kind=None):
+        """the buffers of p's copy; one stale copy refreshes every stale copy of that kind on p's device in the same launch"""
+        ent = self._ents[kind].get(id(p))
+        if ent is None or ent.ver != (p.data_ptr(), p._version):
+            if ent is None or ent.ref() is not p:
+                ent = self._ents[kind][id(p)] = _Copy(p)
+            self.refresh(p.device, kind)
+        return ent.bufs
+
+    def refresh(self, dev, kind=None):
+        """rebuild every stale copy of `kind` whose parameter lives on `dev`: one grouped launch"""
+        rt, todo, items, srcs = self.rt, [], [], []
+        for pid, ent in list(self._ents[kind].items()):
+            q = ent.ref()
+            if q is None:
+                del self._ents[kind][pid]
+                continue
+            ver = (q.data_ptr(), q._version)
+            if q.device != dev or ent.ver == ver:
+                continue
+            N, K = q.shape
+            shapes = ((N, _ru(K)), (K, _ru(N))) if kind is None else ((N, 3 * _ru(K)),)
+            if ent.bufs is None or ent.bufs[0].device != dev or ent.bufs[0].shape != shapes[0]:
+                ent.bufs = tuple(torch.empty(sh, dtype=rt.op_dtype, device=dev) for sh in shapes)
+            src = _f32c(q)
+            if kind is None:
+                plain, tr = ent.bufs
+                items.append(L.TimCastItem(ptr(src), ptr(plain), ptr(tr), N, K, plain.shape[1], tr.shape[1]))
+            else:
+                items.append((src, N, K, K, ent.bufs[0]))
+            srcs.append(src)
+            todo.append((ent, ver))
+        if items and kind is None:
+            arr = (L.TimCastItem * len(items))(*items)
+            call("timhip_cast_weights", rt.prec, C.cast(arr, C.c_void_p), len(items), _stream())
+        elif items:
+            rt.split3(items, mode=kind)
+        for ent, ver in todo:
+            ent.ver = ver
+
+    def invalidate(self, split_only=False, keep=()):
+        """mark copies stale: all of them, the split ones only, or all but the pairs of the parameters in `keep`"""
+        kept = {id(p) for p in keep}
+        for kind, ents in self._ents.items():
+            for pid, ent in ents.items():
+                if kind is not None or not (split_only or pid in kept):
+                    ent.ver = None
+
+    def pairs(self, dev):
+        """[(parameter, plain, transposed)]: the pairs (current or stale) held on `dev` for contiguous fp32 2-D parameters -
+        what a fused optimizer update can write next to the masters"""
+        out = []
+        for ent in self._ents[None].values():
+            q = ent.ref()
+            if q is None or ent.bufs is None or q.device != dev or q.dim() != 2 or q.dtype != torch.float32 or not q.is_contiguous():
+                continue
+            plain, tr = ent.bufs
+            if plain.device == dev and plain.shape[0] == q.shape[0] and tr.shape[0] == q.shape[1] and plain.dtype == self.rt.op_dtype:
+                out.append((q, plain, tr))
+        return out
+
+    def record(self, p, plain, tr):
+        """the pair (plain, tr) now holds p's present contents (somebody other than `refresh` wrote it)"""
+        ent = self._ents[None][id(p)]
+        ent.bufs, ent.ver = (plain, tr), (p.data_ptr(), p._version)
+
+    def is_current(self, p):
+        ent = self._ents[None].get(id(p))
+        return ent is not None and ent.ver == (p.data_ptr(), p._version)
+
+
+GS_FLAG_WORD = 4   # a timhip_grad_scale block is {S, 1/S, scratch, scratch, non-finite flag, 0, 0, 0}
+
+
+def any_flag_set(blocks):
+    """device-side OR of the blocks' non-finite words (no synchronisation)"""
+    return torch.stack([g[GS_FLAG_WORD] for g in blocks]).view(torch.int32).ne(0).any()
+
+
+class NonFiniteWatch:
+    """The non-finite flag words of a runtime's fp16 backward passes (`Runtime.grad_scale` registers one block per pass) until
+    somebody reads them: `Runtime.grads_finite()` on the host, or a fused optimizer step on the device."""
+
+    def __init__(self):
+        self._pending = []    # blocks of the eager passes since the last reader
+        self._captured = []   # blocks of captured (HIP-graph) passes nobody owns yet (strong references)
+        self._adopted = []    # weak references to the blocks a GraphedStep owns (adopt)
+        self._acc = None      # 0-dim bool device tensor: older pending blocks, folded
+
+    n_pending = property(lambda self: len(self._pending))
+    n_captured = property(lambda self: len(self._captured))
+
+    def add(self, gs, capturing):
+        if capturing:
+            # a block of a captured step lives as long as the graph and is rewritten by every replay: watched for good
+            self._captured.append(gs)
+        else:
+            # many backward passes without a reader: fold the OLDER blocks on the device (no sync) BEFORE this pass's block joins
+            # the list - its flag word is still zero here (its kernels are issued later), folding it would lose the pass's flag
+            if len(self._pending) >= 16:
+                self.fold(captured=False)
+            self._pending.append(gs)
+
+    def _or(self, blocks):
+        f = any_flag_set(blocks)
+        self._acc = f if self._acc is None else (self._acc | f)
+
+    def fold(self, captured=True):
+        if self._pending:
+            self._or(self._pending)
+            self._pending = []
+        if captured:   # (not consumed: the next replay zeroes and rewrites them)
+            self._adopted = [r for r in self._adopted if r() is not None]   # blocks of dropped graphs: no longer watched
+            live = [g for g in list(self._captured) + [r() for r in self._adopted] if g is not None]
+            if live:
+                self._or(live)
+
+    def take(self):
+        """(pending blocks, [the folded accumulator as a one-word tensor] or []) for a device-side reader; both are cleared"""
+        blocks, self._pending = self._pending, []
+        acc, self._acc = self._acc, None
+        return blocks, ([] if acc is None else [acc.to(torch.int32).reshape(1)])
+
+    def captured_from(self, since):
+        return list(self._captured[since:])
+
+    def adopt(self, since=0):
+        blocks, self._captured = self._captured[since:], self._captured[:since]
+        self._adopted += [weakref.ref(b) for b in blocks]
+        return blocks
+
+    def forget(self):
+        self._captured = []
+        self._adopted = []
+
+    def read(self, reset=True):
+        self.fold()
+        if self._acc is None:
+            return True
+        bad = bool(self._acc.item())
+        if reset:
+            self._acc = None
+        return not bad
+
+
 class Runtime:
     """Per-model state that is not a parameter: precision, operand-dtype working copies of
     the weights (plain and transposed, refreshed when a parameter's version changes),
@@ -79,8 +245,6 @@ class Runtime:
         self._layer_split = ()
         self._split_warned = False
         self.layer_split = modes[sel]
-        self._wsplit = {}
-        self._wsparams = {}  # id(param) -> weakref: every weight this runtime has split
         # fp16 backward: gradient operands are stored times a power of two chosen per backward pass from the incoming
         # cotangents (timhip_grad_scale): S * max|cotangent| ~ grad_scale_target.  16 leaves a factor 4096 of headroom below
         # the fp16 maximum for gradients that grow along the backward chain (LayerNorm's 1/std) and 2^-18 of the largest
@@ -95,12 +259,8 @@ class Runtime:
         if gsel not in ("16", "fp32"):
             raise ValueError("TIM_AMD_GRAD_STREAM=%r: expected 16 or fp32" % gsel)
         self.grad_stream16 = gsel == "16"
-        self._gs_blocks = []   # this runtime's timhip_grad_scale blocks since the last grads_finite() (word 4 = non-finite flag)
-        self._gs_captured = []  # ... and the blocks of captured (HIP-graph) backward passes nobody owns yet (strong references)
-        self._gs_adopted = []   # ... weak references to the blocks a GraphedStep owns (adopt_captured)
-        self._nf_acc = None
-        self._wcache = {}
-        self._wparams = {}  # id(param) -> weakref: every weight this runtime has cast
+        self.nonfinite = NonFiniteWatch()
+        self.copies = OperandCopies(self)
         # dropout stream: seeded from torch's generator (torch.manual_seed / args.seed select the run's masks, as they do in the
         # reference) and from the rank (data-parallel replicas draw different masks); TIM.dropout_rng_state() /
         # set_dropout_rng_state() let a checkpoint resume the sequence instead of replaying it
@@ -131,9 +291,6 @@ class Runtime:
         return st
 
     # ---- buffers -------------------------------------------------------------------------------
-    def zeros_op(self, rows, cols, dev):
-        return torch.zeros((rows, _ru(cols)), dtype=self.op_dtype, device=dev)
-
     def out_op(self, rows, cols, dev):
         """operand buffer [rows, ru(cols)] that a kernel is about to fill completely in its first `cols` columns: only a
         padded buffer (cols not a multiple of 64) needs the zero fill, for its padding columns"""
@@ -141,54 +298,13 @@ class Runtime:
             return torch.empty((rows, cols), dtype=self.op_dtype, device=dev)
         return torch.zeros((rows, _ru(cols)), dtype=self.op_dtype, device=dev)
 
-    def empty_op(self, rows, cols, dev):
-        assert cols % 64 == 0
-        return torch.empty((rows, cols), dtype=self.op_dtype, device=dev)
-
     # ---- weight working copies -----------------------------------------------------------------
     def weight(self, p, transposed=False):
         """operand-dtype copy of a [N,K] fp32 weight: [N, ru(K)] or (transposed) [K, ru(N)].  Both copies are
         produced together (one pass over the fp32 master) whenever the parameter's version changed; when one
         weight is found stale, every stale weight this runtime has seen is refreshed in the same launch
         (after an optimizer step that is all of them: one kernel instead of one per weight)."""
-        ent = self._wcache.get(id(p))
-        # (same storage address and version = same contents on the same device: no separate device comparison on the fast path)
-        if ent is None or ent[0] != (p.data_ptr(), p._version):
-            self._wparams[id(p)] = weakref.ref(p)
-            self._refresh(p.device)
-            ent = self._wcache[id(p)]
-        return ent[2] if transposed else ent[1]
-
-    def _refresh(self, dev):
-        items, keep, fresh = [], [], {}
-        for key, ref in list(self._wparams.items()):
-            q = ref()
-            if q is None:
-                self._wparams.pop(key, None)
-                self._wcache.pop(key, None)
-                continue
-            if q.device != dev:
-                continue
-            ent = self._wcache.get(key)
-            ver = (q.data_ptr(), q._version)
-            if ent is not None and ent[0] == ver and ent[1].device == dev:
-                continue
-            N, K = q.shape
-            src = q.detach()
-            if src.dtype != torch.float32 or not src.is_contiguous():
-                src = src.float().contiguous()
-            if ent is not None and ent[1].device == dev and ent[1].shape == (N, _ru(K)):
-                plain, tr = ent[1], ent[2]
-            else:
-                plain = torch.empty((N, _ru(K)), dtype=self.op_dtype, device=dev)
-                tr = torch.empty((K, _ru(N)), dtype=self.op_dtype, device=dev)
-            items.append(L.TimCastItem(ptr(src), ptr(plain), ptr(tr), N, K, plain.shape[1], tr.shape[1]))
-            keep.append(src)
-            fresh[key] = (ver, plain, tr)
-        if items:
-            arr = (L.TimCastItem * len(items))(*items)
-            call("timhip_cast_weights", self.prec, C.cast(arr, C.c_void_p), len(items), _stream())
-            self._wcache.update(fresh)
+        return self.copies.get(p)[1 if transposed else 0]
 
     # ---- opt-in weight-split mode of the encoder layers' forward GEMMs -----------------------------------------
     @property
@@ -231,40 +347,7 @@ class Runtime:
         of a three-term split product: time MLP, heads), mode 0 = [hi | lo | hi] (its first two blocks are the weight side of
         the TWO-term product [x | x] [w_hi | w_lo]^T of the encoder layers' out-projection, TIMHIP_DESC_OUTPROJ_SPLIT).  As in
         `weight`, one stale copy refreshes every stale split copy of that mode in the same grouped launch."""
-        key = (id(p), mode)
-        ent = self._wsplit.get(key)
-        ver = (p.data_ptr(), p._version)
-        if ent is None or ent[0] != ver or ent[1].device != p.device:
-            self._wsparams[key] = weakref.ref(p)
-            self._refresh_split(p.device, mode)
-            ent = self._wsplit[key]
-        return ent[1]
-
-    def _refresh_split(self, dev, mode):
-        items, fresh = [], {}
-        for key, ref in list(self._wsparams.items()):
-            if key[1] != mode:
-                continue
-            q = ref()
-            if q is None:
-                self._wsparams.pop(key, None)
-                self._wsplit.pop(key, None)
-                continue
-            if q.device != dev:
-                continue
-            ent = self._wsplit.get(key)
-            ver = (q.data_ptr(), q._version)
-            if ent is not None and ent[0] == ver and ent[1].device == dev:
-                continue
-            N, K = q.shape
-            src = _f32c(q)
-            buf = ent[1] if ent is not None and ent[1].device == dev and ent[1].shape == (N, 3 * _ru(K)) else \
-                torch.empty((N, 3 * _ru(K)), dtype=self.op_dtype, device=dev)
-            items.append((src, N, K, K, buf))
-            fresh[key] = (ver, buf, src)
-        if items:
-            self.split3(items, mode=mode)
-            self._wsplit.update(fresh)
+        return self.copies.get(p, mode)[0]
 
     def split3(self, items, mode, relu=False):
         """items: [(src fp32 [rows, cols] with row stride lds, rows, cols, lds, dst [rows, 3 ru(cols)])]"""
@@ -282,10 +365,7 @@ class Runtime:
         bump it - call this (also exported as `TIM.invalidate_weights()`) after such a write, or set
         `rt.recast_every_forward = True` to rebuild the copies at every training forward (one grouped launch, ~0.1 ms at
         C2a)."""
-        for k, ent in list(self._wcache.items()):
-            self._wcache[k] = (None, ent[1], ent[2])
-        for k, ent in list(self._wsplit.items()):
-            self._wsplit[k] = (None, ent[1], ent[2])
+        self.copies.invalidate()
 
     def next_seed(self):
         self.step += 1
@@ -309,15 +389,7 @@ class Runtime:
         dev = torch.device(dev)
         # {S, 1/S, scratch, scratch, non-finite flag, 0, 0, 0}; `out`: a block the caller has already zero-filled
         gs = out if out is not None else torch.zeros(8, dtype=torch.float32, device=dev)
-        if dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
-            # a block of a captured step lives as long as the graph and is rewritten by every replay: watched for good
-            self._gs_captured.append(gs)
-        else:
-            # many backward passes without a reader: fold the OLDER blocks on the device (no sync) BEFORE this pass's block joins
-            # the list - its flag word is still zero here (its kernels are issued below), folding it would lose the pass's flag
-            if len(self._gs_blocks) >= 16:
-                self._fold_flags(captured=False)
-            self._gs_blocks.append(gs)
+        self.nonfinite.add(gs, dev.type == "cuda" and torch.cuda.is_current_stream_capturing())
         cots = [c for c in cotangents if c is not None and c.numel() > 0]
         if not cots:
             gs[:2] = 1.0
@@ -328,34 +400,18 @@ class Runtime:
                  float(self.grad_scale_target), ptr(gs), _stream())
         return gs
 
-    def _fold_flags(self, captured=True):
-        if self._gs_blocks:
-            f = torch.stack([g[4] for g in self._gs_blocks]).view(torch.int32).ne(0).any()
-            self._nf_acc = f if self._nf_acc is None else (self._nf_acc | f)
-            self._gs_blocks = []
-        if captured:   # (not consumed: the next replay zeroes and rewrites them)
-            self._gs_adopted = [r for r in self._gs_adopted if r() is not None]   # blocks of dropped graphs: no longer watched
-            live = list(self._gs_captured) + [r() for r in self._gs_adopted]
-            live = [g for g in live if g is not None]
-            if live:
-                f = torch.stack([g[4] for g in live]).view(torch.int32).ne(0).any()
-                self._nf_acc = f if self._nf_acc is None else (self._nf_acc | f)
-
     def adopt_captured(self, since=0):
         """Hand the gradient-scale blocks of the backward passes captured so far (from list position `since`) to the caller (`GraphedStep` after its
         capture): the runtime keeps WEAK references from here on, so the blocks - and the watch on their non-finite flags -
         end with the object that owns the graph.  Blocks nobody adopts (a bare `torch.cuda.graph` capture) stay watched until
         `forget_captured()`."""
-        blocks, self._gs_captured = self._gs_captured[since:], self._gs_captured[:since]
-        self._gs_adopted += [weakref.ref(b) for b in blocks]
-        return blocks
+        return self.nonfinite.adopt(since)
 
     def forget_captured(self):
         """Stop watching the blocks of every captured backward pass (a graph was dropped or is about to be re-captured: its
         last replay may have left a flag set that nothing rewrites any more - watched for good it would make every later
         grads_finite() False and a `if rt.grads_finite(): opt.step()` loop skip every step)."""
-        self._gs_captured = []
-        self._gs_adopted = []
+        self.nonfinite.forget()
 
     def grads_finite(self, reset=True):
         """False iff a weight / bias gradient written since the last call (by this runtime's backward passes) was inf or nan -
@@ -364,13 +420,7 @@ class Runtime:
         synchronised until this call reads it.  Always True in the fp32 / bf16 modes (8 exponent bits: no overflow to watch).
         Under HIP-graph replay the words belong to the captured backward passes: every replay zeroes and rewrites them, so
         they describe the LATEST replay (reading does not clear them; eager passes in between are folded in as usual)."""
-        self._fold_flags()
-        if self._nf_acc is None:
-            return True
-        bad = bool(self._nf_acc.item())
-        if reset:
-            self._nf_acc = None
-        return not bad
+        return self.nonfinite.read(reset)
 
     # ---- thin op wrappers ------------------------------------------------------------------------
     def gemm(self, epi, A, B, M, N, K, out0, ld0, out1=None, ld1=0, bias=None, res=None, ldres=0, aux=None,
@@ -398,7 +448,7 @@ class Runtime:
         """items: [dict(A, B, M, N, K, out0, ld0, bias=None, res=None, ldres=0)] - independent small problems with the same
         epilogue; with 16-bit operands up to six go out as one grouped launch (timhip_gemm_nt_group), otherwise one launch each"""
         items = [it for it in items if it["M"] > 0 and it["N"] > 0]
-        if not self.h16 or len(items) < 2 or os.environ.get("TIM_AMD_NO_GEMM_GROUP", "0") == "1":  # (A/B switch)
+        if not self.h16 or len(items) < 2:
             for it in items:
                 self.gemm(epi, it["A"], it["B"], it["M"], it["N"], it["K"], it["out0"], it["ld0"], bias=it.get("bias"),
                           res=it.get("res"), ldres=it.get("ldres", 0), acc_scale=acc_scale, rep=it.get("rep", 0))
@@ -661,6 +711,496 @@ def _gather_head_rows(rt, x, B, S, E, ranges, st, prec=None):
             call("timhip_gather_rows", prec, ptr(x), B, S, E, s0, n, ptr(rows), st)
 
 
+class _Pass:
+    """what every stage of one encoder pass reads: the model, the token plan, the sizes and the dropout draw of the forward"""
+    __slots__ = ("model", "rt", "cfg", "plan", "names", "dev", "st", "B", "T", "d", "S", "F", "M", "E", "R", "p_feat", "p_seq",
+                 "p_enc", "seed", "salt_epoch")
+
+    def __init__(self, model, plan, dev, B, T, training, seed):
+        cfg = model.cfg
+        self.model, self.rt, self.cfg, self.plan, self.names = model, model.rt, cfg, plan, model._encoder_param_names
+        self.dev, self.st, self.seed = dev, _stream(), seed
+        self.B, self.T, self.d, self.E, self.S, self.F = B, T, cfg.d_model, cfg.E, plan.S, plan.F
+        self.M, self.R = B * plan.S, B * cfg.num_feats       # rows of the sequence, rows of one modality's features
+        self.p_feat, self.p_seq, self.p_enc = (cfg.feat_drop, cfg.seq_drop, cfg.enc_dropout) if training else (0.0, 0.0, 0.0)
+        self.salt_epoch = _SALT["epoch"] if training else None
+
+
+# What a forward stage leaves for its backward stage.  One modality's embedder: cast input rows, pre-LayerNorm rows, statistics
+_Embedder = namedtuple("_Embedder", "name slot xT u stats Cin site")
+# the embedders: [_Embedder]; whether both modalities went through the stacked-row launches ([visual | audio], R rows each);
+# the stacked pre-LayerNorm rows and statistics
+_Embedded = namedtuple("_Embedded", "mods paired u_all stats_all")
+# per layer: the saved block (the backward frees each as it goes); the operand-dtype input rows (xs_t[Lyr]: the last layer's
+# output); (TimLayerParams, the tensors it points to); DESC_ATTN_KEEP_BITS if the saved blocks carry the dropout keep-bits
+_Stack = namedtuple("_Stack", "saved xs_t lparams keep_flag")
+# one classification head; `rows`: its gathered operand-dtype input rows (None for an empty slice in the split mode)
+_Head = namedtuple("_Head", "slot pname s0 n rows")
+_RegHead = namedtuple("_RegHead", "slot pname s0 n rows h1 h2 y")
+# what every backward stage reads next to the _Pass: parameters by name (autograd's saved tensors), their gradient views
+# (tim.py: _GradBuckets), fp16: the device addresses of the pass's gradient scale S and of 1 / S (None in the other modes)
+_Back = namedtuple("_Back", "P G gs_in gs_out")
+
+_FE = "feature_encoding."
+
+
+def _keep_bits_fwd(q, Lyr):
+    """Per-layer saved blocks and, in training, the keep-bits of every layer's attention dropout: ONE launch ahead of the
+    stack (timhip_attn_keep_bits -> the layers' saved blocks; 128-wide heads with 97 .. 128 feature keys: C2a / C3 / C4).  The
+    attention forward and the fused backward then read 16 bytes per row instead of running Philox per (row, key) in both
+    directions.  Same stream of random numbers, same masks (tests/test_gpu_train_parity.py); TIM_AMD_ATTN_KEEP_BITS=0: the
+    kernels draw their own (A/B switch)."""
+    rt, cfg = q.rt, q.cfg
+    desc = L.TimDesc(q.B, q.S, q.F, q.d, q.E, cfg.nhead, cfg.FF, rt.prec, q.p_enc, q.seed, 0, rt.layer_split_flags(q.E, cfg.FF), None)
+    saved_bytes = L.load().timhip_layer_saved_bytes(C.byref(desc))
+    layer_saved = [torch.empty(saved_bytes, dtype=torch.uint8, device=q.dev) for _ in range(Lyr)]
+    if q.p_enc > 0.0 and rt.h16 and os.environ.get("TIM_AMD_ATTN_KEEP_BITS", "1") != "0":
+        rc = L.load().timhip_attn_keep_bits(C.byref(desc), Lyr, _parr(layer_saved), q.st)
+        if rc == 0:
+            desc.reserved |= L.DESC_ATTN_KEEP_BITS
+        elif rc != L.EUNSUPPORTED:
+            L.check(rc, "timhip_attn_keep_bits")
+    return desc, layer_saved
+
+
+def _embedders_fwd(q, P, visual, audio):
+    """modality embedders: e = LN(GELU(drop(x) W^T + b))  (encodings.py:21-26,140-153) -> (_Embedded, [e of slot 0, e of slot 1]).
+    Two modalities: their rows are STACKED ([visual | audio], R = B * nf rows each) so that the casts, the projections and the
+    LayerNorms are one launch each (timhip_cast_rows_pair, the grouped GEMM, timhip_layernorm_fwd2; the backward's
+    LayerNorm needs the halves to meet at a multiple of its 16-row blocks)"""
+    rt, dev, st, plan, R, d = q.rt, q.dev, q.st, q.plan, q.R, q.d
+    B, nf = q.B, q.cfg.num_feats
+    inputs = [visual if name == "visual" else audio for name, _ in plan.embedders]
+    for (name, _), x in zip(plan.embedders, inputs):
+        if x.dim() != 3 or x.shape[0] != B or x.shape[1] != nf:
+            raise ValueError("%s input must be [B=%d, num_feats=%d, C], got %s" % (name, B, nf, tuple(x.shape)))
+    ne = len(plan.embedders)
+    paired = ne == 2 and R % 16 == 0
+    u_all = torch.empty((ne * R, d), dtype=torch.float32, device=dev)
+    e_all = torch.empty((ne * R, d), dtype=torch.float32, device=dev)
+    stats_all = torch.empty((ne * R, 2), dtype=torch.float32, device=dev)
+    x2s = [_f32c(x).reshape(R, x.shape[2]) for x in inputs]
+    xTs = [torch.empty((R, _ru(x.shape[2])), dtype=rt.op_dtype, device=dev) for x in inputs]
+    sites = [L.SITE_FEAT_V if name == "visual" else L.SITE_FEAT_A for name, _ in plan.embedders]
+    if paired:
+        call("timhip_cast_rows_pair", rt.prec, _parr(x2s), _iarr([t.shape[1] for t in x2s]), _parr(xTs),
+             _iarr([t.shape[1] for t in xTs]), R, q.p_feat, q.seed, (C.c_uint32 * 2)(*sites), st)
+    mods, gemms, e_bufs = [], [], [None, None]
+    for i, (name, slot) in enumerate(plan.embedders):
+        x2, xT, site = x2s[i], xTs[i], sites[i]
+        Cin = x2.shape[1]
+        if not paired:
+            call("timhip_cast_rows", rt.prec, ptr(x2), R, Cin, Cin, ptr(xT), xT.shape[1], q.p_feat, q.seed, site, None, st)
+        u = u_all[i * R:(i + 1) * R]
+        gemms.append(dict(A=xT, B=rt.weight(P[_FE + name + "_embedder.1.weight"]), M=R, N=d, K=Cin, out0=u, ld0=d,
+                          bias=_f32c(P[_FE + name + "_embedder.1.bias"])))
+        mods.append(_Embedder(name, slot, xT, u, stats_all[i * R:(i + 1) * R], Cin, site))
+        e_bufs[slot] = e_all[i * R:(i + 1) * R]
+    rt.gemm_many(L.EPI_STORE_F32, gemms)   # the two modality embedders (under-filled, independent): one grouped launch
+    lnp = [(_f32c(P[_FE + name + "_embedder.3.weight"]), _f32c(P[_FE + name + "_embedder.3.bias"])) for name, _ in plan.embedders]
+    if paired:
+        call("timhip_layernorm_fwd2", rt.prec, ptr(u_all), 2 * R, d, d, 2, ptr(lnp[0][0]), ptr(lnp[0][1]), R, ptr(lnp[1][0]),
+             ptr(lnp[1][1]), ptr(e_all), d, None, 0, ptr(stats_all), st)
+    else:
+        for m, (w, b) in zip(mods, lnp):
+            rt.ln_fwd(m.u, R, d, 2, w, b, xf=e_bufs[m.slot], ldx=d, stats=m.stats)
+    return _Embedded(mods, paired, u_all, stats_all), e_bufs
+
+
+def _assemble_fwd(q, P, e_bufs, te_c):
+    """sequence assembly (encodings.py:190-250) -> the stack's input rows (fp32, operand dtype)
+    (the CLS token / modality vectors go to the kernel by pointer: separate parameters, no concatenation launches)"""
+    rt, plan = q.rt, q.plan
+    cls_v = [_f32c(P[_FE + n]).reshape(-1) for n in plan.cls_names]
+    mod_v = [_f32c(P[_FE + n]).reshape(-1) for n in plan.mod_names]
+    x_f = torch.empty((q.M, q.E), dtype=torch.float32, device=q.dev)
+    x_t = torch.empty((q.M, q.E), dtype=rt.op_dtype, device=q.dev)
+    call("timhip_assemble_fwd_p", rt.prec, ptr(plan.table(q.dev)), q.B, q.S, q.d, ptr(e_bufs[0]), ptr(e_bufs[1]), q.cfg.num_feats,
+         _parr(cls_v), len(cls_v), ptr(te_c), q.T, _parr(mod_v), len(mod_v), q.p_seq, q.seed, L.SITE_SEQ, ptr(x_f), ptr(x_t), q.st)
+    return x_f, x_t
+
+
+def _layers_fwd(q, P, desc, layer_saved, x0_f, x0_t):
+    """L post-norm encoder layers (transformers.py:44-45,92-111) -> (_Stack, fp32 rows of the last layer's output).
+    fp32 rows exist only at the two ends of the stack: the assembled input and the last layer's output (-> feats);
+    between layers every reader normalises the previous layer's pre-norm rows itself (timhip_layer_fwd_chained)"""
+    rt, model, dev, st = q.rt, q.model, q.dev, q.st
+    Lyr = len(layer_saved)
+    xL_f = torch.empty((q.M, q.E), dtype=torch.float32, device=dev)
+    xs_t = [x0_t] + [torch.empty((q.M, q.E), dtype=rt.op_dtype, device=dev) for _ in range(Lyr)]
+    ws_bytes = L.load().timhip_layer_workspace_bytes(C.byref(desc))
+    ws = model._workspace(ws_bytes, dev)
+    lparams = []
+    for l in range(Lyr):
+        lp = model._layer_params(rt, P, "%s.layers.%d." % (model._stack_prefix, l))
+        lparams.append(lp)
+        desc.layer = l
+        out_f = xL_f if l == Lyr - 1 else None
+        if l == 0:
+            call("timhip_layer_fwd", C.byref(desc), C.byref(lp[0]), ptr(x0_f), ptr(x0_t), ptr(out_f),
+                 ptr(xs_t[1]), ptr(layer_saved[0]), ptr(ws), ws_bytes, st)
+        else:
+            call("timhip_layer_fwd_chained", C.byref(desc), C.byref(lp[0]), C.byref(lparams[l - 1][0]),
+                 ptr(layer_saved[l - 1]), ptr(xs_t[l]), ptr(out_f), ptr(xs_t[l + 1]), ptr(layer_saved[l]), st)
+    return _Stack(layer_saved, xs_t, lparams, desc.reserved & L.DESC_ATTN_KEEP_BITS), xL_f
+
+
+def _heads_fwd(q, P, xL_f, xL_t, outs):
+    """classification heads (head.py:17-38) -> [_Head].  fp16 model: the logits are produced with split operands from the fp32
+    rows of the last layer; the backward gathers the fp16 rows it needs itself"""
+    rt, dev, st, B, S, E = q.rt, q.dev, q.st, q.B, q.S, q.E
+    heads, gemms, ranges = [], [], []
+    for slot, pname, s0, n in q.plan.heads:
+        w = P["cls_head." + pname + ".weight"]
+        Cn = w.shape[0]
+        logits = torch.empty((B * n, Cn), dtype=torch.float32, device=dev)
+        bias = _f32c(P["cls_head." + pname + ".bias"])
+        if rt.split:   # fp32 rows of the last layer -> [hi | lo | hi] fp16 blocks, weights [hi | hi | lo]: K = 3 E
+            rows = torch.empty((B * n, 3 * E), dtype=rt.op_dtype, device=dev)
+            item = dict(A=rows, B=rt.weight_split(w), M=B * n, N=Cn, K=3 * E, out0=logits, ld0=Cn, bias=bias, rep=3) if n > 0 else None
+            # (the backward's fp16 rows ARE the first block: T(fp32 row) = the operand copy the last LayerNorm wrote; its
+            #  weight gradients read that block - row stride 3 E - as their activations: no second gather)
+            heads.append(_Head(slot, pname, s0, n, rows[:, :E] if n > 0 else None))
+        else:
+            rows = torch.empty((B * n, E), dtype=rt.op_dtype, device=dev)
+            item = dict(A=rows, B=rt.weight(w), M=B * n, N=Cn, K=E, out0=logits, ld0=Cn, bias=bias) if n > 0 else None
+            heads.append(_Head(slot, pname, s0, n, rows))
+        if n > 0:
+            ranges.append((s0, n, rows))
+            gemms.append(item)
+        outs[slot] = logits
+    # the heads' row gathers and GEMMs are independent and tiny: one launch of each kind for all of them
+    if rt.split:   # gathered and split in one launch (E is a multiple of 64: d_model % 32 == 0)
+        for i0 in range(0, len(ranges), 6):
+            grp = ranges[i0:i0 + 6]
+            call("timhip_gather_split3_ranges", rt.prec, ptr(xL_f), B, S, E, len(grp), _iarr([r[0] for r in grp]),
+                 _iarr([r[1] for r in grp]), _parr([r[2] for r in grp]), st)
+    else:
+        _gather_head_rows(rt, xL_t, B, S, E, ranges, st)
+    rt.gemm_many(L.EPI_STORE_F32, gemms)
+    return heads
+
+
+def _reg_heads_fwd(q, P, xL_t, outs):
+    """regression heads of the detection variant: Linear-ReLU-Linear-ReLU-Linear-sigmoid on the heads' query rows -> [_RegHead]"""
+    rt, dev, B, E = q.rt, q.dev, q.B, q.E
+    hid = E // 2
+    regs = []
+    for slot, pname, s0, n in q.plan.reg:
+        pre = "reg_head." + pname + "."
+        rows = torch.empty((B * n, E), dtype=rt.op_dtype, device=dev)
+        h1 = rt.out_op(B * n, hid, dev)    # (zero-filled only when hid is not a multiple of 64: padding columns)
+        h2 = rt.out_op(B * n, hid, dev)
+        y = torch.empty((B * n, 2), dtype=torch.float32, device=dev)
+        if n > 0:
+            call("timhip_gather_rows", rt.prec, ptr(xL_t), B, q.S, E, s0, n, ptr(rows), q.st)
+            rt.gemm(L.EPI_RELU_T, rows, rt.weight(P[pre + "0.weight"]), B * n, hid, E, h1, h1.shape[1],
+                    bias=_f32c(P[pre + "0.bias"]))
+            rt.gemm(L.EPI_RELU_T, h1, rt.weight(P[pre + "2.weight"]), B * n, hid, hid, h2, h2.shape[1],
+                    bias=_f32c(P[pre + "2.bias"]))
+            rt.gemm(L.EPI_SIGMOID_F32, h2, rt.weight(P[pre + "4.weight"]), B * n, 2, hid, y, 2,
+                    bias=_f32c(P[pre + "4.bias"]))
+        outs[slot] = y
+        regs.append(_RegHead(slot, pname, s0, n, rows, h1, h2, y))
+    return regs
+
+
+def _heads_bwd(q, k, heads, g, dx):
+    """classification heads: cotangent casts, input-gradient GEMMs and the write of the whole gradient stream `dx` (feature rows
+    <- the `feats` cotangent, query rows <- their heads' rows) -> the heads' weight-gradient items (launched by the caller,
+    grouped by row count with the regression heads')"""
+    rt, dev, st, B, S, E = q.rt, q.dev, q.st, q.B, q.S, q.E
+    wg_items, dgrads, scatter, casts = [], [], [], []
+    for h in heads:
+        go, n, pre = g[h.slot], h.n, "cls_head." + h.pname
+        if go is None or n == 0:
+            continue
+        w = k.P[pre + ".weight"]
+        Cn = w.shape[0]
+        gT = torch.empty((B * n, _ru(Cn)), dtype=rt.op_dtype, device=dev)
+        casts.append((_f32c(go), B * n, Cn, gT))
+        wg_items.append((gT, Cn, h.rows, E, B * n, k.G[pre + ".weight"], k.G[pre + ".bias"]))
+        # A head with a long contraction (the 3806 action classes) as column chunks of the contraction side by side, each into
+        # its own fp32 slab (dx_init adds them up): as ONE item its 240 blocks ran 60 contraction steps while the other heads'
+        # blocks had finished after 2 - 5 (49 us for 8 GFLOP).  At most six items per grouped launch.
+        Kp = _ru(Cn)
+        ns = 1
+        if rt.h16 and Kp >= 2048:
+            ns = max(1, min(4, Kp // 1024, 6 - (len(q.plan.heads) - 1)))
+        wT = rt.weight(w, True)
+        if ns == 1:
+            d_rows = torch.empty((B * n, E), dtype=torch.float32, device=dev)
+            dgrads.append(dict(A=gT, B=wT, M=B * n, N=E, K=Cn, out0=d_rows, ld0=E))
+        else:
+            d_rows = torch.empty((ns, B * n, E), dtype=torch.float32, device=dev)
+            step = _ru((Kp + ns - 1) // ns)
+            for j in range(ns):
+                k0, k1 = j * step, min(Kp, (j + 1) * step)
+                dgrads.append(dict(A=gT[:, k0:k1], B=wT[:, k0:k1], M=B * n, N=E, K=k1 - k0, out0=d_rows[j], ld0=E))
+        scatter.append((d_rows, h.s0, n, ns))
+    # cotangent casts, input-gradient GEMMs and row scatters of all heads: one launch of each kind
+    if 2 <= len(casts) <= 6:
+        call("timhip_cast_rows_many", rt.prec, len(casts), _parr([c[0] for c in casts]), _iarr([c[1] for c in casts]),
+             _iarr([c[2] for c in casts]), _parr([c[3] for c in casts]), _iarr([c[3].shape[1] for c in casts]), k.gs_in, st)
+    else:
+        for go, r_, c_, gT in casts:
+            call("timhip_cast_rows", rt.prec, ptr(go), r_, c_, c_, ptr(gT), gT.shape[1], 0.0, 0, 0, k.gs_in, st)
+    rt.gemm_many(L.EPI_ADD_F32, dgrads, acc_scale=k.gs_out)
+    spans = sorted((s[1], s[1] + s[2]) for s in scatter)
+    disjoint = all(spans[i][1] <= spans[i + 1][0] for i in range(len(spans) - 1))   # detection: several heads read one row
+    gfeats = _f32c(g["feats"]) if g["feats"] is not None else None
+    if len(scatter) <= 6 and disjoint:
+        # one pass writes the whole stream: feature rows <- the `feats` cotangent (a copy, not a zero fill + add: 66 instead of
+        # 118 MB at C2a), query rows <- their head's rows, rest 0
+        call("timhip_dx_init_slabs", B, S, q.F, E, ptr(gfeats), len(scatter), _iarr([s[1] for s in scatter]),
+             _iarr([s[2] for s in scatter]), _parr([s[0] for s in scatter]), _iarr([s[3] for s in scatter]), ptr(dx), st)
+    else:
+        dx3 = dx.view(B, S, E)
+        if gfeats is not None:
+            dx3[:, :q.F].copy_(gfeats)
+        else:
+            dx3[:, :q.F].zero_()
+        if S > q.F:
+            dx3[:, q.F:].zero_()
+        for d_rows, s0, n, ns in scatter:
+            for j in range(ns):
+                call("timhip_scatter_rows_add", ptr(d_rows[j] if ns > 1 else d_rows), B, S, E, s0, n, ptr(dx), st)
+    return wg_items
+
+
+def _reg_heads_bwd(q, k, regs, g, dx):
+    """regression heads: their input gradients added into `dx` -> their weight-gradient items"""
+    rt, dev, st, B, E = q.rt, q.dev, q.st, q.B, q.E
+    P, G, hid = k.P, k.G, E // 2
+    wg_items = []
+    for r in regs:
+        go, n, h1, h2 = g[r.slot], r.n, r.h1, r.h2
+        if go is None or n == 0:
+            continue
+        pre = "reg_head." + r.pname + "."
+        # sigmoid backward on the [B*n, 2] outputs, written as the zero-padded operand rows of the gradient GEMMs
+        gzT = torch.empty((B * n, 64), dtype=rt.op_dtype, device=dev)
+        call("timhip_sigmoid_bwd_rows", rt.prec, ptr(_f32c(go)), ptr(r.y), B * n, 2, ptr(gzT), 64, k.gs_in, st)
+        wg_items.append((gzT, 2, h2, hid, B * n, G[pre + "4.weight"], G[pre + "4.bias"]))
+        dh2 = rt.out_op(B * n, hid, dev)
+        rt.gemm(L.EPI_DRELU_T, gzT, rt.weight(P[pre + "4.weight"], True), B * n, hid, 2, dh2, dh2.shape[1],
+                aux=h2, ldaux=h2.shape[1])
+        wg_items.append((dh2, hid, h1, hid, B * n, G[pre + "2.weight"], G[pre + "2.bias"]))
+        dh1 = rt.out_op(B * n, hid, dev)
+        rt.gemm(L.EPI_DRELU_T, dh2, rt.weight(P[pre + "2.weight"], True), B * n, hid, hid, dh1, dh1.shape[1],
+                aux=h1, ldaux=h1.shape[1])
+        wg_items.append((dh1, hid, r.rows, E, B * n, G[pre + "0.weight"], G[pre + "0.bias"]))
+        d_rows = torch.empty((B * n, E), dtype=torch.float32, device=dev)
+        rt.gemm(L.EPI_ADD_F32, dh1, rt.weight(P[pre + "0.weight"], True), B * n, E, hid, d_rows, E, acc_scale=k.gs_out)
+        call("timhip_scatter_rows_add", ptr(d_rows), B, q.S, E, r.s0, n, ptr(dx), st)
+    return wg_items
+
+
+class _Chain:
+    """the gradient stream through the layer stack, last layer to first: what the three schedules of `_layers_bwd` share"""
+    __slots__ = ("q", "G", "stack", "grads", "desc", "flags", "dx", "dx2", "dxa", "dxh", "add_in", "ln_part", "ln_bytes")
+
+    def __init__(self, q, k, stack, grads, dx, gs):
+        rt, dev, M, E = q.rt, q.dev, q.M, q.E
+        Lyr = len(stack.saved)
+        self.q, self.G, self.stack, self.grads = q, k.G, stack, grads
+        # bf16 / fp16: the layers' Linear gradients are written, not accumulated (their buckets are not zero-filled)
+        self.flags = (L.DESC_WGRAD_OVERWRITE if rt.h16 else 0) | (L.DESC_WGRAD_SEPARATE if rt.separate_wgrad else 0) | stack.keep_flag
+        self.desc = L.TimDesc(q.B, q.S, q.F, q.d, E, q.cfg.nhead, q.cfg.FF, rt.prec, q.p_enc, q.seed, 0, self.flags, k.gs_in)
+        self.dx, self.dx2 = dx, torch.empty_like(dx)
+        # between layers the gradient travels split: fp32 part (what LayerNorm-backward wrote) + operand-dtype part (the
+        # in-projection's input-gradient product, added by the next LayerNorm-backward as it reads): timhip_layer_bwd_split
+        # (plain bf16 would round that part to 8 bits per layer: there the layer returns one complete fp32 gradient instead)
+        split_stream = Lyr > 1 and rt.prec != L.PREC_BF16
+        self.dxa = [torch.empty((M, E), dtype=rt.op_dtype, device=dev) for _ in range(2)] if split_stream else [None, None]
+        # fp16, TIM_AMD_GRAD_STREAM=16 (opt-in): the residual part travels 16-bit as well, under the same gradient scale
+        # (TIMHIP_DESC_STREAM16*): the stack's entry (dx_init) and exit (layer 0 -> assemble_bwd) stay fp32.
+        stream16 = split_stream and rt.prec == L.PREC_F16 and gs is not None and rt.grad_stream16
+        self.dxh = [torch.empty((M, E), dtype=rt.op_dtype, device=dev) for _ in range(2)] if stream16 else None
+        self.add_in = None     # 16-bit part of the gradient entering the current layer (None at the top of the stack)
+        # LayerNorm dgamma / dbeta: every layer leaves per-block partials, one launch reduces them all at the end - unless a
+        # data-parallel hook takes each layer's bucket as soon as the layer is done (then the layer call reduces its own)
+        defer_ln = rt.bucket_hook is None
+        self.ln_bytes = L.load().timhip_layer_ln_partial_bytes(C.byref(self.desc)) if defer_ln else 0
+        self.ln_part = torch.empty(Lyr * self.ln_bytes, dtype=torch.uint8, device=dev) if defer_ln else None
+
+
+def _chain_layer(c, l):
+    """layer l's turn -> (its gradient table, gradient entering it, its 16-bit part, gradient leaving it, its 16-bit part);
+    sets the descriptor's layer and stream flags: fp32 `dx` / `dx2` at the two ends of the stack, with TIM_AMD_GRAD_STREAM=16
+    the 16-bit ping-pong pair in between"""
+    pre = "%s.layers.%d." % (c.q.model._stack_prefix, l)
+    lg = L.TimLayerGrads(*[ptr(c.G[pre + n]) for n in c.q.model._LAYER_GRAD_NAMES])
+    if c.ln_part is not None:
+        lg.ln_partials = ptr(c.ln_part) + l * c.ln_bytes
+    c.desc.layer = l
+    s_in, s_out = c.dx, c.dx2
+    if c.dxh is None:
+        c.desc.reserved = c.flags
+    else:
+        top, bottom = l == len(c.stack.saved) - 1, l == 0
+        c.desc.reserved = c.flags | L.DESC_STREAM16 | (0 if top else L.DESC_STREAM16_IN) | (0 if bottom else L.DESC_STREAM16_OUT)
+        s_in, s_out = (s_in if top else c.dxh[(l + 1) & 1]), (s_out if bottom else c.dxh[l & 1])
+    add_in, add_out = c.add_in, (c.dxa[l & 1] if l > 0 else None)
+    c.add_in = add_out
+    c.dx, c.dx2 = c.dx2, c.dx
+    return lg, s_in, add_in, s_out, add_out
+
+
+def _data_chain(c, l, dyb, ws, stream):
+    """issue the data chain of layer l on `stream` (its weight gradients follow from `dyb` in a launch of their own) -> lg"""
+    lg, s_in, add_in, s_out, add_out = _chain_layer(c, l)
+    call("timhip_layer_bwd_data_split", C.byref(c.desc), C.byref(c.stack.lparams[l][0]), ptr(c.stack.saved[l]), ptr(s_in),
+         ptr(add_in), ptr(s_out), ptr(add_out), ptr(dyb), C.byref(lg), ptr(ws[0]), ws[1], stream)
+    return lg
+
+
+def _split_workspaces(c):
+    """(data-chain workspace, bytes), (weight-gradient workspace, bytes), the two `dy` blocks that layers l and l - 1 alternate
+    between: what the two schedules that launch a layer's weight gradients apart from its data chain work in"""
+    lib, m, dev, d = L.load(), c.q.model, c.q.dev, C.byref(c.desc)
+    dws_bytes, wws_bytes, dy_bytes = (lib.timhip_layer_data_workspace_bytes(d), lib.timhip_layer_wgrad_workspace_bytes(d),
+                                      lib.timhip_layer_dy_bytes(d))
+    return ((m._workspace(dws_bytes, dev), dws_bytes), (m._workspace(wws_bytes, dev, slot="wgrad"), wws_bytes),
+            [m._workspace(dy_bytes, dev, slot="dy0"), m._workspace(dy_bytes, dev, slot="dy1")])
+
+
+def _layers_bwd_overlap(c):
+    """TIM_AMD_OVERLAP_WGRAD=1: the weight-gradient launch of layer l on the runtime's side stream, overlapping the data chain
+    of layer l - 1; each layer's bucket is handed to the hook as soon as its weight gradients are enqueued.  The saved blocks
+    stay alive (the side stream reads them) until the caller has joined the streams."""
+    stack = c.stack
+    main, aux = torch.cuda.current_stream(), c.q.rt.aux_stream(c.q.dev)
+    ws, wws, dys = _split_workspaces(c)
+    done = {}
+    aux.wait_stream(main)  # gradient buckets were zeroed on the main stream
+    for l in reversed(range(len(stack.saved))):
+        dyb = dys[l & 1]
+        if l + 2 in done:
+            main.wait_event(done[l + 2])  # the weight gradients of layer l+2 no longer read this dy
+        lg = _data_chain(c, l, dyb, ws, main.cuda_stream)
+        ev = torch.cuda.Event()
+        ev.record(main)
+        aux.wait_event(ev)
+        call("timhip_layer_bwd_weights", C.byref(c.desc), ptr(stack.xs_t[l]), ptr(stack.saved[l]), ptr(dyb),
+             C.byref(lg), ptr(wws[0]), wws[1], aux.cuda_stream)
+        done[l] = torch.cuda.Event()
+        done[l].record(aux)
+        c.grads.done("layer%d" % l, ready=done[l])
+
+
+def _layers_bwd_paired(c):
+    """Where two layers' weight gradients are ONE round of eight-phase tiles (timhip_layer_wgrad_pair_wins: C2a at production
+    batch sizes), a layer's weight gradients wait for its neighbour's data chain and the pair goes out as one launch on the
+    same stream; each layer of a pair keeps its own `dy` block (TIM_AMD_WGRAD_PAIR=0: A/B switch)"""
+    stack, grads, st = c.stack, c.grads, c.q.st
+    ws, wws, dys = _split_workspaces(c)
+    pending = None
+    for l in reversed(range(len(stack.saved))):
+        dyb = dys[l & 1]
+        lg = _data_chain(c, l, dyb, ws, st)
+        if pending is None and l > 0:
+            pending = (l, lg)      # its weight gradients go out with layer l - 1's
+            continue
+        if pending is not None:
+            lp, lgp = pending
+            call("timhip_layer_bwd_weights_pair", C.byref(c.desc), ptr(stack.xs_t[lp]), ptr(stack.saved[lp]), ptr(dys[lp & 1]),
+                 C.byref(lgp), ptr(stack.xs_t[l]), ptr(stack.saved[l]), ptr(dyb), C.byref(lg), ptr(wws[0]), wws[1], st)
+            grads.done("layer%d" % lp)
+            stack.saved[lp] = None
+            pending = None
+        else:                      # an odd layer count: layer 0 on its own
+            call("timhip_layer_bwd_weights", C.byref(c.desc), ptr(stack.xs_t[l]), ptr(stack.saved[l]), ptr(dyb),
+                 C.byref(lg), ptr(wws[0]), wws[1], st)
+        grads.done("layer%d" % l)
+        stack.saved[l] = None
+
+
+def _layers_bwd_in_sequence(c):
+    """a layer's data chain and weight gradients as one call on the current stream (timhip_layer_bwd_split)"""
+    stack, model = c.stack, c.q.model
+    ws_bytes = L.load().timhip_layer_workspace_bytes(C.byref(c.desc))
+    ws = model._workspace(ws_bytes, c.q.dev)
+    for l in reversed(range(len(stack.saved))):
+        lg, s_in, add_in, s_out, add_out = _chain_layer(c, l)
+        call("timhip_layer_bwd_split", C.byref(c.desc), C.byref(stack.lparams[l][0]), ptr(stack.xs_t[l]), ptr(stack.saved[l]),
+             ptr(s_in), ptr(add_in), ptr(s_out), ptr(add_out), C.byref(lg), ptr(ws), ws_bytes, c.q.st)
+        c.grads.done("layer%d" % l)
+        stack.saved[l] = None
+
+
+def _layers_bwd(c, overlap):
+    """layers, last to first, in one of three weight-gradient schedules -> the gradient of the stack's input rows"""
+    Lyr = len(c.stack.saved)
+    if overlap:
+        _layers_bwd_overlap(c)
+    elif (Lyr >= 2 and os.environ.get("TIM_AMD_WGRAD_PAIR", "1") != "0"
+          and L.load().timhip_layer_wgrad_pair_wins(C.byref(c.desc)) == 1):
+        _layers_bwd_paired(c)
+    else:
+        _layers_bwd_in_sequence(c)
+    return c.dx
+
+
+def _ln_partials_reduce(c):
+    """LayerNorm parameter gradients of all layers: one reduction of the saved per-block partials (sets: norm2, norm1 per layer)"""
+    if c.ln_part is None:
+        return
+    dgs, dbs = [], []
+    for l in range(len(c.stack.saved)):
+        pre = "%s.layers.%d." % (c.q.model._stack_prefix, l)
+        dgs += [c.G[pre + "norm2.weight"], c.G[pre + "norm1.weight"]]
+        dbs += [c.G[pre + "norm2.bias"], c.G[pre + "norm1.bias"]]
+    for i0 in range(0, len(dgs), 16):
+        call("timhip_ln_partials_reduce", ptr(c.ln_part) + (i0 // 2) * c.ln_bytes, len(dgs[i0:i0 + 16]), c.q.M, c.q.E,
+             _parr(dgs[i0:i0 + 16]), _parr(dbs[i0:i0 + 16]), c.q.st)
+
+
+def _assemble_bwd(q, k, dx, mods):
+    """sequence assembly backward -> (embedder output gradients stacked like the forward's rows, per slot, d_te)"""
+    plan, dev, R = q.plan, q.dev, q.R
+    d_e = [None, None]
+    d_e_all = torch.empty((len(mods) * R, q.d), dtype=torch.float32, device=dev)
+    for i, m in enumerate(mods):
+        d_e[m.slot] = d_e_all[i * R:(i + 1) * R]
+    d_te = torch.empty((q.B, q.T, q.d), dtype=torch.float32, device=dev)   # written in full by the kernel
+    # cls / modality gradients: atomics accumulate straight into the parameters' views of the (zero-filled) front-end bucket
+    d_cls = [k.G[_FE + n].view(-1) for n in plan.cls_names]
+    d_mod = [k.G[_FE + n].view(-1) for n in plan.mod_names]
+    call("timhip_assemble_bwd_p", ptr(plan.table(dev)), q.B, q.S, q.d, ptr(dx), q.cfg.num_feats, q.T, q.p_seq, q.seed, L.SITE_SEQ,
+         ptr(d_e[0]), ptr(d_e[1]), _parr(d_cls), len(d_cls), ptr(d_te), _parr(d_mod), len(d_mod), q.st)
+    return d_e_all, d_e, d_te
+
+
+def _embedders_bwd(q, k, emb, d_e_all, d_e, need_in):
+    """embedders backward -> {"visual": input gradient or None, "audio": ...}   (need_in: which inputs want one)"""
+    rt, dev, st, R, d = q.rt, q.dev, q.st, q.R, q.d
+    P, G = k.P, k.G
+    d_inputs = {"visual": None, "audio": None}
+    wg_items = []
+    duT_all = rt.out_op(len(emb.mods) * R, d, dev)
+    if emb.paired:   # both modalities' LayerNorm backward as one launch over the stacked rows
+        ln0, ln1 = (_FE + m.name + "_embedder.3." for m in emb.mods)
+        call("timhip_layernorm_bwd2", rt.prec, ptr(d_e_all), d, ptr(emb.u_all), d, ptr(emb.stats_all), 2 * R, d, 2,
+             ptr(_f32c(P[ln0 + "weight"])), R, ptr(_f32c(P[ln1 + "weight"])), None, 0, ptr(duT_all), duT_all.stride(0),
+             ptr(G[ln0 + "weight"]), ptr(G[ln0 + "bias"]), ptr(G[ln1 + "weight"]), ptr(G[ln1 + "bias"]), k.gs_in, st)
+    for i, m in enumerate(emb.mods):
+        pre, Cin = _FE + m.name + "_embedder.", m.Cin
+        duT = duT_all[i * R:(i + 1) * R]
+        if not emb.paired:
+            rt.ln_bwd(d_e[m.slot], m.u, m.stats, R, d, 2, _f32c(P[pre + "3.weight"]), dyt=duT,
+                      dgamma=G[pre + "3.weight"], dbeta=G[pre + "3.bias"], t_scale=k.gs_in)
+        wg_items.append((duT, d, m.xT, Cin, R, G[pre + "1.weight"], G[pre + "1.bias"]))
+        if need_in[m.name]:
+            gx = torch.empty((R, Cin), dtype=torch.float32, device=dev)
+            rt.gemm(L.EPI_ADD_F32, duT, rt.weight(P[pre + "1.weight"], True), R, Cin, d, gx, Cin, acc_scale=k.gs_out)
+            dxin = torch.empty((R, Cin), dtype=torch.float32, device=dev)
+            call("timhip_dropout_rows_bwd", ptr(gx), R, Cin, Cin, ptr(dxin), Cin, q.p_feat, q.seed, m.site, st)
+            d_inputs[m.name] = dxin.view(q.B, q.cfg.num_feats, Cin)
+    rt.wgrad_many(wg_items, out_scale=k.gs_out)
+    return d_inputs
+
+
 class EncoderFn(torch.autograd.Function):
     """forward(ctx, model, nv, na, visual, audio, te, *params) -> 7 outputs (OUT_SLOTS; None if absent).
     `params` is `model._encoder_param_list()` so that autograd tracks every parameter."""
@@ -669,507 +1209,69 @@ class EncoderFn(torch.autograd.Function):
     def forward(ctx, model, nv, na, visual, audio, te, *params):
         rt, cfg = model.rt, model.cfg
         _require_gpu(te, "encoder")
-        dev = te.device
-        P = dict(zip(model._encoder_param_names, params))
         B, T, d = te.shape
-        E, FF, H, Lyr, nf = cfg.E, cfg.FF, cfg.nhead, cfg.num_layers, cfg.num_feats
         if d != cfg.d_model:
             raise ValueError("time encodings have width %d, model d_model is %d" % (d, cfg.d_model))
         plan = model._plan(T, nv, na)
-        S, F = plan.S, plan.F
-        M = B * S
         training = model.training
         if training and rt.recast_every_forward:
             rt.invalidate_weights()
-        seed = rt.next_seed() if training else 0
-        p_feat = cfg.feat_drop if training else 0.0
-        p_seq = cfg.seq_drop if training else 0.0
-        p_enc = cfg.enc_dropout if training else 0.0
-        te_c = _f32c(te)
-        st = _stream()
-        fe = "feature_encoding."
-
-        # ---- per-layer saved blocks and, in training, the keep-bits of every layer's attention dropout: ONE launch ahead of the
-        # stack (timhip_attn_keep_bits -> the layers' saved blocks; 128-wide heads with 97 .. 128 feature keys: C2a / C3 / C4).  The
-        # attention forward and the fused backward then read 16 bytes per row instead of running Philox per (row, key) in both
-        # directions.  Same stream of random numbers, same masks (tests/test_gpu_train_parity.py); TIM_AMD_ATTN_KEEP_BITS=0: the
-        # kernels draw their own (A/B switch).  TIM_AMD_KEEP_BITS_SIDE=1 (A/B switch): the launch - VALU-bound, 16 us, independent
-        # of the front end - on the runtime's side stream under the embedders / the weight refresh, joined in front of layer 0
-        desc = L.TimDesc(B, S, F, d, E, H, FF, rt.prec, p_enc, seed, 0, rt.layer_split_flags(E, FF), None)
-        saved_bytes = L.load().timhip_layer_saved_bytes(C.byref(desc))
-        layer_saved = [torch.empty(saved_bytes, dtype=torch.uint8, device=dev) for _ in range(Lyr)]
-        keep_flag = 0
-        bits_pending = None
-        if p_enc > 0.0 and rt.h16 and os.environ.get("TIM_AMD_ATTN_KEEP_BITS", "1") != "0":
-            if os.environ.get("TIM_AMD_KEEP_BITS_SIDE", "0") == "1":
-                aux_s = rt.aux_stream(dev)
-                aux_s.wait_stream(torch.cuda.current_stream())   # (the blocks' previous owners are done)
-                rc = L.load().timhip_attn_keep_bits(C.byref(desc), Lyr, _parr(layer_saved), aux_s.cuda_stream)
-                bits_pending = aux_s
-            else:
-                rc = L.load().timhip_attn_keep_bits(C.byref(desc), Lyr, _parr(layer_saved), st)
-            if rc == 0:
-                keep_flag = L.DESC_ATTN_KEEP_BITS
-                desc.reserved |= keep_flag
-            elif rc != L.EUNSUPPORTED:
-                L.check(rc, "timhip_attn_keep_bits")
-
-        # ---- modality embedders: e = LN(GELU(drop(x) W^T + b))  (encodings.py:21-26,140-153)
-        # Two modalities: their rows are STACKED ([visual | audio], R = B * nf rows each) so that the casts, the projections and the
-        # LayerNorms are one launch each (timhip_cast_rows_pair, the grouped GEMM, timhip_layernorm_fwd2; the backward's
-        # LayerNorm needs the halves to meet at a multiple of its 16-row blocks)
-        emb_saved = []
-        emb_gemms = []
-        e_bufs = [None, None]
-        R = B * nf
-        for name, slot in plan.embedders:
-            x = visual if name == "visual" else audio
-            if x.dim() != 3 or x.shape[0] != B or x.shape[1] != nf:
-                raise ValueError("%s input must be [B=%d, num_feats=%d, C], got %s" % (name, B, nf, tuple(x.shape)))
-        ne = len(plan.embedders)
-        pair = ne == 2 and R % 16 == 0 and os.environ.get("TIM_AMD_EMBEDDER_PAIR", "1") != "0"   # (env: A/B switch)
-        u_all = torch.empty((ne * R, d), dtype=torch.float32, device=dev)
-        e_all = torch.empty((ne * R, d), dtype=torch.float32, device=dev)
-        stats_all = torch.empty((ne * R, 2), dtype=torch.float32, device=dev)
-        x2s, xTs, sites = [], [], []
-        for i, (name, slot) in enumerate(plan.embedders):
-            x = visual if name == "visual" else audio
-            Cin = x.shape[2]
-            x2s.append(_f32c(x).reshape(R, Cin))
-            xTs.append(torch.empty((R, _ru(Cin)), dtype=rt.op_dtype, device=dev))
-            sites.append(L.SITE_FEAT_V if name == "visual" else L.SITE_FEAT_A)
-        if pair:
-            call("timhip_cast_rows_pair", rt.prec, _parr(x2s), _iarr([t.shape[1] for t in x2s]), _parr(xTs),
-                 _iarr([t.shape[1] for t in xTs]), R, p_feat, seed, (C.c_uint32 * 2)(*sites), st)
-        for i, (name, slot) in enumerate(plan.embedders):
-            x2, xT, site = x2s[i], xTs[i], sites[i]
-            Cin = x2.shape[1]
-            if not pair:
-                call("timhip_cast_rows", rt.prec, ptr(x2), R, Cin, Cin, ptr(xT), xT.shape[1], p_feat, seed, site, None, st)
-            w = P[fe + name + "_embedder.1.weight"]
-            u = u_all[i * R:(i + 1) * R]
-            emb_gemms.append(dict(A=xT, B=rt.weight(w), M=R, N=d, K=Cin, out0=u, ld0=d,
-                                  bias=_f32c(P[fe + name + "_embedder.1.bias"])))
-            emb_saved.append((name, slot, xT, u, stats_all[i * R:(i + 1) * R], Cin, site))
-            e_bufs[slot] = e_all[i * R:(i + 1) * R]
-        rt.gemm_many(L.EPI_STORE_F32, emb_gemms)   # the two modality embedders (under-filled, independent): one grouped launch
-        del emb_gemms, x2s
-        lnp = [(_f32c(P[fe + name + "_embedder.3.weight"]), _f32c(P[fe + name + "_embedder.3.bias"])) for name, _ in plan.embedders]
-        if pair:
-            call("timhip_layernorm_fwd2", rt.prec, ptr(u_all), 2 * R, d, d, 2, ptr(lnp[0][0]), ptr(lnp[0][1]), R, ptr(lnp[1][0]),
-                 ptr(lnp[1][1]), ptr(e_all), d, None, 0, ptr(stats_all), st)
-        else:
-            for i, (name, slot, xT, u, stats, Cin, site) in enumerate(emb_saved):
-                rt.ln_fwd(u, R, d, 2, lnp[i][0], lnp[i][1], xf=e_bufs[slot], ldx=d, stats=stats)
-
-        # ---- sequence assembly (encodings.py:190-250)
-        # (the CLS token / modality vectors go to the kernel by pointer: separate parameters, no concatenation launches)
-        cls_v = [_f32c(P[fe + n]).reshape(-1) for n in plan.cls_names]
-        mod_v = [_f32c(P[fe + n]).reshape(-1) for n in plan.mod_names]
-        # fp32 rows exist only at the two ends of the stack: the assembled input and the last layer's output (-> feats);
-        # between layers every reader normalises the previous layer's pre-norm rows itself (timhip_layer_fwd_chained)
-        xs_f = [None] * (Lyr + 1)
-        xs_f[0] = torch.empty((M, E), dtype=torch.float32, device=dev)
-        xs_f[Lyr] = torch.empty((M, E), dtype=torch.float32, device=dev)
-        xs_t = [torch.empty((M, E), dtype=rt.op_dtype, device=dev) for _ in range(Lyr + 1)]
-        tab = plan.table(dev)
-        call("timhip_assemble_fwd_p", rt.prec, ptr(tab), B, S, d, ptr(e_bufs[0]), ptr(e_bufs[1]), nf, _parr(cls_v), len(cls_v),
-             ptr(te_c), T, _parr(mod_v), len(mod_v), p_seq, seed, L.SITE_SEQ, ptr(xs_f[0]), ptr(xs_t[0]), st)
-
-        # ---- L post-norm encoder layers (transformers.py:44-45,92-111)
-        ws_bytes = L.load().timhip_layer_workspace_bytes(C.byref(desc))
-        ws = model._workspace(ws_bytes, dev)
-        stack = model._stack_prefix
-        if bits_pending is not None:   # the keep-bits launch of the side stream joins here
-            torch.cuda.current_stream().wait_stream(bits_pending)
-        lparams = []
-        for l in range(Lyr):
-            pre = "%s.layers.%d." % (stack, l)
-            lp = model._layer_params(rt, P, pre)
-            lparams.append(lp)
-            sv = layer_saved[l]
-            desc.layer = l
-            if l == 0:
-                call("timhip_layer_fwd", C.byref(desc), C.byref(lp[0]), ptr(xs_f[0]), ptr(xs_t[0]), ptr(xs_f[1]),
-                     ptr(xs_t[1]), ptr(sv), ptr(ws), ws_bytes, st)
-            else:
-                call("timhip_layer_fwd_chained", C.byref(desc), C.byref(lp[0]), C.byref(lparams[l - 1][0]),
-                     ptr(layer_saved[l - 1]), ptr(xs_t[l]), ptr(xs_f[l + 1]), ptr(xs_t[l + 1]), ptr(sv), st)
-
-        # ---- heads (head.py:17-38).  fp16 model: the logits are produced with split operands from the fp32 rows of the last
-        # layer; the backward gathers the fp16 rows it needs itself
-        xL_t = xs_t[Lyr]
-        outs = {}
-        head_saved = []
-        head_gemms, head_ranges, head_splits = [], [], []
-        for slot, pname, s0, n in plan.heads:
-            w = P["cls_head." + pname + ".weight"]
-            Cn = w.shape[0]
-            logits = torch.empty((B * n, Cn), dtype=torch.float32, device=dev)
-            bias = _f32c(P["cls_head." + pname + ".bias"])
-            if rt.split:   # fp32 rows of the last layer -> [hi | lo | hi] fp16 blocks, weights [hi | hi | lo]: K = 3 E
-                rows3 = torch.empty((B * n, 3 * E), dtype=rt.op_dtype, device=dev)
-                if n > 0:
-                    head_ranges.append((s0, n, rows3))
-                    head_gemms.append(dict(A=rows3, B=rt.weight_split(w), M=B * n, N=Cn, K=3 * E, out0=logits, ld0=Cn, bias=bias, rep=3))
-                # (the backward's fp16 rows ARE the first block of rows3: T(fp32 row) = the operand copy the last LayerNorm wrote)
-                head_saved.append((slot, pname, s0, n, rows3[:, :E] if n > 0 else None))
-            else:
-                rows = torch.empty((B * n, E), dtype=rt.op_dtype, device=dev)
-                if n > 0:
-                    head_ranges.append((s0, n, rows))
-                    head_gemms.append(dict(A=rows, B=rt.weight(w), M=B * n, N=Cn, K=E, out0=logits, ld0=Cn, bias=bias))
-                head_saved.append((slot, pname, s0, n, rows))
-            outs[slot] = logits
-        # the heads' row gathers and GEMMs are independent and tiny: one launch of each kind for all of them
-        if rt.split:   # gathered and split in one launch (E is a multiple of 64: d_model % 32 == 0)
-            for i0 in range(0, len(head_ranges), 6):
-                grp = head_ranges[i0:i0 + 6]
-                call("timhip_gather_split3_ranges", rt.prec, ptr(xs_f[Lyr]), B, S, E, len(grp), _iarr([r[0] for r in grp]),
-                     _iarr([r[1] for r in grp]), _parr([r[2] for r in grp]), st)
-        else:
-            _gather_head_rows(rt, xL_t, B, S, E, head_ranges, st)
-        rt.gemm_many(L.EPI_STORE_F32, head_gemms)
-        del head_gemms, head_ranges, head_splits
-        reg_saved = []
-        for slot, pname, s0, n in plan.reg:
-            pre = "reg_head." + pname + "."
-            hid = E // 2
-            rows = torch.empty((B * n, E), dtype=rt.op_dtype, device=dev)
-            h1 = rt.out_op(B * n, hid, dev)    # (zero-filled only when hid is not a multiple of 64: padding columns)
-            h2 = rt.out_op(B * n, hid, dev)
-            y = torch.empty((B * n, 2), dtype=torch.float32, device=dev)
-            if n > 0:
-                call("timhip_gather_rows", rt.prec, ptr(xL_t), B, S, E, s0, n, ptr(rows), st)
-                rt.gemm(L.EPI_RELU_T, rows, rt.weight(P[pre + "0.weight"]), B * n, hid, E, h1, h1.shape[1],
-                        bias=_f32c(P[pre + "0.bias"]))
-                rt.gemm(L.EPI_RELU_T, h1, rt.weight(P[pre + "2.weight"]), B * n, hid, hid, h2, h2.shape[1],
-                        bias=_f32c(P[pre + "2.bias"]))
-                rt.gemm(L.EPI_SIGMOID_F32, h2, rt.weight(P[pre + "4.weight"]), B * n, 2, hid, y, 2,
-                        bias=_f32c(P[pre + "4.bias"]))
-            outs[slot] = y
-            reg_saved.append((slot, pname, s0, n, rows, h1, h2, y))
-        feats = xs_f[Lyr].view(B, S, E)[:, :F]
-        outs["feats"] = feats
-
-        ctx.model, ctx.plan, ctx.P_names = model, plan, model._encoder_param_names
-        ctx.dims = (B, T, d, S, F, M, nv, na)
-        ctx.drop = (p_feat, p_seq, p_enc, seed)
-        ctx.keep_flag = keep_flag
-        ctx.salt_epoch = _SALT["epoch"] if training else None
-        ctx.emb_saved, ctx.layer_saved, ctx.head_saved, ctx.reg_saved = emb_saved, layer_saved, head_saved, reg_saved
-        ctx.emb_pair = (u_all, stats_all) if pair else None
-        ctx.xs_t, ctx.lparams = xs_t, lparams
-        ctx.in_shapes = (tuple(visual.shape), tuple(audio.shape))
+        q = _Pass(model, plan, te.device, B, T, training, rt.next_seed() if training else 0)
+        P = dict(zip(q.names, params))
+        desc, layer_saved = _keep_bits_fwd(q, cfg.num_layers)
+        emb, e_bufs = _embedders_fwd(q, P, visual, audio)
+        x0_f, x0_t = _assemble_fwd(q, P, e_bufs, _f32c(te))
+        stack, xL_f = _layers_fwd(q, P, desc, layer_saved, x0_f, x0_t)
+        outs = {"feats": xL_f.view(B, q.S, q.E)[:, :q.F]}
+        heads = _heads_fwd(q, P, xL_f, stack.xs_t[-1], outs)
+        regs = _reg_heads_fwd(q, P, stack.xs_t[-1], outs)
+        ctx.q, ctx.emb, ctx.stack, ctx.heads, ctx.regs = q, emb, stack, heads, regs
+        ctx.dims, ctx.layer_saved = (B, T, d, q.S, q.F, q.M, nv, na), layer_saved   # (what the tests read off the graph node)
         ctx.save_for_backward(*params)
-        result = tuple(outs.get(k) for k in OUT_SLOTS)
-        ctx.mark_non_differentiable(*[])
-        return result
+        return tuple(outs.get(k) for k in OUT_SLOTS)
 
     @staticmethod
     def backward(ctx, *gouts):
-        model, plan = ctx.model, ctx.plan
-        rt, cfg = model.rt, model.cfg
+        q, stack = ctx.q, ctx.stack
+        model, rt, dev = q.model, q.rt, q.dev
         params = ctx.saved_tensors
-        names = ctx.P_names
-        P = dict(zip(names, params))
-        B, T, d, S, F, M, nv, na = ctx.dims
-        p_feat, p_seq, p_enc, seed = ctx.drop
-        if _SALT["word"] is not None and ctx.salt_epoch is not None and ctx.salt_epoch != _SALT["epoch"]:
+        if _SALT["word"] is not None and q.salt_epoch is not None and q.salt_epoch != _SALT["epoch"]:
             raise RuntimeError("graph-safe dropout: another training forward ran between this forward and its backward; "
                                "the masks are regenerated from the device-side salt, so each forward needs its backward first")
-        E, FF, H, Lyr, nf = cfg.E, cfg.FF, cfg.nhead, cfg.num_layers, cfg.num_feats
-        dev = params[0].device
-        st = _stream()
+        q.st = _stream()
         g = dict(zip(OUT_SLOTS, gouts))
-        fe = "feature_encoding."
-
         # gradient buckets: one flat fp32 buffer per bucket, parameters are views into it
-        # bf16: the layers' Linear gradients are written, not accumulated -> their buckets are not zero-filled (nor read)
-        overwrite = rt.h16
+        # bf16 / fp16: the layers' Linear gradients are written, not accumulated -> their buckets are not zero-filled (nor read)
         # every buffer of this pass that has to start at zero goes out in ONE multi-tensor launch with the buckets' fills: the
         # gradient-scale block of the fp16 mode (the cls / modality gradient sums are accumulated straight into their views of
         # the zero-filled front-end bucket)
         gs_block = torch.empty(8, dtype=torch.float32, device=dev) if rt.prec == L.PREC_F16 else None
-        extra_zero = [gs_block] if gs_block is not None else []
-        grads = model._alloc_grad_buckets(names, params, dev, layer_overwrite=overwrite, extra_zero=extra_zero)
-        G = grads.views
-
-        # gradient stream of the last layer's output: the feature rows start as the incoming `feats` cotangent (a copy, not a
-        # zero fill + add: 66 instead of 118 MB at C2a), the query rows as zeros for the heads' row scatters to add into
-        dx = torch.empty((M, E), dtype=torch.float32, device=dev)   # (written below, behind the heads' input-gradient products)
-        dx3 = dx.view(B, S, E)
-        xL_t = ctx.xs_t[Lyr]
+        grads = model._alloc_grad_buckets(q.names, params, dev, layer_overwrite=rt.h16,
+                                          extra_zero=[gs_block] if gs_block is not None else [])
+        # gradient stream of the last layer's output (written by the heads stage, behind their input-gradient products)
+        dx = torch.empty((q.M, q.E), dtype=torch.float32, device=dev)
         # fp16: scale of the gradient operands for this pass, from the cotangents that enter it (device side, no sync).  The
         # fp32 stream dx and every parameter gradient stay true-scale; only fp16 tensors carry the factor.
         gs = rt.grad_scale([_f32c(v) for v in gouts if v is not None], dev, out=gs_block)
         gs_in, gs_out = (ptr(gs), ptr(gs) + 4) if gs is not None else (None, None)
-        # (fp16: the forward fed the heads from the fp32 rows as [hi | lo | hi] blocks; the weight gradients read the hi block -
-        #  row stride 3 E - as their fp16 activations: no second gather)
-        head_saved = ctx.head_saved
+        k = _Back(dict(zip(q.names, params)), grads.views, gs_in, gs_out)
 
-        # ---- heads (their weight gradients are collected and launched grouped by row count)
-        wg_items = []
-        head_dgrads, head_scatter, head_casts = [], [], []
-        for slot, pname, s0, n, rows in head_saved:
-            go = g[slot]
-            if go is None or n == 0:
-                continue
-            w = P["cls_head." + pname + ".weight"]
-            Cn = w.shape[0]
-            go = _f32c(go)
-            gT = torch.empty((B * n, _ru(Cn)), dtype=rt.op_dtype, device=dev)
-            head_casts.append((go, B * n, Cn, gT))
-            wg_items.append((gT, Cn, rows, E, B * n, G["cls_head." + pname + ".weight"], G["cls_head." + pname + ".bias"]))
-            # A head with a long contraction (the 3806 action classes) as column chunks of the contraction side by side, each into
-            # its own fp32 slab (dx_init adds them up): as ONE item its 240 blocks ran 60 contraction steps while the other heads'
-            # blocks had finished after 2 - 5 (49 us for 8 GFLOP).  At most six items per grouped launch.
-            Kp = _ru(Cn)
-            ns = 1
-            if rt.h16 and Kp >= 2048:
-                ns = max(1, min(4, Kp // 1024, 6 - (len(plan.heads) - 1)))
-            wT = rt.weight(w, True)
-            if ns == 1:
-                d_rows = torch.empty((B * n, E), dtype=torch.float32, device=dev)
-                head_dgrads.append(dict(A=gT, B=wT, M=B * n, N=E, K=Cn, out0=d_rows, ld0=E))
-            else:
-                d_rows = torch.empty((ns, B * n, E), dtype=torch.float32, device=dev)
-                step = _ru((Kp + ns - 1) // ns)
-                for j in range(ns):
-                    k0, k1 = j * step, min(Kp, (j + 1) * step)
-                    head_dgrads.append(dict(A=gT[:, k0:k1], B=wT[:, k0:k1], M=B * n, N=E, K=k1 - k0, out0=d_rows[j], ld0=E))
-            head_scatter.append((d_rows, s0, n, ns))
-        # cotangent casts, input-gradient GEMMs and row scatters of all heads: one launch of each kind
-        if 2 <= len(head_casts) <= 6:
-            call("timhip_cast_rows_many", rt.prec, len(head_casts), _parr([c[0] for c in head_casts]),
-                 _iarr([c[1] for c in head_casts]), _iarr([c[2] for c in head_casts]), _parr([c[3] for c in head_casts]),
-                 _iarr([c[3].shape[1] for c in head_casts]), gs_in, st)
-        else:
-            for go, r_, c_, gT in head_casts:
-                call("timhip_cast_rows", rt.prec, ptr(go), r_, c_, c_, ptr(gT), gT.shape[1], 0.0, 0, 0, gs_in, st)
-        rt.gemm_many(L.EPI_ADD_F32, head_dgrads, acc_scale=gs_out)
-        spans = sorted((h[1], h[1] + h[2]) for h in head_scatter)
-        disjoint = all(spans[i][1] <= spans[i + 1][0] for i in range(len(spans) - 1))   # detection: several heads read one row
-        gfeats = _f32c(g["feats"]) if g["feats"] is not None else None
-        if len(head_scatter) <= 6 and disjoint:
-            # one pass writes the whole stream: feature rows <- the `feats` cotangent, query rows <- their head's rows, rest 0
-            call("timhip_dx_init_slabs", B, S, F, E, ptr(gfeats), len(head_scatter), _iarr([h[1] for h in head_scatter]),
-                 _iarr([h[2] for h in head_scatter]), _parr([h[0] for h in head_scatter]), _iarr([h[3] for h in head_scatter]),
-                 ptr(dx), st)
-        else:
-            if gfeats is not None:
-                dx3[:, :F].copy_(gfeats)
-            else:
-                dx3[:, :F].zero_()
-            if S > F:
-                dx3[:, F:].zero_()
-            for d_rows, s0, n, ns in head_scatter:
-                for j in range(ns):
-                    call("timhip_scatter_rows_add", ptr(d_rows[j] if ns > 1 else d_rows), B, S, E, s0, n, ptr(dx), st)
-        del head_dgrads, head_scatter, head_casts
-        for slot, pname, s0, n, rows, h1, h2, y in ctx.reg_saved:
-            go = g[slot]
-            if go is None or n == 0:
-                continue
-            pre = "reg_head." + pname + "."
-            hid = E // 2
-            # sigmoid backward on the [B*n, 2] outputs, written as the zero-padded operand rows of the gradient GEMMs
-            gzT = torch.empty((B * n, 64), dtype=rt.op_dtype, device=dev)
-            call("timhip_sigmoid_bwd_rows", rt.prec, ptr(_f32c(go)), ptr(y), B * n, 2, ptr(gzT), 64, gs_in, st)
-            wg_items.append((gzT, 2, h2, hid, B * n, G[pre + "4.weight"], G[pre + "4.bias"]))
-            dh2 = rt.out_op(B * n, hid, dev)
-            rt.gemm(L.EPI_DRELU_T, gzT, rt.weight(P[pre + "4.weight"], True), B * n, hid, 2, dh2, dh2.shape[1],
-                    aux=h2, ldaux=h2.shape[1])
-            wg_items.append((dh2, hid, h1, hid, B * n, G[pre + "2.weight"], G[pre + "2.bias"]))
-            dh1 = rt.out_op(B * n, hid, dev)
-            rt.gemm(L.EPI_DRELU_T, dh2, rt.weight(P[pre + "2.weight"], True), B * n, hid, hid, dh1, dh1.shape[1],
-                    aux=h1, ldaux=h1.shape[1])
-            wg_items.append((dh1, hid, rows, E, B * n, G[pre + "0.weight"], G[pre + "0.bias"]))
-            d_rows = torch.empty((B * n, E), dtype=torch.float32, device=dev)
-            rt.gemm(L.EPI_ADD_F32, dh1, rt.weight(P[pre + "0.weight"], True), B * n, E, hid, d_rows, E, acc_scale=gs_out)
-            call("timhip_scatter_rows_add", ptr(d_rows), B, S, E, s0, n, ptr(dx), st)
-        rt.wgrad_many(wg_items, out_scale=gs_out)
+        wg_items = _heads_bwd(q, k, ctx.heads, g, dx) + _reg_heads_bwd(q, k, ctx.regs, g, dx)
+        rt.wgrad_many(wg_items, out_scale=gs_out)   # the heads' weight gradients, grouped by row count
         del wg_items
         grads.done("heads")
-
-        # ---- layers, last to first.  Per layer: the data chain on the current stream, the four
-        # weight-gradient GEMMs on a side stream (they overlap the data chain of the next layer);
-        # each layer's bucket is handed to the hook as soon as its weight gradients are enqueued.
-        desc = L.TimDesc(B, S, F, d, E, H, FF, rt.prec, p_enc, seed, 0,
-                         (L.DESC_WGRAD_OVERWRITE if overwrite else 0) | (L.DESC_WGRAD_SEPARATE if rt.separate_wgrad else 0) | ctx.keep_flag,
-                         gs_in)
-        lib = L.load()
-        dx2 = torch.empty_like(dx)
-        # between layers the gradient travels split: fp32 part (what LayerNorm-backward wrote) + operand-dtype part (the
-        # in-projection's input-gradient product, added by the next LayerNorm-backward as it reads): timhip_layer_bwd_split
-        # (plain bf16 would round that part to 8 bits per layer: there the layer returns one complete fp32 gradient instead)
-        split_stream = Lyr > 1 and rt.prec != L.PREC_BF16
-        dxa = [torch.empty((M, E), dtype=rt.op_dtype, device=dev) for _ in range(2)] if split_stream else [None, None]
-        # fp16, TIM_AMD_GRAD_STREAM=16 (opt-in): the residual part travels 16-bit as well, under the same gradient scale
-        # (TIMHIP_DESC_STREAM16*): the stack's entry (dx_init) and exit (layer 0 -> assemble_bwd) stay fp32.
-        stream16 = split_stream and rt.prec == L.PREC_F16 and gs is not None and rt.grad_stream16
-        dxh = [torch.empty((M, E), dtype=rt.op_dtype, device=dev) for _ in range(2)] if stream16 else [None, None]
-        base_flags = desc.reserved
-        add_in = None     # 16-bit part of the gradient entering the current layer (None at the top of the stack)
-        stack = model._stack_prefix
-        main = torch.cuda.current_stream()
         overlap = rt.overlap_wgrad
-        keep_alive = []
-        if overlap:
-            aux = rt.aux_stream(dev)
-            dws_bytes = lib.timhip_layer_data_workspace_bytes(C.byref(desc))
-            wws_bytes = lib.timhip_layer_wgrad_workspace_bytes(C.byref(desc))
-            dy_bytes = lib.timhip_layer_dy_bytes(C.byref(desc))
-            ws = model._workspace(dws_bytes, dev)
-            wws = model._workspace(wws_bytes, dev, slot="wgrad")
-            dys = [model._workspace(dy_bytes, dev, slot="dy0"), model._workspace(dy_bytes, dev, slot="dy1")]
-            done = {}
-            aux.wait_stream(main)  # gradient buckets were zeroed on the main stream
-        else:
-            ws_bytes = lib.timhip_layer_workspace_bytes(C.byref(desc))
-            ws = model._workspace(ws_bytes, dev)
-        # round 6: where two layers' weight gradients are ONE round of eight-phase tiles (timhip_layer_wgrad_pair_wins: C2a at
-        # production batch sizes), a layer's weight gradients wait for its neighbour's data chain and the pair goes out as one
-        # launch on the same stream; each layer of a pair keeps its own `dy` block (TIM_AMD_WGRAD_PAIR=0: A/B switch)
-        pair = (not overlap and Lyr >= 2 and os.environ.get("TIM_AMD_WGRAD_PAIR", "1") != "0"
-                and lib.timhip_layer_wgrad_pair_wins(C.byref(desc)) == 1)
-        pending = None
-        if pair:
-            dws_bytes = lib.timhip_layer_data_workspace_bytes(C.byref(desc))
-            wws_bytes = lib.timhip_layer_wgrad_workspace_bytes(C.byref(desc))
-            dy_bytes = lib.timhip_layer_dy_bytes(C.byref(desc))
-            ws = model._workspace(dws_bytes, dev)
-            wws = model._workspace(wws_bytes, dev, slot="wgrad")
-            dys = [model._workspace(dy_bytes, dev, slot="dy0"), model._workspace(dy_bytes, dev, slot="dy1")]
-        # LayerNorm dgamma / dbeta: every layer leaves per-block partials, one launch reduces them all at the end - unless a
-        # data-parallel hook takes each layer's bucket as soon as the layer is done (then the layer call reduces its own)
-        defer_ln = rt.bucket_hook is None and os.environ.get("TIM_AMD_NO_DEFER_LN", "0") != "1"   # (env: A/B switch)
-        ln_part_bytes = lib.timhip_layer_ln_partial_bytes(C.byref(desc)) if defer_ln else 0
-        ln_part = torch.empty(Lyr * ln_part_bytes, dtype=torch.uint8, device=dev) if defer_ln else None
-        def _stream16_io(l):
-            """(gradient entering layer l, gradient leaving it) and the layer's stream flags: fp32 `dx` / `dx2` at the two ends of
-            the stack, the 16-bit ping-pong pair in between"""
-            if not stream16:
-                desc.reserved = base_flags
-                return dx, dx2
-            top, bottom = l == Lyr - 1, l == 0
-            desc.reserved = base_flags | L.DESC_STREAM16 | (0 if top else L.DESC_STREAM16_IN) | (0 if bottom else L.DESC_STREAM16_OUT)
-            return (dx if top else dxh[(l + 1) & 1]), (dx2 if bottom else dxh[l & 1])
-
-        for l in reversed(range(Lyr)):
-            pre = "%s.layers.%d." % (stack, l)
-            lg = L.TimLayerGrads(*[ptr(G[pre + n]) for n in model._LAYER_GRAD_NAMES])
-            if defer_ln:
-                lg.ln_partials = ptr(ln_part) + l * ln_part_bytes
-            desc.layer = l
-            if overlap:
-                dyb = dys[l & 1]
-                if l + 2 in done:
-                    main.wait_event(done[l + 2])  # the weight gradients of layer l+2 no longer read this dy
-                add_out = dxa[l & 1] if l > 0 else None
-                s_in, s_out = _stream16_io(l)
-                call("timhip_layer_bwd_data_split", C.byref(desc), C.byref(ctx.lparams[l][0]), ptr(ctx.layer_saved[l]),
-                     ptr(s_in), ptr(add_in), ptr(s_out), ptr(add_out), ptr(dyb), C.byref(lg), ptr(ws), dws_bytes, main.cuda_stream)
-                add_in = add_out
-                ev = torch.cuda.Event()
-                ev.record(main)
-                aux.wait_event(ev)
-                call("timhip_layer_bwd_weights", C.byref(desc), ptr(ctx.xs_t[l]), ptr(ctx.layer_saved[l]), ptr(dyb),
-                     C.byref(lg), ptr(wws), wws_bytes, aux.cuda_stream)
-                dn = torch.cuda.Event()
-                dn.record(aux)
-                done[l] = dn
-                keep_alive.append(ctx.layer_saved[l])
-                grads.done("layer%d" % l, ready=dn)
-            elif pair:
-                dyb = dys[l & 1]
-                add_out = dxa[l & 1] if l > 0 else None
-                s_in, s_out = _stream16_io(l)
-                call("timhip_layer_bwd_data_split", C.byref(desc), C.byref(ctx.lparams[l][0]), ptr(ctx.layer_saved[l]),
-                     ptr(s_in), ptr(add_in), ptr(s_out), ptr(add_out), ptr(dyb), C.byref(lg), ptr(ws), dws_bytes, st)
-                add_in = add_out
-                if pending is None and l > 0:
-                    pending = (l, lg)      # its weight gradients go out with layer l - 1's
-                elif pending is not None:
-                    lp, lgp = pending
-                    call("timhip_layer_bwd_weights_pair", C.byref(desc), ptr(ctx.xs_t[lp]), ptr(ctx.layer_saved[lp]), ptr(dys[lp & 1]),
-                         C.byref(lgp), ptr(ctx.xs_t[l]), ptr(ctx.layer_saved[l]), ptr(dyb), C.byref(lg), ptr(wws), wws_bytes, st)
-                    grads.done("layer%d" % lp)
-                    grads.done("layer%d" % l)
-                    ctx.layer_saved[lp] = None
-                    pending = None
-                else:                      # an odd layer count: layer 0 on its own
-                    call("timhip_layer_bwd_weights", C.byref(desc), ptr(ctx.xs_t[l]), ptr(ctx.layer_saved[l]), ptr(dyb),
-                         C.byref(lg), ptr(wws), wws_bytes, st)
-                    grads.done("layer%d" % l)
-            else:
-                add_out = dxa[l & 1] if l > 0 else None
-                s_in, s_out = _stream16_io(l)
-                call("timhip_layer_bwd_split", C.byref(desc), C.byref(ctx.lparams[l][0]), ptr(ctx.xs_t[l]),
-                     ptr(ctx.layer_saved[l]), ptr(s_in), ptr(add_in), ptr(s_out), ptr(add_out), C.byref(lg), ptr(ws), ws_bytes, st)
-                add_in = add_out
-                grads.done("layer%d" % l)
-            dx, dx2 = dx2, dx
-            if pending is None or pending[0] != l:
-                ctx.layer_saved[l] = None
-
-        # LayerNorm parameter gradients of all layers: one reduction of the saved per-block partials (sets: norm2, norm1 per layer)
-        dgs, dbs = [], []
-        for l in range(Lyr if defer_ln else 0):
-            pre = "%s.layers.%d." % (stack, l)
-            dgs += [G[pre + "norm2.weight"], G[pre + "norm1.weight"]]
-            dbs += [G[pre + "norm2.bias"], G[pre + "norm1.bias"]]
-        for i0 in range(0, len(dgs), 16):
-            call("timhip_ln_partials_reduce", ptr(ln_part) + (i0 // 2) * ln_part_bytes, len(dgs[i0:i0 + 16]), M, E,
-                 _parr(dgs[i0:i0 + 16]), _parr(dbs[i0:i0 + 16]), st)
-        del ln_part
-
-        # ---- sequence assembly backward
-        d_e = [None, None]
-        d_e_all = torch.empty((len(ctx.emb_saved) * B * nf, d), dtype=torch.float32, device=dev)   # (stacked like the forward's rows)
-        for i, (name, slot, *_) in enumerate(ctx.emb_saved):
-            d_e[slot] = d_e_all[i * B * nf:(i + 1) * B * nf]
-        d_te = torch.empty((B, T, d), dtype=torch.float32, device=dev)   # written in full by the kernel
-        # cls / modality gradients: atomics accumulate straight into the parameters' views of the (zero-filled) front-end bucket
-        d_cls = [G[fe + n].view(-1) for n in plan.cls_names]
-        d_mod = [G[fe + n].view(-1) for n in plan.mod_names]
-        call("timhip_assemble_bwd_p", ptr(plan.table(dev)), B, S, d, ptr(dx), nf, T, p_seq, seed, L.SITE_SEQ,
-             ptr(d_e[0]), ptr(d_e[1]), _parr(d_cls), len(d_cls), ptr(d_te), _parr(d_mod), len(d_mod), st)
-
-        # ---- embedders backward
-        d_inputs = {"visual": None, "audio": None}
-        emb_items = []
-        need_in = {"visual": ctx.needs_input_grad[3], "audio": ctx.needs_input_grad[4]}
-        R = B * nf
-        duT_all = rt.out_op(len(ctx.emb_saved) * R, d, dev)
-        if ctx.emb_pair is not None:   # both modalities' LayerNorm backward as one launch over the stacked rows
-            (n0, _, _, _, _, _, _), (n1, _, _, _, _, _, _) = ctx.emb_saved
-            u_all, stats_all = ctx.emb_pair
-            call("timhip_layernorm_bwd2", rt.prec, ptr(d_e_all), d, ptr(u_all), d, ptr(stats_all), 2 * R, d, 2,
-                 ptr(_f32c(P[fe + n0 + "_embedder.3.weight"])), R, ptr(_f32c(P[fe + n1 + "_embedder.3.weight"])), None, 0,
-                 ptr(duT_all), duT_all.stride(0), ptr(G[fe + n0 + "_embedder.3.weight"]), ptr(G[fe + n0 + "_embedder.3.bias"]),
-                 ptr(G[fe + n1 + "_embedder.3.weight"]), ptr(G[fe + n1 + "_embedder.3.bias"]), gs_in, st)
-        for i, (name, slot, xT, u, stats, Cin, site) in enumerate(ctx.emb_saved):
-            w = P[fe + name + "_embedder.1.weight"]
-            duT = duT_all[i * R:(i + 1) * R]
-            if ctx.emb_pair is None:
-                rt.ln_bwd(d_e[slot], u, stats, R, d, 2, _f32c(P[fe + name + "_embedder.3.weight"]), dyt=duT,
-                          dgamma=G[fe + name + "_embedder.3.weight"], dbeta=G[fe + name + "_embedder.3.bias"], t_scale=gs_in)
-            emb_items.append((duT, d, xT, Cin, R, G[fe + name + "_embedder.1.weight"], G[fe + name + "_embedder.1.bias"]))
-            if need_in[name]:
-                gx = torch.empty((R, Cin), dtype=torch.float32, device=dev)
-                rt.gemm(L.EPI_ADD_F32, duT, rt.weight(w, True), R, Cin, d, gx, Cin, acc_scale=gs_out)
-                dxin = torch.empty((R, Cin), dtype=torch.float32, device=dev)
-                call("timhip_dropout_rows_bwd", ptr(gx), R, Cin, Cin, ptr(dxin), Cin, p_feat, seed, site, st)
-                d_inputs[name] = dxin.view(B, nf, Cin)
-        rt.wgrad_many(emb_items, out_scale=gs_out)
-        del emb_items
+        chain = _Chain(q, k, stack, grads, dx, gs)
+        dx = _layers_bwd(chain, overlap)
+        _ln_partials_reduce(chain)
+        d_e_all, d_e, d_te = _assemble_bwd(q, k, dx, ctx.emb.mods)
+        d_inputs = _embedders_bwd(q, k, ctx.emb, d_e_all, d_e, {"visual": ctx.needs_input_grad[3], "audio": ctx.needs_input_grad[4]})
         grads.done("front")
         if overlap:
-            main.wait_stream(aux)  # all weight gradients are complete before autograd sees them
-        del keep_alive
+            torch.cuda.current_stream().wait_stream(rt.aux_stream(dev))  # all weight gradients are complete before autograd sees them
+            stack.saved[:] = [None] * len(stack.saved)   # (the side stream was reading them until here)
         if rt.finish_hook is not None:
             rt.finish_hook()
         out = [None, None, None, d_inputs["visual"], d_inputs["audio"], d_te if ctx.needs_input_grad[5] else None]
-        out += [G[n] if ctx.needs_input_grad[6 + i] else None for i, n in enumerate(names)]
+        out += [k.G[n] if ctx.needs_input_grad[6 + i] else None for i, n in enumerate(q.names)]
         return tuple(out)

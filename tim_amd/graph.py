@@ -90,7 +90,7 @@ class GraphedStep:
                 fn()
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
-        n_before = len(self.rt._gs_captured)   # (blocks of an earlier bare capture stay with the runtime)
+        n_before = self.rt.nonfinite.n_captured   # (blocks of an earlier bare capture stay with the runtime)
         self.kernel_nodes = self.nodes = None
         try:
             self.graph = torch.cuda.CUDAGraph(keep_graph=True) if count_nodes else torch.cuda.CUDAGraph()
@@ -124,7 +124,7 @@ class GraphedStep:
                 self.nodes = self.kernel_nodes = None
             self.graph.instantiate()
         # the gradient-scale blocks (non-finite flags) of the captured backward passes live and die with this object
-        self._gs_blocks = self.rt.adopt_captured(since=n_before)
+        self._flag_blocks = self.rt.adopt_captured(since=n_before)
         # the gradient tensors the captured backward writes: re-attached on every replay, so eager steps in between (which
         # may re-allocate .grad) do not detach the parameters from the graph's results
         self._grads = [(p, p.grad) for p in inner.parameters() if p.grad is not None]
@@ -133,7 +133,7 @@ class GraphedStep:
     def reset(self):
         """Drop the captured graph (before a re-capture with new shapes, or when the loop goes back to eager steps): its
         gradient-scale blocks are no longer watched by `Runtime.grads_finite()`."""
-        self._gs_blocks = []
+        self._flag_blocks = []
         self.graph = None
         self._grads = []
 

@@ -19,6 +19,7 @@ import math
 import torch
 
 from . import _lib as L
+from .functional import GS_FLAG_WORD, any_flag_set
 
 _TORCH_ONLY = ("amsgrad", "maximize", "foreach", "capturable", "differentiable", "fused", "decoupled_weight_decay")
 
@@ -98,7 +99,7 @@ class FusedAdamW(torch.optim.Optimizer):
         self._sig = None
         self._cpu_stats = None
         self.extra_flags = []    # 1-element 32-bit tensors: a non-zero word skips the step (a caller's own non-finite watch)
-        self._capture_since = 0  # GraphedStep: first of rt._gs_captured that belongs to the capture in progress
+        self._capture_since = 0  # GraphedStep: first of the runtime's captured flag blocks that belongs to the capture in progress
 
     @classmethod
     def for_model(cls, model, **kw):
@@ -203,18 +204,8 @@ class FusedAdamW(torch.optim.Optimizer):
                            L.OPT_SKIPPED: torch.tensor(self._steps[0]["skipped"], dtype=torch.int32)}
 
     def _copies_of(self, dev):
-        """data_ptr -> (cache key, plain, tr) of every operand copy the runtime holds on `dev`"""
-        out = {}
-        if self.rt is None:
-            return out
-        for key, ref in self.rt._wparams.items():
-            q, ent = ref(), self.rt._wcache.get(key)
-            if q is None or ent is None or q.device != dev or q.dim() != 2 or q.dtype != torch.float32 or not q.is_contiguous():
-                continue
-            N, K = q.shape
-            if ent[1].device == dev and ent[1].shape[0] == N and ent[2].shape[0] == K and ent[1].dtype == self.rt.op_dtype:
-                out[q.data_ptr()] = (key, ent[1], ent[2])
-        return out
+        """data_ptr -> (the runtime's parameter, plain, tr) of every operand copy the runtime holds on `dev`"""
+        return {} if self.rt is None else {q.data_ptr(): (q, plain, tr) for q, plain, tr in self.rt.copies.pairs(dev)}
 
     def _build(self, live, dev, copies):
         """the item tables (host arrays: they travel in the launches' arguments), one per group, and the partials buffer"""
@@ -233,10 +224,10 @@ class FusedAdamW(torch.optim.Optimizer):
                 if ent is None:
                     items.append(L.TimOptItem(p.data_ptr(), p.grad.data_ptr(), m.data_ptr(), v.data_ptr(), None, None, rows, cols, 0, 0))
                 else:
-                    key, plain, tr = ent
+                    q, plain, tr = ent
                     items.append(L.TimOptItem(p.data_ptr(), p.grad.data_ptr(), m.data_ptr(), v.data_ptr(), plain.data_ptr(),
                                               tr.data_ptr(), rows, cols, plain.shape[1], tr.shape[1]))
-                    keys.append((key, p, plain, tr))
+                    keys.append(ent)
             arr = (L.TimOptItem * max(1, len(items)))(*items)
             cnt = L.load().timhip_optim_norm_partials(C.cast(arr, C.c_void_p), len(items))
             L.check(min(cnt, 0), "timhip_optim_norm_partials")
@@ -267,21 +258,16 @@ class FusedAdamW(torch.optim.Optimizer):
                 raise ValueError("FusedAdamW.extra_flags: at most %d words" % L.OPT_MAX_FLAGS)
             return [f.data_ptr() for f in mine], mine
         if capturing:
-            blocks = list(rt._gs_captured[self._capture_since:])
-            extra = []
+            blocks, extra = rt.nonfinite.captured_from(self._capture_since), []
         else:
-            blocks, rt._gs_blocks = list(rt._gs_blocks), []
-            extra = []
-            if rt._nf_acc is not None:      # passes folded earlier for want of a reader
-                extra.append(rt._nf_acc.to(torch.int32).reshape(1))
-                rt._nf_acc = None
+            blocks, extra = rt.nonfinite.take()   # (extra: the passes folded earlier for want of a reader)
         blocks = [b for b in blocks if b.device == dev]
         extra += mine
         if len(blocks) + len(extra) > L.OPT_MAX_FLAGS:   # fold the surplus on the device
             keep = max(0, L.OPT_MAX_FLAGS - 1 - len(extra))
-            extra.append(torch.stack([b[4] for b in blocks[keep:]]).view(torch.int32).ne(0).any().to(torch.int32).reshape(1))
+            extra.append(any_flag_set(blocks[keep:]).to(torch.int32).reshape(1))
             blocks = blocks[:keep]
-        return [b.data_ptr() + 16 for b in blocks] + [e.data_ptr() for e in extra], blocks + extra
+        return [b.data_ptr() + 4 * GS_FLAG_WORD for b in blocks] + [e.data_ptr() for e in extra], blocks + extra
 
     def _step_gpu(self, live, dev):
         capturing = torch.cuda.is_current_stream_capturing()
@@ -330,29 +316,25 @@ class FusedAdamW(torch.optim.Optimizer):
         if rt is None:
             return
         for t in self._tables["groups"]:
-            for key, p, plain, tr in t["copies"]:
-                rt._wcache[key] = ((p.data_ptr(), p._version), plain, tr)
-        for k, ent in list(rt._wsplit.items()):
-            rt._wsplit[k] = (None, ent[1], ent[2])
+            for q, plain, tr in t["copies"]:
+                rt.copies.record(q, plain, tr)
+        rt.copies.invalidate(split_only=True)
 
     # ---- HIP-graph replay (tim_amd/graph.py: GraphedStep(..., optimizer=self)) ---------------------------------------------
     def before_capture(self, since):
         """Called by GraphedStep after its eager warm-up steps: the captured update writes the operand copies, so the cast at
         the head of the captured step is recorded only for what the update does not cover (split copies, weights outside the
-        optimizer); the flag words of the capture's own backward passes (rt._gs_captured[since:]) feed the captured update."""
+        optimizer); the flag words of the capture's own backward passes (the runtime's captured blocks from position `since`)
+        feed the captured update."""
         self._capture_since = since
         self._push_lr()
         rt = self.rt
         if rt is None:
             return
-        covered = {key: p for t in (self._tables["groups"] if self._tables else []) for key, p, _, _ in t["copies"]}
-        if any(rt._wcache[k][0] != (p.data_ptr(), p._version) for k, p in covered.items()):
-            rt._refresh(self._blocks.device)   # (a covered copy somebody invalidated by hand: rebuilt eagerly, once)
-        for k, ent in list(rt._wcache.items()):
-            if k not in covered:
-                rt._wcache[k] = (None, ent[1], ent[2])
-        for k, ent in list(rt._wsplit.items()):
-            rt._wsplit[k] = (None, ent[1], ent[2])
+        covered = [q for t in (self._tables["groups"] if self._tables else []) for q, _, _ in t["copies"]]
+        if not all(rt.copies.is_current(q) for q in covered):
+            rt.copies.refresh(self._blocks.device)   # (a covered copy somebody invalidated by hand: rebuilt eagerly, once)
+        rt.copies.invalidate(keep=covered)
 
     def before_replay(self):
         """the learning rate a scheduler wrote since the last replay, and a refresh of copies somebody invalidated between
@@ -362,16 +344,13 @@ class FusedAdamW(torch.optim.Optimizer):
         if rt is None or self._tables is None:
             return
         for t in self._tables["groups"]:
-            for key, p, _, _ in t["copies"]:
-                ent = rt._wcache.get(key)
-                if ent is None or ent[0] != (p.data_ptr(), p._version):
-                    rt._refresh(p.device)
+            for q, _, _ in t["copies"]:
+                if not rt.copies.is_current(q):
+                    rt.copies.refresh(q.device)
                     return
 
     def after_replay(self):
         """a replay moved the masters without touching any version counter: the split copies (refreshed at the head of the
         captured step, i.e. BEFORE its update) no longer match them for an eager forward that might follow"""
-        rt = self.rt
-        if rt is not None:
-            for k, ent in list(rt._wsplit.items()):
-                rt._wsplit[k] = (None, ent[1], ent[2])
+        if self.rt is not None:
+            self.rt.copies.invalidate(split_only=True)
