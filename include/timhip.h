@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define TIMHIP_VERSION 6   /* 6 (round 6): timhip_timing_stop_families; 5 (round 5): timhip_assemble_{fwd,bwd}_p (token / modality vectors by pointer), timhip_dx_init_slabs, timhip_det_side_loss_{fwd,bwd}, timhip_sigmoid_bwd_rows, timhip_time_l1_fwd_split3, timhip_gather_split3_ranges, TIMHIP_EPI_RELU_SPLIT3_T, timhip_layernorm_{fwd,bwd}2, timhip_cast_rows_pair; 4 (round 4): 8-word timhip_grad_scale block + non-finite flag, TIMHIP_DESC_STREAM16*, timhip_dx_init, timhip_reload_env */
+#define TIMHIP_VERSION 6   /* 6, additive (no layout or signature change, so no new number): timhip_stack_infer, timhip_stack_infer_workspace_bytes, timhip_attention_fwd_rows, TIMHIP_EPI_GELU_T, lse = NULL in timhip_attention_fwd; 6 (round 6): timhip_timing_stop_families; 5 (round 5): timhip_assemble_{fwd,bwd}_p (token / modality vectors by pointer), timhip_dx_init_slabs, timhip_det_side_loss_{fwd,bwd}, timhip_sigmoid_bwd_rows, timhip_time_l1_fwd_split3, timhip_gather_split3_ranges, TIMHIP_EPI_RELU_SPLIT3_T, timhip_layernorm_{fwd,bwd}2, timhip_cast_rows_pair; 4 (round 4): 8-word timhip_grad_scale block + non-finite flag, TIMHIP_DESC_STREAM16*, timhip_dx_init, timhip_reload_env */
 
 enum {
   TIMHIP_OK = 0,
@@ -78,9 +78,11 @@ enum {
                                    backward multiplies with, so that its epilogue (TIMHIP_EPI_MULAUX_T) needs no erf / exp and
                                    no second look at the dropout mask */
   TIMHIP_EPI_MULAUX_T = 12,     /* out0(T) = acc * aux(T) */
-  TIMHIP_EPI_RELU_SPLIT3_T = 13 /* v = relu(acc + bias) as the split operand [hi | lo | hi]: out0(T)[m, n] = T(v), [m, ld1 + n] = T(v - hi),
+  TIMHIP_EPI_RELU_SPLIT3_T = 13,/* v = relu(acc + bias) as the split operand [hi | lo | hi]: out0(T)[m, n] = T(v), [m, ld1 + n] = T(v - hi),
                                    [m, 2 ld1 + n] = T(v); ld1 = the block width (a multiple of 64), ld0 = the row stride (3 ld1) - what
                                    timhip_split3_many (mode 0, relu) makes of the fp32 output, without the round trip (time MLP) */
+  TIMHIP_EPI_GELU_T = 14        /* out0(T) = gelu(acc + bias): linear1 of an evaluation forward - no out1, no mask, no dropout; the bits
+                                   TIMHIP_EPI_GELU_DROP_G2 writes to out0 at p_drop = 0, from the same kernels at the same shapes */
 };
 
 /* Shape of one call.  M = B*S rows flow through the encoder. */
@@ -369,8 +371,14 @@ int timhip_layernorm_bwd2(int precision, const float* dx, int lddx, const float*
                           float* dgamma, float* dbeta, float* dgamma2, float* dbeta2, const float* t_scale, void* stream);
 
 /* structured attention over qkv[B*S, 3E] (T): token i attends to the F feature tokens and to
- * itself.  o[B*S,E] (T), lse[B,H,S] fp32. */
+ * itself.  o[B*S,E] (T), lse[B,H,S] fp32 (only the backward reads it: NULL skips the store). */
 int timhip_attention_fwd(const TimDesc* d, const void* qkv, void* o, float* lse, void* stream);
+/* The same for the token rows s0 <= s < S of every window only, written compactly: o_rows[b * (S - s0) + (s - s0), :] (T).  Keys
+ * and values still come from the full qkv; no lse, no dropout (d->p_drop must be 0: TIMHIP_EINVAL).  Every row goes through the
+ * arithmetic of the full kernel in the same key order - the rows of o_rows equal rows s0 .. S - 1 of timhip_attention_fwd's o
+ * bit for bit; 32-row blocks that lie wholly below s0 are not run.  With s0 = F: the query rows, all the last layer of an
+ * evaluation forward needs once nobody reads `feats` (timhip_stack_infer, tail_only). */
+int timhip_attention_fwd_rows(const TimDesc* d, const void* qkv, int s0, void* o_rows, void* stream);
 /* ABI 6: keep-bits of the attention dropout of `nlayers` encoder layers in ONE launch, written into the layers' saved blocks
  * (saved[l] = the block timhip_layer_fwd of layer l will fill; field TIMHIP_SAVED_ATTN_KEEP_BITS: per (window, head, token row)
  * two 64-bit words, word g bit 4 c + t = key 8 c + 4 g + t kept, keys 0 .. 127 - the order in which the MFMA attention
@@ -453,6 +461,21 @@ int timhip_layer_fwd(const TimDesc* d, const TimLayerParams* w, const float* x_i
 int timhip_layer_fwd_chained(const TimDesc* d, const TimLayerParams* w, const TimLayerParams* prev_w,
                              const void* prev_saved, const void* x_in_T, float* x_out, void* x_out_T, void* saved,
                              void* stream);
+/* Evaluation forward of a whole stack of `nlayers` post-norm layers of one shape, out of ONE arena whose size does not depend on
+ * nlayers (at most timhip_layer_saved_bytes plus one fp32 and one operand-dtype [B S, E] row buffer): per layer the launches of
+ * timhip_layer_fwd / timhip_layer_fwd_chained in evaluation arithmetic (d->p_drop must be 0: TIMHIP_EINVAL), minus the stores
+ * only a backward reads - attention without lse, linear1 through TIMHIP_EPI_GELU_T.  The TIMHIP_DESC_*_SPLIT flags of
+ * d->reserved are honoured as there.  layers[l]: the parameters of layer l.  x_in (fp32) / x_in_T (T): the [B S, E] input rows.
+ *   tail_only = 0: x_out (fp32, may be NULL) and x_out_T (T) are [B S, E] - the values timhip_layer_fwd of the last layer writes.
+ *   tail_only = 1: the last layer runs its in-projection on all rows and everything behind it on the B (S - F) query rows only
+ *     (timhip_attention_fwd_rows with s0 = F; the residual rows gathered): x_out / x_out_T are compact, [B (S - F), E], row
+ *     b (S - F) + (s - F) = token s of window b.  A token's row depends on the feature rows' keys and values and on itself,
+ *     so these are the rows tail_only = 0 computes, up to the tiles the GEMMs pick at the smaller row count.  S == F: TIMHIP_EINVAL.
+ * TIMHIP_EWORKSPACE when workspace_bytes < timhip_stack_infer_workspace_bytes(d, nlayers, tail_only).  Launches only: one stream,
+ * no events - capturable as a linear graph. */
+size_t timhip_stack_infer_workspace_bytes(const TimDesc* d, int nlayers, int tail_only);
+int timhip_stack_infer(const TimDesc* d, int nlayers, const TimLayerParams* layers, const float* x_in, const void* x_in_T,
+                       float* x_out, void* x_out_T, int tail_only, void* workspace, size_t workspace_bytes, void* stream);
 /* dx_out: gradient w.r.t. the layer output (fp32 [M,E], clobbered).  dx_in: gradient w.r.t. the
  * layer input (fp32 [M,E]).  Parameter gradients are accumulated (+=) into *g. */
 int timhip_layer_bwd(const TimDesc* d, const TimLayerParams* w, const void* x_in_T,
@@ -537,7 +560,8 @@ int timhip_assemble_bwd_p(const TimSeqRow* rows, int B, int S, int d, const floa
                           float* d_te, float* const* d_mod, int nmod, void* stream);
 
 /* ---- heads ------------------------------------------------------------------ */
-/* rows_T[B*n, E] (T) = x_T[b, s0 + i, :] for i < n : gathers the query rows a head reads */
+/* rows_T[B*n, E] (T) = x_T[b, s0 + i, :] for i < n : gathers the query rows a head reads (any E > 0; E % 4 == 0 moves 4 elements
+ * per access - with TIMHIP_PREC_FP32 as the element type also the fp32 rows and [rows, 2] statistics of the evaluation tail) */
 int timhip_gather_rows(int precision, const void* x_T, int B, int S, int E, int s0, int n,
                        void* rows_T, void* stream);
 /* dx[b, s0+i, :] += d_rows[b*n+i, :]  (fp32) */

@@ -15,7 +15,8 @@ PRECISIONS = {"bf16": PREC_BF16, "bf16x3": PREC_BF16X3, "fp32": PREC_FP32, "fp16
 H16 = (PREC_BF16, PREC_F16)   # 16-bit operand storage (the MFMA GEMM / attention / transposing weight-gradient kernels)
 
 (EPI_STORE_T, EPI_RELU_T, EPI_STORE_F32, EPI_GELU_DROP_T2, EPI_DROP_RES_F32, EPI_ADD_F32,
- EPI_DGELU_T, EPI_DRELU_T, EPI_ATOMIC_F32, EPI_SIGMOID_F32, EPI_DRELU_F32IN_T, EPI_GELU_DROP_G2, EPI_MULAUX_T, EPI_RELU_SPLIT3_T) = range(14)
+ EPI_DGELU_T, EPI_DRELU_T, EPI_ATOMIC_F32, EPI_SIGMOID_F32, EPI_DRELU_F32IN_T, EPI_GELU_DROP_G2, EPI_MULAUX_T, EPI_RELU_SPLIT3_T,
+ EPI_GELU_T) = range(15)
 
 # dropout site ids (csrc/common.h)
 SITE_FEAT_V, SITE_FEAT_A, SITE_SEQ = 1, 2, 3
@@ -110,6 +111,7 @@ _SIGS = {
     "timhip_layernorm_bwd": (C.c_int, [i32, vp, i32, vp, i32, vp, i32, i32, i32, vp, vp, i32, vp, i32,
                                        f32, u64, u32, vp, vp, vp, vp]),
     "timhip_attention_fwd": (C.c_int, [C.POINTER(TimDesc), vp, vp, vp, vp]),
+    "timhip_attention_fwd_rows": (C.c_int, [C.POINTER(TimDesc), vp, i32, vp, vp]),
     "timhip_attention_bwd": (C.c_int, [C.POINTER(TimDesc), vp, vp, vp, vp, vp, vp, sz, vp]),
     "timhip_attention_bwd_workspace_bytes": (sz, [C.POINTER(TimDesc)]),
     "timhip_time_l1_fwd": (C.c_int, [i32, vp, i32, i32, vp, vp, vp, i32, vp]),
@@ -120,6 +122,8 @@ _SIGS = {
     "timhip_layer_fwd": (C.c_int, [C.POINTER(TimDesc), C.POINTER(TimLayerParams), vp, vp, vp, vp, vp, vp, sz, vp]),
     "timhip_layer_fwd_chained": (C.c_int, [C.POINTER(TimDesc), C.POINTER(TimLayerParams), C.POINTER(TimLayerParams), vp, vp, vp,
                                            vp, vp, vp]),
+    "timhip_stack_infer_workspace_bytes": (sz, [C.POINTER(TimDesc), i32, i32]),
+    "timhip_stack_infer": (C.c_int, [C.POINTER(TimDesc), i32, C.POINTER(TimLayerParams), vp, vp, vp, vp, i32, vp, sz, vp]),
     "timhip_layer_bwd": (C.c_int, [C.POINTER(TimDesc), C.POINTER(TimLayerParams), vp, vp, vp, vp,
                                    C.POINTER(TimLayerGrads), vp, sz, vp]),
     "timhip_layer_bwd_split": (C.c_int, [C.POINTER(TimDesc), C.POINTER(TimLayerParams), vp, vp, vp, vp, vp, vp,

@@ -293,16 +293,31 @@ int timhip_wgrad(int precision, const void* dY, int ldy, int Nout, const void* X
 // (TimEpi.ln_*): a layer's input rows are LayerNorm-2 of the previous layer's y2, its inner residual LayerNorm-1 of its own
 // y1.  So the normalised fp32 rows are written only where someone else needs them (x_out of the last layer -> feats);
 // LayerNorm writes its bf16 operand copy and the statistics, 60 instead of 100 MB per launch.
-static int layer_fwd_impl(const TimDesc& d, const TimLayerParams* w, const float* x_in, const float* x_in_prenorm,
-                          const float* x_in_stats, const float* x_in_lnw, const float* x_in_lnb, const void* x_in_T,
-                          float* x_out, void* x_out_T, void* saved, hipStream_t s) {
-  int rc;
-  const int M = d.B * d.S, E = d.E, FF = d.FF, prec = d.precision;
+// One layer body for training and evaluation, parameterised by WHERE the intermediates live and WHICH stores exist:
+//   u == NULL      linear1 writes h only (TIMHIP_EPI_GELU_T) - nobody multiplies with gelu' in an evaluation forward
+//   lse == NULL    attention skips its log-sum-exp store
+//   s0 > 0         "tail": everything behind the in-projection runs on the token rows s0 .. S - 1 of every window only, compactly
+//                  (B (S - s0) rows: o, y1, x1t, h, y2, the outputs - and the residual rows the caller hands in)
+struct LayerBufs {
+  void* qkv; void* o; float* lse; float* y1; float* st1; void* x1t; void* u; void* h; float* y2; float* st2;
+  uint8_t* ffn_mask; const unsigned long long* attn_keep;
+};
+
+static LayerBufs saved_bufs(const TimDesc& d, void* saved) {
   const SavedLayout L = saved_layout(d);
   char* sv = (char*)saved;
-  void* qkv = sv + L.qkv; void* o = sv + L.o; float* lse = (float*)(sv + L.lse);
-  float* y1 = (float*)(sv + L.y1); float* st1 = (float*)(sv + L.st1); void* x1t = sv + L.x1t;
-  void* u = sv + L.u; void* h = sv + L.h; float* y2 = (float*)(sv + L.y2); float* st2 = (float*)(sv + L.st2);
+  return LayerBufs{sv + L.qkv, sv + L.o, (float*)(sv + L.lse), (float*)(sv + L.y1), (float*)(sv + L.st1), sv + L.x1t, sv + L.u,
+                   sv + L.h, (float*)(sv + L.y2), (float*)(sv + L.st2), (uint8_t*)(sv + L.ffn_mask),
+                   reinterpret_cast<const unsigned long long*>(sv + L.attn_keep)};
+}
+
+static int layer_fwd_body(const TimDesc& d, const TimLayerParams* w, const float* x_in, const float* x_in_prenorm,
+                          const float* x_in_stats, const float* x_in_lnw, const float* x_in_lnb, const void* x_in_T,
+                          float* x_out, void* x_out_T, const LayerBufs& bufs, int s0, hipStream_t s) {
+  int rc;
+  const int Mall = d.B * d.S, M = d.B * (d.S - s0), E = d.E, FF = d.FF, prec = d.precision;
+  void* qkv = bufs.qkv; void* o = bufs.o; float* y1 = bufs.y1; float* st1 = bufs.st1; void* x1t = bufs.x1t;
+  void* u = bufs.u; void* h = bufs.h; float* y2 = bufs.y2; float* st2 = bufs.st2;
 
   // 1. packed in-projection (F._in_projection_packed)
   // (a *_SPLIT flag: that weight pointer is a split copy [hi | lo | ..] with row stride 3 K; the product runs over 2 K with the
@@ -312,12 +327,11 @@ static int layer_fwd_impl(const TimDesc& d, const TimLayerParams* w, const float
   e.out0 = qkv; e.ld0 = 3 * E; e.bias = w->in_b;
   if (split(TIMHIP_DESC_INPROJ_SPLIT)) {
     e.a_wrap_k = E; e.reserved = 2;
-    if ((rc = tim_gemm_nt(prec, TIMHIP_EPI_STORE_T, x_in_T, E, w->in_w, 3 * E, M, 3 * E, 2 * E, e, 1, s))) return rc;
-  } else if ((rc = tim_gemm_nt(prec, TIMHIP_EPI_STORE_T, x_in_T, E, w->in_w, E, M, 3 * E, E, e, 1, s))) return rc;
-  // 2. structured attention
-  const unsigned long long* akeep = ((d.reserved & TIMHIP_DESC_ATTN_KEEP_BITS) && d.p_drop > 0.f)
-                                        ? reinterpret_cast<const unsigned long long*>(sv + L.attn_keep) : nullptr;
-  if ((rc = tim_attention_fwd(d, qkv, o, lse, s, akeep))) return rc;
+    if ((rc = tim_gemm_nt(prec, TIMHIP_EPI_STORE_T, x_in_T, E, w->in_w, 3 * E, Mall, 3 * E, 2 * E, e, 1, s))) return rc;
+  } else if ((rc = tim_gemm_nt(prec, TIMHIP_EPI_STORE_T, x_in_T, E, w->in_w, E, Mall, 3 * E, E, e, 1, s))) return rc;
+  // 2. structured attention (keys and values of all rows; the rows from s0 on)
+  const unsigned long long* akeep = ((d.reserved & TIMHIP_DESC_ATTN_KEEP_BITS) && d.p_drop > 0.f) ? bufs.attn_keep : nullptr;
+  if ((rc = tim_attention_fwd(d, qkv, o, bufs.lse, s, akeep, s0))) return rc;
   // 3. out-projection + dropout1 + residual
   e = epi0();
   e.out0 = y1; e.ld0 = E; e.bias = w->out_b; e.ldres = E;
@@ -327,7 +341,7 @@ static int layer_fwd_impl(const TimDesc& d, const TimLayerParams* w, const float
     e.res = x_in_prenorm; e.ln_stats = x_in_stats; e.ln_w = x_in_lnw; e.ln_b = x_in_lnb;
   }
   e.p_drop = d.p_drop; e.seed = d.seed; e.site = layer_site(d.layer, SITE_L_DROP1);
-  uint8_t* fmask = d.p_drop > 0.f ? (uint8_t*)(sv + L.ffn_mask) : nullptr;
+  uint8_t* fmask = d.p_drop > 0.f ? bufs.ffn_mask : nullptr;
   // TIMHIP_FUSE_LN=1 (round 3, opt-in): the LayerNorm that follows the out-projection / linear2 inside the GEMM's epilogue
   // (gemm_nt_ldln_kernel: the column tiles of a row panel exchange row statistics); the stand-alone LayerNorm stays behind it as
   // a launch that exits at once unless a tile's wait timed out.  Falls back to the two kernels wherever the shape does not fit.
@@ -353,15 +367,19 @@ static int layer_fwd_impl(const TimDesc& d, const TimLayerParams* w, const float
                               layer_site(d.layer, SITE_L_FFN), fused1 ? ln_run_if : nullptr))) return rc;
   // 5. linear1 + GELU(erf) + dropout
   e = epi0();
-  e.out0 = h; e.ld0 = FF; e.out1 = u; e.ld1 = FF; e.bias = w->l1_b;
-  e.p_drop = d.p_drop; e.seed = d.seed; e.site = layer_site(d.layer, SITE_L_FFN);
-  e.mask = fmask; e.ldmask = FF / 8;
+  e.out0 = h; e.ld0 = FF; e.bias = w->l1_b;
   // (out1 = `u` holds dropmask * gelu'(linear1 output): the factor the backward multiplies with - it never needs the
-  //  pre-activations themselves, so its epilogue is a plain multiply)
+  //  pre-activations themselves, so its epilogue is a plain multiply; no `u`: no backward, h alone)
+  const int epi1 = u ? TIMHIP_EPI_GELU_DROP_G2 : TIMHIP_EPI_GELU_T;
+  if (u) {
+    e.out1 = u; e.ld1 = FF;
+    e.p_drop = d.p_drop; e.seed = d.seed; e.site = layer_site(d.layer, SITE_L_FFN);
+    e.mask = fmask; e.ldmask = FF / 8;
+  }
   if (split(TIMHIP_DESC_L1_SPLIT)) {
     e.a_wrap_k = E; e.reserved = 2;
-    if ((rc = tim_gemm_nt(prec, TIMHIP_EPI_GELU_DROP_G2, x1t, E, w->l1_w, 3 * E, M, FF, 2 * E, e, 1, s))) return rc;
-  } else if ((rc = tim_gemm_nt(prec, TIMHIP_EPI_GELU_DROP_G2, x1t, E, w->l1_w, E, M, FF, E, e, 1, s))) return rc;
+    if ((rc = tim_gemm_nt(prec, epi1, x1t, E, w->l1_w, 3 * E, M, FF, 2 * E, e, 1, s))) return rc;
+  } else if ((rc = tim_gemm_nt(prec, epi1, x1t, E, w->l1_w, E, M, FF, E, e, 1, s))) return rc;
   // 6. linear2 + dropout2 + residual
   e = epi0();
   e.out0 = y2; e.ld0 = E; e.bias = w->l2_b; e.ldres = E;
@@ -385,6 +403,12 @@ static int layer_fwd_impl(const TimDesc& d, const TimLayerParams* w, const float
                            fused2 ? ln_run_if : nullptr);
 }
 
+static int layer_fwd_impl(const TimDesc& d, const TimLayerParams* w, const float* x_in, const float* x_in_prenorm,
+                          const float* x_in_stats, const float* x_in_lnw, const float* x_in_lnb, const void* x_in_T,
+                          float* x_out, void* x_out_T, void* saved, hipStream_t s) {
+  return layer_fwd_body(d, w, x_in, x_in_prenorm, x_in_stats, x_in_lnw, x_in_lnb, x_in_T, x_out, x_out_T, saved_bufs(d, saved), 0, s);
+}
+
 int timhip_layer_fwd(const TimDesc* dp, const TimLayerParams* w, const float* x_in, const void* x_in_T, float* x_out,
                      void* x_out_T, void* saved, void* workspace, size_t workspace_bytes, void* stream) {
   (void)workspace; (void)workspace_bytes;   // kept in the signature: earlier versions staged norm1's fp32 rows there
@@ -403,6 +427,72 @@ int timhip_layer_fwd_chained(const TimDesc* dp, const TimLayerParams* w, const T
   const char* ps = (const char*)prev_saved;
   return layer_fwd_impl(*dp, w, nullptr, (const float*)(ps + L.y2), (const float*)(ps + L.st2), prev_w->n2_w, prev_w->n2_b,
                         x_in_T, x_out, x_out_T, saved, (hipStream_t)stream);
+}
+
+// ---- evaluation forward of the whole stack out of one arena (timhip_stack_infer) ---------------------------------------------
+// The arena holds ONE layer's intermediates - the fields of a saved block a forward itself reads (no lse, no u, no keep-bits) -
+// plus the operand-dtype rows between two layers and, for the query-row tail, the gathered residual rows.  One copy is enough:
+// a layer reads the previous layer's y2 / st2 (its residual, normalised by the out-projection epilogue) before its own linear2
+// rewrites them, and the previous layer's operand rows (its in-projection) before its own norm2 rewrites those.
+struct InferLayout { size_t qkv, o, y1, st1, x1t, h, y2, st2, xt, resg, stg, total; };
+static InferLayout infer_layout(const TimDesc& d, int tail_only) {
+  const size_t M = (size_t)d.B * d.S, Mt = (size_t)d.B * (d.S - d.F), ts = opsize(d.precision);
+  InferLayout L;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
+  L.qkv = take(M * 3 * d.E * ts);
+  L.o = take(M * d.E * ts);
+  L.y1 = take(M * d.E * 4);
+  L.st1 = take(M * 2 * 4);
+  L.x1t = take(M * d.E * ts);
+  L.h = take(M * d.FF * ts);
+  L.y2 = take(M * d.E * 4);
+  L.st2 = take(M * 2 * 4);
+  L.xt = take(M * d.E * ts);
+  L.resg = take(tail_only ? Mt * d.E * 4 : 0);   // fp32 residual rows of the tail's query rows (pre-norm, or x_in's own)
+  L.stg = take(tail_only ? Mt * 2 * 4 : 0);      // their LayerNorm statistics
+  L.total = off;
+  return L;
+}
+
+size_t timhip_stack_infer_workspace_bytes(const TimDesc* d, int nlayers, int tail_only) {
+  (void)nlayers;   // (in the signature for the caller's sake: the arena is one layer's, whatever the depth)
+  return (d && check_layer_desc(*d) == TIMHIP_OK) ? infer_layout(*d, tail_only).total : 0;
+}
+
+int timhip_stack_infer(const TimDesc* dp, int nlayers, const TimLayerParams* layers, const float* x_in, const void* x_in_T,
+                       float* x_out, void* x_out_T, int tail_only, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!dp || !layers || nlayers <= 0 || !x_in || !x_in_T || !x_out_T || !workspace) return TIMHIP_EINVAL;
+  TimDesc d = *dp;
+  int rc = check_layer_desc(d);
+  if (rc) return rc;
+  if (d.p_drop != 0.f || (tail_only && d.S == d.F)) return TIMHIP_EINVAL;
+  const InferLayout L = infer_layout(d, tail_only);
+  if (workspace_bytes < L.total) return TIMHIP_EWORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  char* ws = (char*)workspace;
+  const LayerBufs bufs{ws + L.qkv, ws + L.o, nullptr, (float*)(ws + L.y1), (float*)(ws + L.st1), ws + L.x1t, nullptr, ws + L.h,
+                       (float*)(ws + L.y2), (float*)(ws + L.st2), nullptr, nullptr};
+  d.reserved &= ~TIMHIP_DESC_ATTN_KEEP_BITS;
+  for (int l = 0; l < nlayers; ++l) {
+    const bool last = l == nlayers - 1;
+    const int s0 = (last && tail_only) ? d.F : 0;
+    d.layer = l;
+    // the residual of the out-projection: the caller's fp32 rows (first layer), LayerNorm-2 of the previous layer's y2 otherwise
+    const float* res = l == 0 ? x_in : nullptr;
+    const float* pre = l == 0 ? nullptr : bufs.y2;
+    const float* pst = l == 0 ? nullptr : bufs.st2;
+    if (s0) {   // the tail reads them by compact row index: gather the query rows (fp32; pre-norm rows with their statistics)
+      float* resg = (float*)(ws + L.resg); float* stg = (float*)(ws + L.stg);
+      if ((rc = timhip_gather_rows(TIMHIP_PREC_FP32, l == 0 ? x_in : pre, d.B, d.S, d.E, s0, d.S - s0, resg, stream))) return rc;
+      if (l > 0 && (rc = timhip_gather_rows(TIMHIP_PREC_FP32, pst, d.B, d.S, 2, s0, d.S - s0, stg, stream))) return rc;
+      if (l == 0) res = resg; else { pre = resg; pst = stg; }
+    }
+    const void* in_T = l == 0 ? x_in_T : (const void*)(ws + L.xt);
+    if ((rc = layer_fwd_body(d, &layers[l], res, pre, pst, l ? layers[l - 1].n2_w : nullptr, l ? layers[l - 1].n2_b : nullptr, in_T,
+                             last ? x_out : nullptr, last ? x_out_T : (void*)(ws + L.xt), bufs, s0, s))) return rc;
+  }
+  return TIMHIP_OK;
 }
 
 // gradient operands handed from the data chain to the weight-gradient part: df[M,E] | du[M,FF] | da[M,E] | dqkv[M,3E]

@@ -13,6 +13,7 @@ namespace {
 
 struct AttnArgs {
   int S, F, E, H, Dh, LP;  // LP = round_up(F + 1, 8): row pitch of the probability dropout stream
+  int s0;                  // first token row computed and stored; rows land compactly, S - s0 per window (0: all rows)
   float scale;
   uint32_t thr; float dscale; TimSeed seed; uint32_t site;
 };
@@ -46,7 +47,7 @@ __global__ __launch_bounds__(256) void attn_fwd_simple(const T* __restrict__ qkv
     sV[j * KS + c] = base[(size_t)j * ld + 2 * E + c];
   }
   __syncthreads();
-  for (int r0 = 0; r0 < S; r0 += 4) {
+  for (int r0 = a.s0; r0 < S; r0 += 4) {
     const int row = r0 + wave;
     const bool active = row < S;
     const T* qp = base + (size_t)(active ? row : 0) * ld;
@@ -82,7 +83,7 @@ __global__ __launch_bounds__(256) void attn_fwd_simple(const T* __restrict__ qkv
     const float pself_un = isq ? __expf(sself - mx) : 0.f;
     sum = wave_sum(sum) + pself_un;
     const float inv = 1.f / sum;
-    if (active && lane == 0) lse[((size_t)b * a.H + h) * S + row] = mx + __logf(sum);
+    if (active && lane == 0 && lse) lse[((size_t)b * a.H + h) * S + row] = mx + __logf(sum);
 #pragma unroll
     for (int kk = 0; kk < KPL; ++kk) {
       const int j = lane + 64 * kk;
@@ -95,7 +96,7 @@ __global__ __launch_bounds__(256) void attn_fwd_simple(const T* __restrict__ qkv
         float acc = 0.f;
         for (int j = 0; j < F; ++j) acc = fmaf(sP[wave * PP + j], OpT<T>::to_f(sV[j * KS + c]), acc);
         if (isq) acc = fmaf(pself, OpT<T>::to_f(qp[2 * E + c]), acc);
-        o[((size_t)b * S + row) * E + (size_t)h * Dh + c] = OpT<T>::from_f(acc);
+        o[((size_t)b * (S - a.s0) + (row - a.s0)) * E + (size_t)h * Dh + c] = OpT<T>::from_f(acc);
       }
     }
     __syncthreads();
@@ -218,6 +219,7 @@ AttnArgs make_args(const TimDesc& d) {
   a.thr = d.p_drop > 0.f ? drop_threshold(d.p_drop) : 0u;
   a.dscale = d.p_drop > 0.f ? 1.f / (1.f - d.p_drop) : 1.f;
   a.seed = d.seed; a.site = layer_site(d.layer, SITE_L_ATTN);
+  a.s0 = 0;
   return a;
 }
 
@@ -236,35 +238,36 @@ int check_desc(const TimDesc& d) {
 
 }  // namespace
 
-int tim_attention_fwd_mfma(const TimDesc& d, const void* qkv, void* o, float* lse, hipStream_t s, const unsigned long long* kbits);
+int tim_attention_fwd_mfma(const TimDesc& d, const void* qkv, void* o, float* lse, hipStream_t s, const unsigned long long* kbits, int s0);
 int tim_attention_bwd_mfma(const TimDesc& d, const void* qkv, const void* o, const float* lse, const void* d_o,
                            void* dqkv, hipStream_t s);
 int tim_attention_bwd2_mfma(const TimDesc& d, const void* qkv, const void* o, const float* lse, const void* d_o,
                             void* dqkv, void* ws, size_t ws_bytes, hipStream_t s, const unsigned long long* kbits);
 size_t tim_attention_bwd2_ws(const TimDesc& d);
 // attention_f32.hip: exact-fp32 MFMA kernels for the fp32 / bf16x3 modes
-int tim_attention_fwd_f32(const TimDesc& d, const void* qkv, void* o, float* lse, hipStream_t s);
+int tim_attention_fwd_f32(const TimDesc& d, const void* qkv, void* o, float* lse, hipStream_t s, int s0);
 int tim_attention_bwd_f32(const TimDesc& d, const void* qkv, const void* o, const float* lse, const void* d_o, void* dqkv,
                           void* ws, size_t ws_bytes, hipStream_t s);
 size_t tim_attention_f32_bwd_ws(const TimDesc& d);
 
-int tim_attention_fwd(const TimDesc& d, const void* qkv, void* o, float* lse, hipStream_t s, const unsigned long long* kbits) {
+int tim_attention_fwd(const TimDesc& d, const void* qkv, void* o, float* lse, hipStream_t s, const unsigned long long* kbits, int s0) {
   int rc = check_desc(d);
   if (rc) return rc;
-  if (!qkv || !o || !lse) return TIMHIP_EINVAL;
+  if (!qkv || !o || s0 < 0 || s0 >= d.S) return TIMHIP_EINVAL;
   // (bench.py's non-GEMM brackets: qkv read, o written, in the operand type)
   TimGemmScope timing((double)d.B * d.S * d.E * 4 * (h16_storage(d.precision) ? 2 : 4), s, 1);
   if (h16_storage(d.precision) && !(d.reserved & 1)) {  // reserved bit 0: force the fp32-arithmetic kernels
-    rc = tim_attention_fwd_mfma(d, qkv, o, lse, s, kbits);
+    rc = tim_attention_fwd_mfma(d, qkv, o, lse, s, kbits, s0);
     if (rc != TIMHIP_EUNSUPPORTED) return rc;
   }
   if (f32_storage(d.precision) && !(d.reserved & 1)) {   // fp32 / bf16x3: f32 matrix cores
-    rc = tim_attention_fwd_f32(d, qkv, o, lse, s);
+    rc = tim_attention_fwd_f32(d, qkv, o, lse, s, s0);
     if (rc != TIMHIP_EUNSUPPORTED) return rc;
   }
   const size_t lds = simple_lds(d, 1);
   if (lds > 160 * 1024) return TIMHIP_EUNSUPPORTED;
   AttnArgs a = make_args(d);
+  a.s0 = s0;
   DISPATCH_T(d.precision,
     (void)hipFuncSetAttribute((const void*)attn_fwd_simple<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(attn_fwd_simple<T>, dim3(d.B * d.H), dim3(256), lds, s, (const T*)qkv, (T*)o, lse, a));
@@ -320,6 +323,10 @@ int timhip_attention_bwd(const TimDesc* d, const void* qkv, const void* o, const
                          void* dqkv, void* workspace, size_t workspace_bytes, void* stream) {
   if (!d) return TIMHIP_EINVAL;
   return tim_attention_bwd(*d, qkv, o, lse, d_o, dqkv, workspace, workspace_bytes, (hipStream_t)stream);
+}
+int timhip_attention_fwd_rows(const TimDesc* d, const void* qkv, int s0, void* o_rows, void* stream) {
+  if (!d || d->p_drop != 0.f) return TIMHIP_EINVAL;
+  return tim_attention_fwd(*d, qkv, o_rows, nullptr, (hipStream_t)stream, nullptr, s0);
 }
 size_t timhip_attention_bwd_workspace_bytes(const TimDesc* d) { return d ? tim_attention_bwd_ws(*d) : 0; }
 }

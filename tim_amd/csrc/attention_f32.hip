@@ -18,6 +18,7 @@ namespace {
 
 struct AttnArgsF {
   int S, F, E, H, LP;
+  int s0;   // forward: first token row computed and stored; rows land compactly, S - s0 per window (0: all rows)
   float scale;
   uint32_t thr; float dscale; TimSeed seed; uint32_t site;
 };
@@ -114,12 +115,13 @@ __global__ __launch_bounds__(512) void attn_fwd_f32(const float* __restrict__ qk
   const int li = lane & 31, g = lane >> 5;
   const size_t ld = (size_t)3 * E;
   const float* base = qkv + (size_t)b * S * ld + (size_t)h * DH;
-  const int nrb = (S + 31) >> 5, npass = (nrb + nwaves - 1) / nwaves;
+  const int rb0 = a.s0 >> 5;                     // (row blocks wholly below s0 are not run)
+  const int nrb = (S + 31) >> 5, npass = (nrb - rb0 + nwaves - 1) / nwaves;
   for (int pass = 0; pass < npass; ++pass) {     // every wave takes part in every barrier
-    const int rb = pass * nwaves + wave;
+    const int rb = rb0 + pass * nwaves + wave;
     const bool work = rb < nrb;
     const int row = rb * 32 + li;
-    const bool valid = work && row < S;
+    const bool valid = work && row < S && row >= a.s0;
     const int rowc = valid ? row : S - 1;
     const bool isq = rowc >= F;
     const float* qp = base + (size_t)rowc * ld;
@@ -162,7 +164,7 @@ __global__ __launch_bounds__(512) void attn_fwd_f32(const float* __restrict__ qk
     const float pself_un = isq ? expf((sself - mx) * a.scale) : 0.f;
     sum += pself_un;
     const float inv = 1.f / sum;
-    if (valid && g == 0) lse[((size_t)b * a.H + h) * S + row] = mx * a.scale + logf(sum);
+    if (valid && g == 0 && lse) lse[((size_t)b * a.H + h) * S + row] = mx * a.scale + logf(sum);
     const uint64_t rowbase = (((uint64_t)b * a.H + h) * S + rowc) * (uint64_t)a.LP;
 #pragma unroll
     for (int jb = 0; jb < NJB; ++jb)
@@ -178,7 +180,7 @@ __global__ __launch_bounds__(512) void attn_fwd_f32(const float* __restrict__ qk
     __syncthreads();                             // K tile no longer needed
     stage_f32<DH>(tile, base + 2 * E, ld, FP, F, tid, blockDim.x);
     __syncthreads();
-    float* op = o + ((size_t)b * S + rowc) * E + (size_t)h * DH;
+    float* op = o + ((size_t)b * (S - a.s0) + (valid ? row - a.s0 : 0)) * E + (size_t)h * DH;
 #pragma unroll 1
     for (int db = 0; db < NDB; ++db) {
       f32x16_t oa;
@@ -399,17 +401,20 @@ AttnArgsF make_args_f(const TimDesc& d) {
   a.thr = d.p_drop > 0.f ? drop_threshold(d.p_drop) : 0u;
   a.dscale = d.p_drop > 0.f ? 1.f / (1.f - d.p_drop) : 1.f;
   a.seed = d.seed; a.site = layer_site(d.layer, SITE_L_ATTN);
+  a.s0 = 0;
   return a;
 }
 
 static inline int waves_for(int S) { const int n = (S + 31) / 32; return n < 1 ? 1 : (n > 8 ? 8 : n); }
 
 template <int DH, int NJB>
-int launch_fwd(const TimDesc& d, const void* qkv, void* o, float* lse, hipStream_t s) {
+int launch_fwd(const TimDesc& d, const void* qkv, void* o, float* lse, hipStream_t s, int s0) {
   const size_t lds = (size_t)NJB * 32 * DH * 4;
+  AttnArgsF a = make_args_f(d);
+  a.s0 = s0;
   (void)hipFuncSetAttribute((const void*)attn_fwd_f32<DH, NJB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((attn_fwd_f32<DH, NJB>), dim3(d.B * d.H), dim3(64 * waves_for(d.S)), lds, s, (const float*)qkv,
-                     (float*)o, lse, make_args_f(d));
+  hipLaunchKernelGGL((attn_fwd_f32<DH, NJB>), dim3(d.B * d.H), dim3(64 * waves_for(d.S - (s0 & ~31))), lds, s, (const float*)qkv,
+                     (float*)o, lse, a);
   return hipGetLastError() == hipSuccess ? TIMHIP_OK : TIMHIP_ELAUNCH;
 }
 
@@ -447,8 +452,8 @@ size_t tim_attention_f32_bwd_ws(const TimDesc& d) {
   }                                                                                                                    \
   return TIMHIP_EUNSUPPORTED;
 
-int tim_attention_fwd_f32(const TimDesc& d, const void* qkv, void* o, float* lse, hipStream_t s) {
-#define FWD(DHc, NJBc) return launch_fwd<DHc, NJBc>(d, qkv, o, lse, s)
+int tim_attention_fwd_f32(const TimDesc& d, const void* qkv, void* o, float* lse, hipStream_t s, int s0) {
+#define FWD(DHc, NJBc) return launch_fwd<DHc, NJBc>(d, qkv, o, lse, s, s0)
   F32_DISPATCH(FWD)
 #undef FWD
 }

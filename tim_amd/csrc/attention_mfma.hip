@@ -27,6 +27,8 @@ struct AttnArgsM {
   float scale;
   uint32_t thr; float dscale; TimSeed seed; uint32_t site;
   int rsplit, rper;   // the 32-row blocks of a (window, head) are spread over rsplit workgroups of rper row blocks each (1: one workgroup)
+  int s0;             // forward: first token row computed and stored (0: all).  Row blocks keep their 32-row alignment - the grid
+                      // starts at block s0 / 32 - and rows land compactly in o, S - s0 per window (timhip_attention_fwd_rows)
   const unsigned long long* kbits;   // keep-bits drawn ahead of the layer (tim_attn_keep_bits; round 6), or nullptr
 };
 
@@ -87,7 +89,8 @@ __global__ __launch_bounds__(512) void attn_fwd_mfma(const HT* __restrict__ qkv,
   const size_t ld = (size_t)3 * E;
   const HT* base = qkv + (size_t)b * S * ld + (size_t)h * DH;
   const int li = lane & 31, g = lane >> 5;
-  const int nrb = min((S + 31) >> 5, (part + 1) * a.rper);
+  const int rb0 = a.s0 >> 5;
+  const int nrb = min((S + 31) >> 5, rb0 + (part + 1) * a.rper);
   const int nwaves = blockDim.x >> 6;
   // (five key blocks - F > 128 - hold 80 score registers per lane: no room for operands in flight, the requests stay where
   //  they are consumed)
@@ -110,8 +113,8 @@ __global__ __launch_bounds__(512) void attn_fwd_mfma(const HT* __restrict__ qkv,
   // one 32-row block of queries; qf / kself: its q rows and (query tokens) own-key rows, already requested
   auto row_block = [&](int rb, vec8<HT> (&qf)[NKK], vec8<HT> (&kself)[NKK]) {
     const int row = rb * 32 + li;
-    const bool valid = row < S;
-    const int rowc = valid ? row : S - 1;
+    const bool valid = row < S && row >= a.s0;   // (rows of the first block below s0: computed like the padding rows, not stored)
+    const int rowc = row < S ? row : S - 1;
     const bool isq = rowc >= F;
     const HT* qp = base + (size_t)rowc * ld;
     unsigned long long kw = 0ull;   // KB: this lane's keep-bits, bit 4 c + t = key 8 c + 4 g + t (requested ahead of the products)
@@ -172,7 +175,7 @@ __global__ __launch_bounds__(512) void attn_fwd_mfma(const HT* __restrict__ qkv,
     const float pself_un = isq ? __builtin_amdgcn_exp2f(fmaf(sself, c2, -mc)) : 0.f;
     sum += pself_un;
     const float inv = 1.f / sum;
-    if (valid && g == 0) lse[((size_t)b * a.H + h) * S + row] = mx * a.scale + __logf(sum);
+    if (valid && g == 0 && lse) lse[((size_t)b * a.H + h) * S + row] = mx * a.scale + __logf(sum);
     const uint64_t rowbase = (((uint64_t)b * a.H + h) * S + rowc) * (uint64_t)a.LP;
 #pragma unroll
     for (int jb = 0; jb < NJB; ++jb)
@@ -212,7 +215,7 @@ __global__ __launch_bounds__(512) void attn_fwd_mfma(const HT* __restrict__ qkv,
       for (int kk = 0; kk < NKK; ++kk) vself[kk] = *reinterpret_cast<const vec8<HT>*>(qp + 2 * E + kk * 16 + g * 8);
     }
     constexpr int NH = NDB >= 2 ? 2 : 1, DBH = NDB / NH;
-    HT* op = o + ((size_t)b * S + rowc) * E + (size_t)h * DH;
+    HT* op = o + ((size_t)b * (S - a.s0) + (valid ? row - a.s0 : 0)) * E + (size_t)h * DH;
 #pragma unroll
     for (int hh = 0; hh < NH; ++hh) {
       f32x16_t oa[DBH];
@@ -255,7 +258,7 @@ __global__ __launch_bounds__(512) void attn_fwd_mfma(const HT* __restrict__ qkv,
 
   // The wave's first row block is peeled out of the loop: its operands were requested before the K / V staging, and keeping
   // them in registers of their own (not loop-carried) is what lets the compiler fit the kernel without spills.
-  int rb = part * a.rper + wave;
+  int rb = rb0 + part * a.rper + wave;
   if constexpr (!PRE) {   // the plain loop: operands requested where they are consumed
     stage_tile<DH>(sK, base + E, ld, FP, F, tid, blockDim.x);
     stage_tile<DH>(sV, base + 2 * E, ld, FP, F, tid, blockDim.x);
@@ -531,14 +534,15 @@ AttnArgsM make_args(const TimDesc& d) {
   a.dscale = d.p_drop > 0.f ? 1.f / (1.f - d.p_drop) : 1.f;
   a.seed = d.seed; a.site = layer_site(d.layer, SITE_L_ATTN);
   a.rsplit = 1; a.rper = (d.S + 31) / 32;
+  a.s0 = 0;
   a.kbits = nullptr;
   return a;
 }
 
 // Row split of a (window, head): enough workgroups for two per CU (512) when B * H alone does not provide them, each with at
 // least `waves_min` row blocks (one per wave).  C4 training (B = 16, H = 8, S = 499: 16 row blocks): 4 parts of 4 row blocks.
-static inline void attn_row_split(const TimDesc& d, int waves_min, int& rsplit, int& rper) {
-  const int nrb = (d.S + 31) / 32, bh = d.B * d.H;
+static inline void attn_row_split(const TimDesc& d, int s0, int waves_min, int& rsplit, int& rper) {
+  const int nrb = (d.S + 31) / 32 - s0 / 32, bh = d.B * d.H;
   int want = bh >= 512 ? 1 : (512 + bh - 1) / bh;
   const int most = nrb / (waves_min < 1 ? 1 : waves_min);
   if (want > most) want = most;
@@ -561,12 +565,13 @@ static inline int attn_waves(int S) {
 }
 
 template <typename HT, int DH, int NJB>
-int launch_fwd(const TimDesc& d, const void* qkv, void* o, float* lse, hipStream_t s, const unsigned long long* kbits) {
+int launch_fwd(const TimDesc& d, const void* qkv, void* o, float* lse, hipStream_t s, const unsigned long long* kbits, int s0) {
   const size_t lds = (size_t)2 * NJB * 32 * DH * 2;
   AttnArgsM a = make_args(d);
+  a.s0 = s0;
   // (few windows - B * H < 128, e.g. C2a at 8 windows per GPU - leave most CUs without a block: split down to TIMHIP_ATTN_SPLIT_MIN
   //  row blocks per workgroup there; default 4 = one per wave of a full block)
-  attn_row_split(d, d.B * d.H < 128 ? tim_knobs().attn_split_min : 4, a.rsplit, a.rper);
+  attn_row_split(d, s0, d.B * d.H < 128 ? tim_knobs().attn_split_min : 4, a.rsplit, a.rper);
   if constexpr (DH == 128 && NJB == 4) {   // (the keep-bit form exists for the geometry tim_attn_keep_bits serves: C2a / C3 / C4)
     if (kbits && a.thr != 0u) {
       a.kbits = kbits;
@@ -652,9 +657,9 @@ int launch_bwd(const TimDesc& d, const void* qkv, const void* o, const float* ls
     return TIMHIP_EUNSUPPORTED;                                                  \
   } while (0)
 
-int tim_attention_fwd_mfma(const TimDesc& d, const void* qkv, void* o, float* lse, hipStream_t s, const unsigned long long* kbits) {
+int tim_attention_fwd_mfma(const TimDesc& d, const void* qkv, void* o, float* lse, hipStream_t s, const unsigned long long* kbits, int s0) {
   if (!h16_storage(d.precision) || (d.E % 8) != 0) return TIMHIP_EUNSUPPORTED;
-  DISPATCH_H16(d.precision, ATTN_DISPATCH(launch_fwd, d, qkv, o, lse, s, kbits));
+  DISPATCH_H16(d.precision, ATTN_DISPATCH(launch_fwd, d, qkv, o, lse, s, kbits, s0));
   return TIMHIP_EUNSUPPORTED;
 }
 

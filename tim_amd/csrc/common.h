@@ -474,7 +474,10 @@ int tim_layernorm_bwd(int precision, const float* dx, int lddx, const float* y, 
 size_t tim_layernorm_bwd_ws(int rows, int cols);
 int tim_layernorm_bwd_blocks(int rows);   // partial rows one backward launch over `rows` rows writes
 // kbits (round 6): the layer's attention keep-bits as tim_attn_keep_bits wrote them (nullptr: the kernels draw their own)
-int tim_attention_fwd(const TimDesc& d, const void* qkv, void* o, float* lse, hipStream_t s, const unsigned long long* kbits = nullptr);
+// lse == nullptr: no log-sum-exp store (a forward without a backward).  s0 > 0: only the token rows s0 .. S - 1 of every window, written
+// compactly - o[b * (S - s0) + (s - s0), :] - with the per-row arithmetic of the full form (timhip_attention_fwd_rows)
+int tim_attention_fwd(const TimDesc& d, const void* qkv, void* o, float* lse, hipStream_t s, const unsigned long long* kbits = nullptr,
+                      int s0 = 0);
 int tim_attention_bwd(const TimDesc& d, const void* qkv, const void* o, const float* lse,
                       const void* d_o, void* dqkv, void* ws, size_t ws_bytes, hipStream_t s, const unsigned long long* kbits = nullptr);
 // attention_mfma.hip: keep-bits of layers first .. first + n - 1 (n <= 8) into out[i]: [B * H * S][2] 64-bit words

@@ -886,6 +886,7 @@ int tim_gemm_nt(int precision, int epi, const void* A, int lda, const void* B, i
     CASE(TIMHIP_EPI_GELU_DROP_G2)
     CASE(TIMHIP_EPI_MULAUX_T)
     CASE(TIMHIP_EPI_RELU_SPLIT3_T)
+    CASE(TIMHIP_EPI_GELU_T)
 #undef CASE
     default: return TIMHIP_EINVAL;
   }

@@ -73,6 +73,10 @@ __device__ __forceinline__ void epi_one(const EpiDev& e, int m, int n, int N, fl
     gelu_both_f(v, gl, dg);
     ((T*)e.out1)[(size_t)m * e.ld1 + n] = OpT<T>::from_f(dg * mask);
     ((T*)e.out0)[i0] = OpT<T>::from_f(gl * mask);
+  } else if (EPI == TIMHIP_EPI_GELU_T) {
+    float gl, dg;
+    gelu_both_f(v, gl, dg);
+    ((T*)e.out0)[i0] = OpT<T>::from_f(gl);
   } else if (EPI == TIMHIP_EPI_MULAUX_T) {
     ((T*)e.out0)[i0] = OpT<T>::from_f(v * OpT<T>::to_f(((const T*)e.aux)[(size_t)m * e.ldaux + n]));
   } else if (EPI == TIMHIP_EPI_DROP_RES_F32) {
@@ -150,6 +154,10 @@ __device__ __forceinline__ void epi_quad(const EpiDev& e, int m, int n, int N, f
       gelu_both_f(v0, g0, d0); gelu_both_f(v1, g1, d1); gelu_both_f(v2, g2, d2); gelu_both_f(v3, g3, d3);
       nt_store4<T>((T*)e.out1 + (size_t)m * e.ld1 + n, d0 * k0, d1 * k1, d2 * k2, d3 * k3);
       nt_store4<T>((T*)e.out0 + i0, g0 * k0, g1 * k1, g2 * k2, g3 * k3);
+    } else if (EPI == TIMHIP_EPI_GELU_T) {   // (gelu_both_f, its derivative dropped: the same bits GELU_DROP_G2 stores at p_drop = 0)
+      float g0, g1, g2, g3, d0, d1, d2, d3;
+      gelu_both_f(v0, g0, d0); gelu_both_f(v1, g1, d1); gelu_both_f(v2, g2, d2); gelu_both_f(v3, g3, d3);
+      nt_store4<T>((T*)e.out0 + i0, g0, g1, g2, g3);
     } else if (EPI == TIMHIP_EPI_MULAUX_T) {
       float u0, u1, u2, u3;
       load4<T>((const T*)e.aux + (size_t)m * e.ldaux + n, u0, u1, u2, u3);
@@ -224,7 +232,7 @@ __device__ __forceinline__ void static_for(F&& f) {
 constexpr bool epi_has_oct(int EPI) {
   return EPI == TIMHIP_EPI_STORE_T || EPI == TIMHIP_EPI_RELU_T || EPI == TIMHIP_EPI_GELU_DROP_T2 ||
          EPI == TIMHIP_EPI_DGELU_T || EPI == TIMHIP_EPI_DRELU_T || EPI == TIMHIP_EPI_GELU_DROP_G2 ||
-         EPI == TIMHIP_EPI_MULAUX_T;
+         EPI == TIMHIP_EPI_MULAUX_T || EPI == TIMHIP_EPI_GELU_T;
 }
 template <typename HT, bool NT = true>
 __device__ __forceinline__ void store8(HT* p, float4 lo, float4 hi) {
@@ -246,6 +254,11 @@ __device__ __forceinline__ float4 epi_math4(float4 v, float4 a, float4 k) {
   if (EPI == TIMHIP_EPI_DRELU_T)
     return make_float4(a.x > 0.f ? v.x : 0.f, a.y > 0.f ? v.y : 0.f, a.z > 0.f ? v.z : 0.f, a.w > 0.f ? v.w : 0.f);
   if (EPI == TIMHIP_EPI_MULAUX_T) return make_float4(v.x * a.x, v.y * a.y, v.z * a.z, v.w * a.w);
+  if (EPI == TIMHIP_EPI_GELU_T) {
+    float4 gl, dg;
+    gelu_both_f(v.x, gl.x, dg.x); gelu_both_f(v.y, gl.y, dg.y); gelu_both_f(v.z, gl.z, dg.z); gelu_both_f(v.w, gl.w, dg.w);
+    return gl;
+  }
   return v;
 }
 // 8 consecutive columns n..n+7 of row m for the epilogues that write bf16: ONE 16-byte store (and 16-byte aux load)
@@ -268,7 +281,7 @@ __device__ __forceinline__ void epi_oct(const EpiDev& e, int m, int n, int N, fl
   }
   const size_t i0 = (size_t)m * e.ld0 + n;
   if ((EPI == TIMHIP_EPI_STORE_T || EPI == TIMHIP_EPI_RELU_T || EPI == TIMHIP_EPI_GELU_DROP_T2 ||
-       EPI == TIMHIP_EPI_GELU_DROP_G2) && e.bias) {
+       EPI == TIMHIP_EPI_GELU_DROP_G2 || EPI == TIMHIP_EPI_GELU_T) && e.bias) {
     float4 b0 = pb0, b1 = pb1;
     if (!has_b) { b0 = *reinterpret_cast<const float4*>(e.bias + n); b1 = *reinterpret_cast<const float4*>(e.bias + n + 4); }
     lo.x += b0.x; lo.y += b0.y; lo.z += b0.z; lo.w += b0.w; hi.x += b1.x; hi.y += b1.y; hi.z += b1.z; hi.w += b1.w;

@@ -1069,7 +1069,7 @@ void launch_p8(const void* A, int lda, const void* B, int ldb, int M, int N, int
 static int p8_choice(int epi, int M, int N, int K, const EpiDev& e) {
   const int kn = tim_knobs().gemm_p8;
   if (kn == 0 || e.a_wrap != 0 || K % 64 || K < 128 || N % PP_BN || M < 1) return 0;
-  if (epi != TIMHIP_EPI_STORE_T && epi != TIMHIP_EPI_GELU_DROP_G2 && epi != TIMHIP_EPI_MULAUX_T) return 0;
+  if (epi != TIMHIP_EPI_STORE_T && epi != TIMHIP_EPI_GELU_DROP_G2 && epi != TIMHIP_EPI_GELU_T && epi != TIMHIP_EPI_MULAUX_T) return 0;
   if (kn == 8 || kn == 10) return kn;
   if (epi == TIMHIP_EPI_MULAUX_T && kn != 2) return 0;
   const long long t160 = (long long)((M + 159) / 160) * (N / PP_BN);
@@ -1700,6 +1700,7 @@ plain:
 #define CASE(X) case X: DISPATCH_H16(precision, (tm8 == 8 ? launch_p8<HT, X, 8>(A, lda, B, ldb, M, N, K, e, s) : launch_p8<HT, X, 10>(A, lda, B, ldb, M, N, K, e, s))); break;
       CASE(TIMHIP_EPI_STORE_T)
       CASE(TIMHIP_EPI_GELU_DROP_G2)
+      CASE(TIMHIP_EPI_GELU_T)
       CASE(TIMHIP_EPI_MULAUX_T)
 #undef CASE
       default: return TIMHIP_EUNSUPPORTED;
@@ -1714,6 +1715,7 @@ plain:
     CASE(TIMHIP_EPI_DROP_RES_F32)
     CASE(TIMHIP_EPI_ADD_F32)
     CASE(TIMHIP_EPI_GELU_DROP_G2)
+    CASE(TIMHIP_EPI_GELU_T)
     CASE(TIMHIP_EPI_MULAUX_T)
 #undef CASE
     default: return TIMHIP_EUNSUPPORTED;

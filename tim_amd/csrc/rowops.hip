@@ -949,6 +949,10 @@ __global__ void gather_rows_kernel(const T* __restrict__ xt, int B, int S, int E
   const int b = i / n, j = i % n;
   const T* src = xt + ((size_t)b * S + s0 + j) * E;
   T* dst = out + (size_t)i * E;
+  if (E & 3) {   // narrow rows (the [rows, 2] LayerNorm statistics of timhip_stack_infer's query-row tail): element by element
+    for (int c = threadIdx.x; c < E; c += blockDim.x) dst[c] = src[c];
+    return;
+  }
   for (int c = threadIdx.x * 4; c < E; c += blockDim.x * 4) {
     float a0, a1, a2, a3;
     load4<T>(src + c, a0, a1, a2, a3);
@@ -1651,7 +1655,7 @@ int timhip_assemble_bwd_p(const TimSeqRow* rows, int B, int S, int d, const floa
 }
 
 int timhip_gather_rows(int precision, const void* x_T, int B, int S, int E, int s0, int n, void* rows_T, void* stream) {
-  if (!x_T || !rows_T || n <= 0 || E % 4) return TIMHIP_EINVAL;
+  if (!x_T || !rows_T || n <= 0 || E <= 0) return TIMHIP_EINVAL;   // (E % 4 != 0: the element-wise form)
   DISPATCH_T(precision, hipLaunchKernelGGL(gather_rows_kernel<T>, dim3(B * n), dim3(256), 0, (hipStream_t)stream,
                                            (const T*)x_T, B, S, E, s0, n, (T*)rows_T));
   TIM_CHECK_LAUNCH();

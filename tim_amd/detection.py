@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from ._lib import call, ptr
-from .functional import EncoderFn, OUT_SLOTS, _require_gpu, _stream
+from .functional import OUT_SLOTS, _require_gpu, _stream, encoder
 from .tim import TIM as _TIMBase
 
 
@@ -150,7 +150,7 @@ class TIM(_TIMBase):
             a_queries = torch.flatten(a_queries, 0, 1)
 
         time_encodings = self._time_mlp(all_times)
-        outs = EncoderFn.apply(self, num_v, num_a, inputs[0], inputs[1], time_encodings, *self._encoder_param_list())
+        outs = encoder(self, num_v, num_a, inputs[0], inputs[1], time_encodings)
         o = dict(zip(OUT_SLOTS, outs))
         cls_scores = (o["verb"], o["noun"], o["action"], o["audio"])
         reg_scores = (o["reg_visual"], o["reg_audio"])

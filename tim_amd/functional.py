@@ -845,10 +845,11 @@ def _layers_fwd(q, P, desc, layer_saved, x0_f, x0_t):
     return _Stack(layer_saved, xs_t, lparams, desc.reserved & L.DESC_ATTN_KEEP_BITS), xL_f
 
 
-def _heads_fwd(q, P, xL_f, xL_t, outs):
+def _heads_fwd(q, P, xL_f, xL_t, outs, row0=0):
     """classification heads (head.py:17-38) -> [_Head].  fp16 model: the logits are produced with split operands from the fp32
-    rows of the last layer; the backward gathers the fp16 rows it needs itself"""
-    rt, dev, st, B, S, E = q.rt, q.dev, q.st, q.B, q.S, q.E
+    rows of the last layer; the backward gathers the fp16 rows it needs itself.  row0: the first token row xL holds (the
+    compact query rows of an evaluation forward without `feats`: F)"""
+    rt, dev, st, B, S, E = q.rt, q.dev, q.st, q.B, q.S - row0, q.E
     heads, gemms, ranges = [], [], []
     for slot, pname, s0, n in q.plan.heads:
         w = P["cls_head." + pname + ".weight"]
@@ -866,7 +867,7 @@ def _heads_fwd(q, P, xL_f, xL_t, outs):
             item = dict(A=rows, B=rt.weight(w), M=B * n, N=Cn, K=E, out0=logits, ld0=Cn, bias=bias) if n > 0 else None
             heads.append(_Head(slot, pname, s0, n, rows))
         if n > 0:
-            ranges.append((s0, n, rows))
+            ranges.append((s0 - row0, n, rows))
             gemms.append(item)
         outs[slot] = logits
     # the heads' row gathers and GEMMs are independent and tiny: one launch of each kind for all of them
@@ -881,8 +882,9 @@ def _heads_fwd(q, P, xL_f, xL_t, outs):
     return heads
 
 
-def _reg_heads_fwd(q, P, xL_t, outs):
-    """regression heads of the detection variant: Linear-ReLU-Linear-ReLU-Linear-sigmoid on the heads' query rows -> [_RegHead]"""
+def _reg_heads_fwd(q, P, xL_t, outs, row0=0):
+    """regression heads of the detection variant: Linear-ReLU-Linear-ReLU-Linear-sigmoid on the heads' query rows -> [_RegHead]
+    (row0: as in _heads_fwd)"""
     rt, dev, B, E = q.rt, q.dev, q.B, q.E
     hid = E // 2
     regs = []
@@ -893,7 +895,7 @@ def _reg_heads_fwd(q, P, xL_t, outs):
         h2 = rt.out_op(B * n, hid, dev)
         y = torch.empty((B * n, 2), dtype=torch.float32, device=dev)
         if n > 0:
-            call("timhip_gather_rows", rt.prec, ptr(xL_t), B, q.S, E, s0, n, ptr(rows), q.st)
+            call("timhip_gather_rows", rt.prec, ptr(xL_t), B, q.S - row0, E, s0 - row0, n, ptr(rows), q.st)
             rt.gemm(L.EPI_RELU_T, rows, rt.weight(P[pre + "0.weight"]), B * n, hid, E, h1, h1.shape[1],
                     bias=_f32c(P[pre + "0.bias"]))
             rt.gemm(L.EPI_RELU_T, h1, rt.weight(P[pre + "2.weight"]), B * n, hid, hid, h2, h2.shape[1],
@@ -1275,3 +1277,48 @@ class EncoderFn(torch.autograd.Function):
         out = [None, None, None, d_inputs["visual"], d_inputs["audio"], d_te if ctx.needs_input_grad[5] else None]
         out += [k.G[n] if ctx.needs_input_grad[6 + i] else None for i, n in enumerate(q.names)]
         return tuple(out)
+
+
+# ==================================================================================================
+# evaluation forward: the same stages, no backward to prepare for
+# ==================================================================================================
+def _infer_forward(model, nv, na, visual, audio, te):
+    """The encoder under `model.eval()` and no-grad (validation, feature extraction): the stages of `EncoderFn.forward` with the
+    layer stack as ONE library call out of one arena (timhip_stack_infer) - no saved blocks, no per-layer row buffers, no
+    stores only a backward reads, no autograd node; a single-stream chain of launches (capturable as a linear graph).
+    `model.eval_feats` (default True): every output is the training route's evaluation output bit for bit.  False: `feats`
+    is None and the last layer runs behind its in-projection on the query rows alone (tail_only); the heads read compact rows."""
+    rt, cfg = model.rt, model.cfg
+    _require_gpu(te, "encoder")
+    B, T, d = te.shape
+    if d != cfg.d_model:
+        raise ValueError("time encodings have width %d, model d_model is %d" % (d, cfg.d_model))
+    q = _Pass(model, model._plan(T, nv, na), te.device, B, T, False, 0)
+    P = dict(zip(q.names, model._encoder_param_list()))
+    _, e_bufs = _embedders_fwd(q, P, visual, audio)
+    x0_f, x0_t = _assemble_fwd(q, P, e_bufs, _f32c(te))
+    tail = not model.eval_feats and q.S > q.F
+    row0 = q.F if tail else 0
+    Lyr = cfg.num_layers
+    desc = L.TimDesc(q.B, q.S, q.F, q.d, q.E, cfg.nhead, cfg.FF, rt.prec, 0.0, 0, 0, rt.layer_split_flags(q.E, cfg.FF), None)
+    lparams = [model._layer_params(rt, P, "%s.layers.%d." % (model._stack_prefix, l)) for l in range(Lyr)]
+    layers = (L.TimLayerParams * Lyr)(*[lp[0] for lp in lparams])
+    rows = q.B * (q.S - row0)
+    xL_f = torch.empty((rows, q.E), dtype=torch.float32, device=q.dev)
+    xL_t = torch.empty((rows, q.E), dtype=rt.op_dtype, device=q.dev)
+    ws_bytes = L.load().timhip_stack_infer_workspace_bytes(C.byref(desc), Lyr, int(tail))
+    ws = model._workspace(ws_bytes, q.dev, slot="infer")
+    call("timhip_stack_infer", C.byref(desc), Lyr, layers, ptr(x0_f), ptr(x0_t), ptr(xL_f), ptr(xL_t), int(tail), ptr(ws), ws_bytes, q.st)
+    outs = {"feats": None if not model.eval_feats else xL_f.view(B, q.S, q.E)[:, :q.F]}
+    _heads_fwd(q, P, xL_f, xL_t, outs, row0)
+    _reg_heads_fwd(q, P, xL_t, outs, row0)
+    return tuple(outs.get(k) for k in OUT_SLOTS)
+
+
+def encoder(model, nv, na, visual, audio, te):
+    """The encoder of one call -> the 7 outputs (OUT_SLOTS; None if absent).  `model.eval()` with gradients off takes the
+    evaluation route (`_infer_forward`); everything else - training, or an evaluation somebody differentiates - the autograd
+    Function.  TIM_AMD_INFER=0: the Function everywhere (A/B switch)."""
+    if not model.training and not torch.is_grad_enabled() and os.environ.get("TIM_AMD_INFER", "1") != "0":
+        return _infer_forward(model, nv, na, visual, audio, te)
+    return EncoderFn.apply(model, nv, na, visual, audio, te, *model._encoder_param_list())

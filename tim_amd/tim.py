@@ -17,7 +17,7 @@ from torch.nn.init import normal_
 
 from . import _lib as L
 from .config import TimConfig
-from .functional import EncoderFn, EncoderPlan, Runtime, TimeMlpFn, OUT_SLOTS
+from .functional import EncoderPlan, Runtime, TimeMlpFn, OUT_SLOTS, encoder
 
 
 # ---- parameter containers, registered in the reference's order so that state_dict() key order matches ----
@@ -359,6 +359,9 @@ class TIM(nn.Module):
         self.pool = _AVGAParams(audio_input_dim, visual_input_dim, visual_input_dim) if pool_features else None
 
         self.rt = Runtime(precision)
+        # evaluation under no-grad (functional._infer_forward): False = nobody reads `feats` (validation, feature extraction) - the
+        # slot comes back None and the last layer's feature rows are not computed behind their keys and values
+        self.eval_feats = True
         self._plans = {}
         self._ws = {}
         self._ws_pinned = False   # set by GraphedStep: workspaces captured in a graph are never freed
@@ -476,8 +479,7 @@ class TIM(nn.Module):
     def forward_encoder(self, inputs, time_encodings, num_v_queries, num_a_queries):
         if self.pool is not None:
             inputs = [self.pool(inputs[1], inputs[0]), inputs[1]]
-        outs = EncoderFn.apply(self, int(num_v_queries or 0), int(num_a_queries or 0), inputs[0], inputs[1],
-                               time_encodings, *self._encoder_param_list())
+        outs = encoder(self, int(num_v_queries or 0), int(num_a_queries or 0), inputs[0], inputs[1], time_encodings)
         o = dict(zip(OUT_SLOTS, outs))
         return (o["verb"], o["noun"], o["action"], o["audio"]), o["feats"]
 
