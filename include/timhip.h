@@ -306,7 +306,9 @@ int timhip_gemm_nt(int precision, int epi, const void* A, int lda, const void* B
 int timhip_transpose(int precision, const void* src, int rows, int cols, int lds, void* dst, int ld,
                      void* stream);
 
-/* out[n] += sum_m src[m, n]  (T source, fp32 accumulate): bias gradients */
+/* out[n] += sum_m src[m, n]  (T source of row stride ld >= cols, fp32 accumulate): bias gradients.  ACCUMULATED: every block of 64
+ * rows ends in one float atomicAdd per column, so `out` keeps what it held (the caller zeroes it for a plain sum) and the order of
+ * the additions - the last bits of the result - is not fixed. */
 int timhip_colsum(int precision, const void* src, int rows, int cols, int ld, float* out,
                   void* stream);
 
@@ -404,7 +406,11 @@ int timhip_wgrad(int precision, const void* dY, int ldy, int Nout, const void* X
  * exactly 512 tiles = the chip's 512 block slots, the contraction is not split and dW / db are written directly, with no
  * partial slabs and no reduce.  accumulate = 0 writes dW / db instead of adding to them.  bf16 operands only (the fp32 and
  * bf16x3 modes go through timhip_wgrad); every Nout*Kout must be a multiple of 4.  items is a HOST array, copied into the
- * kernel arguments.  workspace may be NULL when timhip_wgrad_group_workspace_bytes returns 0. */
+ * kernel arguments.  workspace may be NULL when timhip_wgrad_group_workspace_bytes returns 0.
+ * Alignment, one rule for every kernel the group may run on (the plain tiles, the ping-pong grid, the eight-phase grid): ldy and
+ * ldx multiples of 8 elements, dY, X and dW 16-byte aligned - otherwise TIMHIP_EALIGN.  The whole group is checked on the host
+ * BEFORE any launch: a refused group has written nothing, whichever item was at fault.  A group that one of the tiled grids
+ * cannot address (M * ld * 2 bytes >= 2^32) runs on the plain tiles instead of being refused. */
 typedef struct TimWgradItem {
   const void* dY;   /* [M, ldy] */
   const void* X;    /* [M, ldx] */
@@ -543,14 +549,18 @@ int timhip_assemble_fwd(int precision, const TimSeqRow* rows /*device, [S]*/, in
                         const float* e0, const float* e1, int n_e_rows, const float* cls,
                         const float* te, int T, const float* mod, float p_seq_drop, uint64_t seed,
                         uint32_t site, float* x, void* x_T, void* stream);
-/* d_e0/d_e1 are written; d_cls, d_te, d_mod are accumulated (+=, must be zeroed by the caller) */
+/* d_e0 / d_e1 (either may be NULL) are WRITTEN: row (b, src) of every feature row the table names, no other row is touched.
+ * d_te (may be NULL) is WRITTEN in full, [B, T, d]: the sum over the token rows that read time row t, in table order, no atomics -
+ * zero for a time row no token row reads; the caller need not clear it.  d_cls and d_mod are ACCUMULATED (+=, float atomics, the
+ * order of the additions is not fixed): the caller zeroes them, or passes a gradient that is to be added to. */
 int timhip_assemble_bwd(const TimSeqRow* rows, int B, int S, int d, const float* dx, int n_e_rows,
                         int T, float p_seq_drop, uint64_t seed, uint32_t site, float* d_e0,
                         float* d_e1, float* d_cls, float* d_te, float* d_mod, void* stream);
 
 /* The same with the CLS token vectors (ncls <= 8, [d] each) and the modality vectors (nmod <= 4, [2 d] each) given by pointer:
  * host arrays of device pointers, 16-byte aligned - the separate nn.Parameters of encodings.py:29-35,158-175 as they lie (and, in
- * the backward, their gradient views: accumulated into, zeroed by the caller).  Saves the two concatenations of a forward and
+ * the backward, their gradient views: accumulated into, zeroed by the caller; a NULL entry of a gradient table means that
+ * gradient is not wanted - the forward refuses NULL or misaligned entries with TIMHIP_EALIGN before it launches).  Saves the two concatenations of a forward and
  * the copy back of a backward. */
 int timhip_assemble_fwd_p(int precision, const TimSeqRow* rows, int B, int S, int d, const float* e0, const float* e1,
                           int n_e_rows, const float* const* cls, int ncls, const float* te, int T, const float* const* mod,

@@ -376,6 +376,196 @@ def test_layernorm_fwd_bwd(prec, cols, act):
     assert (dbeta.cpu().double() - b64.grad).abs().max().item() <= 1e-4 * max(1.0, b64.grad.abs().max().item())
 
 
+@pytest.mark.parametrize("prec", ["bf16", "fp16"])
+@pytest.mark.parametrize("M", [2048, 256])   # a group the eight-phase grid takes (8 x 32 whole tiles, M >= 2048) and one it does not
+def test_wgrad_group_alignment_is_checked_before_any_launch(prec, M):
+    """include/timhip.h, timhip_wgrad_group: ldy / ldx multiples of 8 and 16-byte aligned dY / X / dW, one rule for every kernel the
+    group may run on, checked for the WHOLE group on the host before anything is launched (wgrad.hip: the loop at the top of
+    tim_wgrad_group_h16) - a refused group has written nothing, whichever item was at fault"""
+    rt = Runtime(prec)
+    N, K, n = 1024, 2048, 8
+    dY = torch.zeros((M, N + 8), dtype=rt.op_dtype, device=DEV)
+    X = torch.zeros((M, K + 8), dtype=rt.op_dtype, device=DEV)
+    dW = torch.full((n * N * K + 4,), float("nan"), device=DEV)
+    db = torch.full((n * N,), float("nan"), device=DEV)
+    ws = torch.empty(64 << 20, dtype=torch.uint8, device=DEV)
+    lib = L.load()
+
+    def group(bad_item, dw_shift=0, ldx=K):
+        arr = (L.TimWgradItem * n)()
+        for i in range(n):
+            sh, lx = (dw_shift, ldx) if i == bad_item else (0, K)
+            arr[i] = L.TimWgradItem(dY.data_ptr(), X.data_ptr(), dW.data_ptr() + 4 * (i * N * K + sh), db.data_ptr() + 4 * i * N, N, lx, N, K)
+        return arr
+
+    ealign = -5   # include/timhip.h: TIMHIP_EALIGN
+    assert lib.timhip_strerror(ealign).decode().startswith("pointer or leading dimension")
+    for bad in (0, 5, 7):
+        assert lib.timhip_wgrad_group(rt.prec, group(bad, dw_shift=2), n, M, 0, L.ptr(ws), ws.numel(), None, st()) == ealign   # dW 8-byte aligned
+        assert lib.timhip_wgrad_group(rt.prec, group(bad, ldx=K + 4), n, M, 0, L.ptr(ws), ws.numel(), None, st()) == ealign     # ldx % 8 != 0
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(dW).all()) and bool(torch.isnan(db).all())
+
+
+# ---- LayerNorm at its edges: block heights, slot counts, padded pitches, ill-conditioned rows, the dropout site ------------------
+def _bits_equal(a, b):
+    iv = {4: torch.int32, 2: torch.int16}
+    return torch.equal(a.contiguous().view(iv[a.element_size()]), b.contiguous().view(iv[b.element_size()]))
+
+
+def _ln_edge(prec, rows, cols, act=0, pad=0, ldt=None, y=None, p=0.0, t_scale=None, check_bwd=True):
+    """forward and backward of one LayerNorm against tests/rowops_ref.py; every matrix has row pitch cols + pad (the operand
+    copies `ldt`), the padding columns and two guard rows on either side start as NaN and must come back bit-identical.
+    u = 2^-24.  Forward bound: the row mean is a sum of <= 32 terms per lane and a 6-level wave tree, so it is within
+    Em = 40 u mean|x|; a centred value within Em + u |x|; the variance sum likewise (relative 40 u), rstd half of that; so
+    |out - ref| <= |w| rstd (Em + 2 u |x| + Ea) + |w| |xhat| 24 u + 2 u (|ref| + |b|), Ea = the activation's own error
+    (gelu: the erf approximation, 1.5e-7 absolute, common.h: 0.75e-7 |x|).  A one-pass variance E[x^2] - mean^2 misses this by
+    orders of magnitude on a row with mean 100 and deviation 0.1."""
+    from tests import rowops_ref as R
+    rt = Runtime(prec)
+    T, u, F64 = rt.op_dtype, 2.0 ** -24, torch.float64
+    ld = cols + pad
+    ldt = ld if ldt is None else ldt
+    y = rnd(rows, cols, seed=7) if y is None else y
+    w, b, dxo = 1 + 0.1 * rnd(cols, seed=8), 0.1 * rnd(cols, seed=9), rnd(rows, cols, seed=10)
+
+    def padded(src, ldm, dtype=torch.float32):
+        m = torch.full((rows + 4, ldm), float("nan"), dtype=dtype, device=DEV)
+        if src is not None:
+            m[2:2 + rows, :cols] = src.to(DEV).to(dtype)
+        return m, m[2:2 + rows]
+
+    def untouched(whole, before):
+        return _bits_equal(whole[:2], before[:2]) and _bits_equal(whole[2 + rows:], before[2 + rows:]) and \
+            _bits_equal(whole[2:2 + rows, cols:], before[2:2 + rows, cols:])
+
+    yb, yv = padded(y, ld)
+    wd, bd = w.to(DEV), b.to(DEV)
+    outs = []
+    for _ in range(2):
+        xfb, xf = padded(None, ld)
+        xtb, xt = padded(None, ldt, T)
+        stats = torch.full((rows, 2), float("nan"), device=DEV)
+        keep = (xfb.clone(), xtb.clone())
+        L.call("timhip_layernorm_fwd", rt.prec, L.ptr(yv), rows, cols, ld, act, L.ptr(wd), L.ptr(bd), L.ptr(xf), ld, L.ptr(xt), ldt,
+               L.ptr(stats), st())
+        torch.cuda.synchronize()
+        assert untouched(xfb, keep[0]) and untouched(xtb, keep[1])
+        outs.append((xf[:, :cols].clone(), xt[:, :cols].clone(), stats))
+    assert all(_bits_equal(a, c) for a, c in zip(outs[0], outs[1]))                       # no atomics: repeats bit for bit
+    xf, xt, stats = outs[0]
+    y64, w64, b64 = y.double(), w.double(), b.double()
+    ref, mean, rstd = R.layernorm(y64, w64, b64, act)
+    x = R.act(act, y64)
+    Ea = (0.75e-7 + 2 * u) * y64.abs() if act == 2 else 0.0
+    Em = 40 * u * x.abs().mean(-1, keepdim=True)
+    rs = rstd.unsqueeze(-1)
+    xhat = (x - mean.unsqueeze(-1)) * rs
+    lim = w64.abs() * rs * (Em + 2 * u * x.abs() + Ea) + w64.abs() * xhat.abs() * 24 * u + 2 * u * (ref.abs() + b64.abs())
+    err = (xf.cpu().double() - ref).abs()
+    assert bool((err <= lim).all()), ("fwd", (err - lim).max().item())
+    assert bool(((xt.float().cpu().double() - ref).abs() <= lim * 1.01 + HALF_ULP.get(prec, 0.0) * ref.abs()).all())
+    assert bool(((stats[:, 0].cpu().double() - mean).abs() <= Em.squeeze(-1) + u * mean.abs() + (Ea.mean(-1) if act == 2 else 0)).all())
+    assert bool(torch.isfinite(xf).all())
+    if not check_bwd:
+        return
+    # backward.  The kernel reads the forward's fp32 statistics, so the reference is taken at THOSE statistics' accuracy: every term
+    # of dy = rstd (g - mean(g) - xhat mean(g xhat)) g = dx w, is a sum of `cols` products (40 u of its absolute sum, as above) and
+    # xhat carries the forward's error e_x = rstd (Em + 2 u |x| + Ea) + 24 u |xhat|
+    dxb, dxv = padded(dxo, ld)
+    dyfb, dyf = padded(None, ld)
+    dytb, dyt = padded(None, ldt, T)
+    keep = (dyfb.clone(), dytb.clone())
+    dg, dbeta = torch.full((cols,), 0.5, device=DEV), torch.full((cols,), -0.25, device=DEV)    # accumulated: pre-filled
+    seed, site = 777, 21
+    ts = None
+    if t_scale is not None:
+        ts = torch.zeros(8, device=DEV)
+        ts[0] = t_scale
+    L.call("timhip_layernorm_bwd", rt.prec, L.ptr(dxv), ld, L.ptr(yv), ld, L.ptr(stats), rows, cols, act, L.ptr(wd), L.ptr(dyf), ld,
+           L.ptr(dyt), ldt, p, seed, site, L.ptr(dg), L.ptr(dbeta), L.ptr(ts), st())
+    torch.cuda.synchronize()
+    assert untouched(dyfb, keep[0]) and untouched(dytb, keep[1])
+    rdy, rdg, rdb = R.layernorm_bwd(y64, w64, dxo.double(), act)
+    g = dxo.double() * w64
+    e_x = rs * (Em + 2 * u * x.abs() + Ea) + 24 * u * xhat.abs()
+    m1, m2 = g.abs().mean(-1, keepdim=True), (g * xhat).abs().mean(-1, keepdim=True)
+    lim_dy = rs * (4 * u * g.abs() + 40 * u * m1 + xhat.abs() * 40 * u * m2 + e_x * m2 + xhat.abs() * (g.abs() * e_x).mean(-1, keepdim=True)) \
+        + 8 * u * rdy.abs() / (1.0 if act == 0 else 0.1)
+    if act != 0:      # act': gelu' within 4e-7 (erf 1.5e-7, exp 2 ulp), relu' exact away from 0
+        lim_dy = lim_dy * 1.2 + 4e-7 * rs * (g.abs() + m1 + xhat.abs() * m2)
+    err = (dyf[:, :cols].cpu().double() - rdy).abs()
+    assert bool((err <= lim_dy).all()), ("dy", (err - lim_dy).max().item())
+    # the operand-type output carries the dropout mask of (seed, site) at row pitch `cols` and t_scale; the fp32 output neither
+    k = torch.ones(rows, cols, dtype=F64)
+    if p > 0:
+        mk = torch.empty((rows, cols), dtype=torch.uint8, device=DEV)
+        L.call("timhip_dropout_mask", seed, site, p, rows, cols, L.ptr(mk), st())
+        torch.cuda.synchronize()
+        k = mk.cpu().double() / (1 - p)
+        assert 0.5 * (1 - p) < mk.float().mean().item() <= 1.0
+    f = (t_scale or 1.0)
+    want_t = rdy * k * f
+    err = (dyt[:, :cols].float().cpu().double() - want_t).abs()
+    assert bool((err <= (lim_dy * 1.01 + 2 * u * rdy.abs()) * k * f + HALF_ULP.get(prec, 0.0) * want_t.abs() + (2.0 ** -24 if prec == "fp16" else 0)).all()), "dy_T"
+    if p > 0:
+        assert bool((dyt[:, :cols].float().cpu()[k == 0] == 0).all())
+    # dgamma / dbeta: `rows` terms per column, fp32, block partials joined by atomics: (rows + blocks) u sum|terms| + the error of xhat
+    lim_g = (rows + rows // 4 + 8) * u * (0.5 + (dxo.double() * xhat).abs().sum(0)) + (dxo.double().abs() * e_x).sum(0)
+    lim_b = (rows + rows // 4 + 8) * u * (0.25 + dxo.double().abs().sum(0))
+    assert bool(((dg.cpu().double() - (0.5 + rdg)).abs() <= lim_g).all()), "dgamma"
+    assert bool(((dbeta.cpu().double() - (-0.25 + rdb)).abs() <= lim_b).all()), "dbeta"
+
+
+@pytest.mark.parametrize("prec", ["fp32", "fp16"])
+@pytest.mark.parametrize("rows", [1, 3, 4, 5, 1240, 9920, 12300])
+def test_layernorm_block_heights(prec, rows, knobs):
+    """cols = 1024, act = 0: 4 ... 20 rows per block of the backward and its ragged last block (1240 rows: 4 per block, 9920: 20,
+    12300: 20 by the balanced-round rule); forward, dy, dgamma, dbeta"""
+    _ln_edge(prec, rows, 1024)
+    if rows in (5, 1240):
+        for rpb in ("4", "24"):
+            knobs(TIMHIP_LN_RPB=rpb)
+            _ln_edge(prec, rows, 1024)
+
+
+@pytest.mark.parametrize("prec", ["fp32", "bf16", "fp16"])
+@pytest.mark.parametrize("cols", [4, 96, 260, 1000, 2048])
+@pytest.mark.parametrize("act", [0, 2])
+def test_layernorm_slot_counts(prec, cols, act):
+    """one to eight 256-column slots with a partial last slot; the 8-column forward at 2048"""
+    _ln_edge(prec, 37, cols, act=act)
+
+
+@pytest.mark.parametrize("prec", ["fp32", "fp16"])
+@pytest.mark.parametrize("cols", [96, 512, 1024])
+def test_layernorm_padded_pitches(prec, cols):
+    """every row pitch larger than cols; an operand pitch of cols + 4 (not a multiple of 8: the 8-column forward steps aside, the
+    result does not change)"""
+    _ln_edge(prec, 37, cols, pad=8)
+    _ln_edge(prec, 37, cols, pad=8, ldt=cols + 4, p=0.1, t_scale=2.0 ** -3)
+
+
+@pytest.mark.parametrize("cols", [260, 1024])
+def test_layernorm_ill_conditioned_rows(cols):
+    """mean 100 with deviation 0.1; a constant row (rstd = 1 / sqrt(eps), output = beta, finite gradients); 1e4-sized values
+    under gelu"""
+    rows = 9
+    y = 100.0 + 0.1 * rnd(rows, cols, seed=3)
+    y[4] = 3.25
+    _ln_edge("fp32", rows, cols, y=y)
+    _ln_edge("fp32", rows, cols, act=2, y=1e4 * rnd(rows, cols, seed=4))
+
+
+@pytest.mark.parametrize("prec", ["fp32", "bf16", "fp16"])
+@pytest.mark.parametrize("cols", [96, 1024])
+def test_layernorm_backward_dropout_site_and_scale(prec, cols):
+    """p = 0.1: the mask on the operand-type gradient is the one timhip_dropout_mask returns for (seed, site) at row pitch cols;
+    t_scale multiplies the operand-type output only"""
+    _ln_edge(prec, 77, cols, p=0.1)
+    _ln_edge(prec, 77, cols, p=0.1, t_scale=2.0 ** 5)
+
+
 def _attn_case(prec, B, S, F, H, Dh, p=0.0, seed=11):
     rt = Runtime(prec)
     E = H * Dh
@@ -437,7 +627,8 @@ def test_attention_dropout(prec):
 @pytest.mark.parametrize("prec", H16)
 @pytest.mark.parametrize("fused", ["1", "1-one-wave-per-row-block", "0"])
 @pytest.mark.parametrize("B,S,F,H,Dh,p", [(3, 155, 100, 2, 128, 0.1), (2, 125, 100, 1, 128, 0.0), (1, 160, 128, 2, 128, 0.1),
-                                          (2, 192, 97, 1, 128, 0.0), (2, 129, 128, 1, 128, 0.1), (1, 98, 97, 2, 128, 0.1)])
+                                          (2, 192, 97, 1, 128, 0.0), (2, 129, 128, 1, 128, 0.1), (1, 98, 97, 2, 128, 0.1),
+                                          (1, 176, 128, 2, 128, 0.1), (2, 192, 97, 1, 128, 0.1)])   # 160 < S <= 192 WITH dropout
 def test_attention_backward_fused_and_two_kernel(prec, fused, B, S, F, H, Dh, p, knobs):
     """the production-shape backward in its three forms: rows + keys kernels with the dS / P~ scratch (TIMHIP_ATTN_FUSED=0), and the
     one-kernel form that keeps dS / P~ in LDS (128-wide heads, 97..128 feature keys, S <= 192) with phase 1 as the pipeline over
