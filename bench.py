@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py — interval-queries/sec of the TIM encoder hot path (fwd+bwd) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--precision fp16|bf16|bf16x3|fp32] [--batch 64] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--precision fp16|bf16|bf16x3|fp32] [--batch 64] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: set-up, W warm-up steps, the K timed steps, the files of
+--dump-outputs, one JSON line.  `--full` adds every other measurement to that line (the step issued eagerly, per-launch roofline
+events, repeat sets, forward only, the gradient exchange's cost, parity against the CPU oracle, the bf16 mode, the further
+BASELINE.json configurations, the CPU baseline); the `--no-*` options drop single legs of a `--full` run.
 
 Workload (BASELINE.json configs[1] = SURVEY.md C2a): EPIC-100 audio-visual recognition,
 d_model 512 (E 1024), 6 layers, 8 heads, 50+50 feature tokens, 15 visual + 10 audio interval
@@ -12,8 +17,8 @@ to every parameter gradient, operand-copy refresh of the weights (as after an op
 and, for N > 1, the gradient exchange over RCCL (tim_amd/dp.py).  Inputs are resident in HBM before the timed region.
 
 The timed mode is `fp16` (fp16 MFMA operands, fp32 accumulation, split operands for the time MLP and the heads): the fastest
-mode whose per-query logits stay within north_star's 1e-3 of the fp32 reference arithmetic; that error is measured in this
-run (`parity`), and the plain-bf16 mode (faster by a few per cent, 1e-2 off) is reported beside it (`bf16_mode`).
+mode whose per-query logits stay within north_star's 1e-3 of the fp32 reference arithmetic; a `--full` run measures that error
+(`parity`) and reports the plain-bf16 mode (faster by a few per cent, 1e-2 off) beside it (`bf16_mode`).
 """
 import argparse
 import json
@@ -551,6 +556,9 @@ def main():
     ap.add_argument("--precision", default="fp16")
     ap.add_argument("--batch", type=int, default=64, help="windows per GPU")
     ap.add_argument("--workload", default="C2a")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps, measure everything else the line can carry: eager steps, roofline, repeat sets, forward "
+                         "only, exchange cost, parity, bf16 mode, secondary configurations, CPU baseline (minutes instead of seconds)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-extra-step", action="store_true",
@@ -574,6 +582,8 @@ def main():
                     help="behind the timed region, write what its last step computed (returned tensors + parameter gradients, rank 0) "
                          "as DIR/<name>.npy: at most 64 MB, larger arrays as a fixed sample; same arguments -> same inputs")
     args = ap.parse_args()
+    if not args.full:   # a plain run: every leg a --no-* option can drop is dropped, and so are the three gated on args.full below
+        args.no_cpu_baseline = args.no_roofline = args.no_extra_step = args.no_repeat = args.no_per_shape = args.no_secondary = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -680,7 +690,7 @@ def main():
     eager = None
     live = None
     fam = None
-    if mode == "graph":
+    if mode == "graph" and args.full:
         # the same step issued eagerly, right BEFORE the capture and the timed region: its wall-clock rate and host issue time (the
         # robustness margin the replay buys), and - in its last step - the per-launch HIP events of the roofline: a replayed graph
         # cannot carry events around individual launches; the kernels, their launch parameters and the stream are the eager
@@ -769,7 +779,7 @@ def main():
             dtr = t.item()
         repeat_ms.append(dtr / args.steps * 1e3)
     comm = None
-    if dp_on:
+    if dp_on and args.full:
         # what the gradient exchange costs the step: (a) the same steps with the exchange switched off (every rank, same
         # barriers; replays of a second captured graph when the timed steps were replays) -> exposed time = difference;
         # (b) one eager step with events on the comm stream -> its busy time and bus rate
@@ -988,7 +998,7 @@ def main():
     # `value`, which stays the eager number so that the roofline events above sit inside the timed region.  Measured in a CHILD
     # process (`--graph-child`): whatever a runtime does with a capture it dislikes - an exception, or a crash - the bench
     # line of this process is not at stake.
-    if rank == 0 and not dp_on and not args.no_graph and gstep is None:
+    if rank == 0 and not dp_on and not args.no_graph and gstep is None and args.full:
         import subprocess
         cmd = [sys.executable, os.path.abspath(__file__), "--graph-child", "--workload", args.workload, "--batch", str(B),
                "--precision", args.precision, "--steps", str(args.steps), "--warmup", str(args.warmup)]

@@ -18,7 +18,7 @@ def test_two_ranks_one_json_line():
     env = dict(os.environ, TIM_AMD_BENCH_SHARE_GPU="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29571", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--batch", "40", "--no-per-shape"]
+           "--batch", "40", "--full", "--no-per-shape"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=420)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -38,7 +38,7 @@ def test_data_parallel_step_as_graph_replay_on_one_rank():
     the ranks agreeing on replay-or-eager, the exchange-free comparison step captured as well.  One rank (TIM_AMD_BENCH_FORCE_DP=1:
     every collective a copy) is what a one-GPU box can run; the arithmetic of W > 1 is covered on gloo (tests/test_dp_gloo.py)."""
     env = dict(os.environ, TIM_AMD_BENCH_FORCE_DP="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29573")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--batch", "40", "--no-per-shape"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--batch", "40", "--full", "--no-per-shape"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=420)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -6,7 +6,7 @@ TAG=${1:-r05}
 OUT=/root/repo/gpurun_out/$TAG
 mkdir -p $OUT
 cd /root/repo
-timeout 900 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout 900 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 timeout 300 python tools/blas_ref.py > $OUT/blas_ref.txt 2>&1
 cd /tmp && export TMPDIR=/tmp
 B="python /root/repo/bench.py --no-cpu-baseline --no-extra-step --no-per-shape --no-secondary"
