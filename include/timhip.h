@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define TIMHIP_VERSION 6   /* 6, additive (no layout or signature change, so no new number): timhip_stack_infer, timhip_stack_infer_workspace_bytes, timhip_attention_fwd_rows, TIMHIP_EPI_GELU_T, lse = NULL in timhip_attention_fwd; 6 (round 6): timhip_timing_stop_families; 5 (round 5): timhip_assemble_{fwd,bwd}_p (token / modality vectors by pointer), timhip_dx_init_slabs, timhip_det_side_loss_{fwd,bwd}, timhip_sigmoid_bwd_rows, timhip_time_l1_fwd_split3, timhip_gather_split3_ranges, TIMHIP_EPI_RELU_SPLIT3_T, timhip_layernorm_{fwd,bwd}2, timhip_cast_rows_pair; 4 (round 4): 8-word timhip_grad_scale block + non-finite flag, TIMHIP_DESC_STREAM16*, timhip_dx_init, timhip_reload_env */
+#define TIMHIP_VERSION 6   /* 6, additive (no layout or signature change, so no new number): timhip_det_candidates_{count,emit}, timhip_stack_infer, timhip_stack_infer_workspace_bytes, timhip_attention_fwd_rows, TIMHIP_EPI_GELU_T, lse = NULL in timhip_attention_fwd; 6 (round 6): timhip_timing_stop_families; 5 (round 5): timhip_assemble_{fwd,bwd}_p (token / modality vectors by pointer), timhip_dx_init_slabs, timhip_det_side_loss_{fwd,bwd}, timhip_sigmoid_bwd_rows, timhip_time_l1_fwd_split3, timhip_gather_split3_ranges, TIMHIP_EPI_RELU_SPLIT3_T, timhip_layernorm_{fwd,bwd}2, timhip_cast_rows_pair; 4 (round 4): 8-word timhip_grad_scale block + non-finite flag, TIMHIP_DESC_STREAM16*, timhip_dx_init, timhip_reload_env */
 
 enum {
   TIMHIP_OK = 0,
@@ -697,6 +697,32 @@ int timhip_softnms_1d(const float* segs, const float* scores, const int32_t* gro
  * removed_scratch: N bytes. */
 int timhip_nms_1d(const float* segs, const int32_t* order, const int32_t* group_offsets, int n_groups, float iou_threshold,
                   uint8_t* removed_scratch, int32_t* keep, int32_t* count, void* stream);
+
+/* ---------------------------------------------------------------- detection candidates */
+/* The inference tail between the detection heads and the NMS, per batch and per head, as the reference computes it in
+ * detection/time_interval_machine/utils/meters.py (FeatureMeter.update) and detection/eval_detection/format_predictions.py
+ * (main): proposal r = w * Nq + q of window w becomes clamp(reg[r], 0, *max_time) * window_size (fp32) + window_start[w]
+ * (fp64), rounded to three decimals as numpy.round does on float64; it is kept iff its rounded width is > 0.  Class c of a
+ * kept proposal is a candidate iff score = (float)(1 / (1 + exp(-(double)logit))) > score_threshold (fp32 compare).
+ * Candidates are listed proposal by proposal and by ascending class inside a proposal; that order is part of the result.
+ *
+ * timhip_det_candidates_count: logits [R, C] fp32 with row stride ld_logits (elements, >= C: a head's slice needs no copy),
+ *   reg [R, 2] fp32, window_start [R / Nq] fp64, max_time: DEVICE pointer to one float (no host read).  Writes seg32 [R, 2]
+ *   (the rounded segment cast to fp32), seg_ok [R] (1: kept) and row_offsets [R + 1]: row r's candidates occupy output
+ *   slots [row_offsets[r], row_offsets[r + 1]), row_offsets[R] is their total.  Two launches (count, scan).
+ * timhip_det_candidates_emit: the same walk over the same logits; writes candidate k of row r at row_offsets[r] + k:
+ *   seg [N, 2], score [N], key [N] = video_index[w] * C + class, row [N] = r.  `capacity` = the number of candidates the four
+ *   output buffers hold; a slot at or beyond it (or beyond its row's range) is not written, so a worst-case-sized output
+ *   (R * C) makes the pair replayable in a HIP graph.  One launch.
+ * Neither call allocates, synchronises or reads device memory on the host.  R * C must fit in int32; R must be a multiple
+ * of Nq. */
+int timhip_det_candidates_count(const float* logits, int64_t ld_logits, const float* reg, const double* window_start,
+                                float window_size, const float* max_time, int R, int C, int Nq, float score_threshold,
+                                float* seg32, uint8_t* seg_ok, int32_t* row_offsets, void* stream);
+int timhip_det_candidates_emit(const float* logits, int64_t ld_logits, const float* seg32, const uint8_t* seg_ok,
+                               const int32_t* row_offsets, const int32_t* video_index, int R, int C, int Nq,
+                               float score_threshold, int64_t capacity, float* seg, float* score, int64_t* key,
+                               int32_t* row, void* stream);
 
 /* ---------------------------------------------------------------- sliding-window batch assembly */
 /* recognition datasets/sliding_window.py:341-421 (__getitem__) for a batch, on feature stores resident in HBM.

@@ -19,6 +19,9 @@ def __getattr__(name):  # lazy: importing the package must not require torch on 
     if name == "FusedAdamW":
         from .optim import FusedAdamW
         return FusedAdamW
+    if name == "DetectionCollector":
+        from .detect import DetectionCollector
+        return DetectionCollector
     if name == "optim":
         import importlib
         return importlib.import_module(".optim", __name__)

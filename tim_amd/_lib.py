@@ -155,6 +155,8 @@ _SIGS = {
     "timhip_softnms_1d_workspace_bytes": (C.c_size_t, [C.c_int64, i32]),
     "timhip_softnms_1d": (C.c_int, [vp, vp, vp, vp, i32, f32, f32, f32, i32, vp, vp, vp, vp, C.c_size_t, vp]),
     "timhip_nms_1d": (C.c_int, [vp, vp, vp, i32, f32, vp, vp, vp, vp]),
+    "timhip_det_candidates_count": (C.c_int, [vp, C.c_int64, vp, vp, f32, vp, i32, i32, i32, f32, vp, vp, vp, vp]),
+    "timhip_det_candidates_emit": (C.c_int, [vp, C.c_int64, vp, vp, vp, vp, i32, i32, i32, f32, C.c_int64, vp, vp, vp, vp, vp]),
     "timhip_window_gather": (C.c_int, [vp, i32, i32, vp, vp, i32, vp, i32, vp, vp, vp]),
     "timhip_window_times": (C.c_int, [vp, i32, vp, vp, i32, vp, vp, i32, vp, i32, vp, i32, vp, i32, vp, f32, vp, vp]),
     "timhip_gemm_timing_start": (C.c_int, [i32, C.c_double]),
