@@ -107,7 +107,7 @@ typedef struct TimDesc {
 /* TimDesc.reserved flags */
 #define TIMHIP_DESC_ATTN_FP32 1        /* run the attention in fp32 arithmetic (reference kernels) */
 #define TIMHIP_DESC_ATTN_BWD_ONE_KERNEL 2 /* single-kernel MFMA attention backward */
-#define TIMHIP_DESC_WGRAD_OVERWRITE 4  /* bf16 only: timhip_layer_bwd[_weights] WRITES the weight and bias gradients of the four
+#define TIMHIP_DESC_WGRAD_OVERWRITE 4  /* bf16 only: timhip_layer_bwd_split / _bwd_weights[_pair] WRITE the weight and bias gradients of the four
                                           Linears (dW = ..., not +=): those buffers need no zero fill and are not read */
 #define TIMHIP_DESC_WGRAD_SEPARATE 8   /* bf16 only: four timhip_wgrad launches per layer instead of the grouped one (A/B knob) */
 #define TIMHIP_DESC_OUTPROJ_SPLIT 16   /* forward, 16-bit precisions: TimLayerParams.out_w is a [E, ld >= 2E] SPLIT copy of the out-projection
@@ -482,8 +482,9 @@ int timhip_layer_fwd_chained(const TimDesc* d, const TimLayerParams* w, const Ti
 size_t timhip_stack_infer_workspace_bytes(const TimDesc* d, int nlayers, int tail_only);
 int timhip_stack_infer(const TimDesc* d, int nlayers, const TimLayerParams* layers, const float* x_in, const void* x_in_T,
                        float* x_out, void* x_out_T, int tail_only, void* workspace, size_t workspace_bytes, void* stream);
-/* dx_out: gradient w.r.t. the layer output (fp32 [M,E], clobbered).  dx_in: gradient w.r.t. the
- * layer input (fp32 [M,E]).  Parameter gradients are accumulated (+=) into *g. */
+/* dx_out: gradient w.r.t. the layer output (fp32 [M,E]).  dx_in: gradient w.r.t. the
+ * layer input (fp32 [M,E]).  Parameter gradients are accumulated (+=) into *g.
+ * This is timhip_layer_bwd_split (below: the form tim_amd calls) with dx_out_add = dx_in_add = NULL. */
 int timhip_layer_bwd(const TimDesc* d, const TimLayerParams* w, const void* x_in_T,
                      const void* saved, float* dx_out, float* dx_in, const TimLayerGrads* g,
                      void* workspace, size_t workspace_bytes, void* stream);
@@ -493,7 +494,8 @@ int timhip_layer_bwd(const TimDesc* d, const TimLayerParams* w, const void* x_in
  * `dy` (timhip_layer_dy_bytes); the weight-gradient part consumes `dy` and the saved activations and
  * may be enqueued on a second stream so that it overlaps the data chain of the next layer
  * (the caller orders the two streams with events).  LayerNorm gradients are written by the data chain,
- * all other parameter gradients by the weights part. */
+ * all other parameter gradients by the weights part.  timhip_layer_bwd_data is timhip_layer_bwd_data_split (below: the form
+ * tim_amd calls) with dx_out_add = dx_in_add = NULL. */
 size_t timhip_layer_dy_bytes(const TimDesc* d);
 size_t timhip_layer_data_workspace_bytes(const TimDesc* d);
 size_t timhip_layer_wgrad_workspace_bytes(const TimDesc* d);

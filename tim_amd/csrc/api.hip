@@ -7,28 +7,58 @@
 namespace {
 
 struct SavedLayout {
-  size_t qkv, o, lse, y1, st1, x1t, u, h, y2, st2, ffn_mask, attn_keep, total;
+  Field qkv, o, lse, y1, st1, x1t, u, h, y2, st2, ffn_mask, attn_keep;
+  size_t total;
 };
 
 SavedLayout saved_layout(const TimDesc& d) {
   const size_t M = (size_t)d.B * d.S, ts = opsize(d.precision);
+  Arena a;
   SavedLayout L;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-  L.qkv = take(M * 3 * d.E * ts);
-  L.o = take(M * d.E * ts);
-  L.lse = take((size_t)d.B * d.H * d.S * 4);
-  L.y1 = take(M * d.E * 4);
-  L.st1 = take(M * 2 * 4);
-  L.x1t = take(M * d.E * ts);
-  L.u = take(M * d.FF * ts);
-  L.h = take(M * d.FF * ts);
-  L.y2 = take(M * d.E * 4);
-  L.st2 = take(M * 2 * 4);
-  L.ffn_mask = take(M * d.FF / 8);   // keep-bits of the FFN dropout (FF % 64 == 0): written by norm1, read by the linear1 epilogue
-  L.attn_keep = take((size_t)d.B * d.H * d.S * 16);   // keep-bits of the attention dropout (timhip_attn_keep_bits, TIMHIP_DESC_ATTN_KEEP_BITS)
-  L.total = off;
+  L.qkv = a.take(M * 3 * d.E * ts);
+  L.o = a.take(M * d.E * ts);
+  L.lse = a.take((size_t)d.B * d.H * d.S * 4);
+  L.y1 = a.take(M * d.E * 4);
+  L.st1 = a.take(M * 2 * 4);
+  L.x1t = a.take(M * d.E * ts);
+  L.u = a.take(M * d.FF * ts);
+  L.h = a.take(M * d.FF * ts);
+  L.y2 = a.take(M * d.E * 4);
+  L.st2 = a.take(M * 2 * 4);
+  L.ffn_mask = a.take(M * d.FF / 8);   // keep-bits of the FFN dropout (FF % 64 == 0): written by norm1, read by the linear1 epilogue
+  L.attn_keep = a.take((size_t)d.B * d.H * d.S * 16);   // keep-bits of the attention dropout (timhip_attn_keep_bits, TIMHIP_DESC_ATTN_KEEP_BITS)
+  L.total = a.total();
   return L;
+}
+
+// gradient operands handed from the data chain to the weight-gradient part: df[M,E] | du[M,FF] | da[M,E] | dqkv[M,3E]
+struct DyLayout { Field df, du, da, dqkv; size_t total; };
+DyLayout dy_layout(const TimDesc& d) {
+  const size_t M = (size_t)d.B * d.S, ts = opsize(d.precision);
+  Arena a;
+  DyLayout L;
+  L.df = a.take(M * d.E * ts);
+  L.du = a.take(M * d.FF * ts);
+  L.da = a.take(M * d.E * ts);
+  L.dqkv = a.take(M * 3 * d.E * ts);
+  L.total = a.total();
+  return L;
+}
+
+// The four Linear products of a layer as weight-gradient items:
+//   linear2: dW2 += df^T h ; linear1: dW1 += du^T x1 ; out-proj: dWo += da^T o ; in-proj: dWin += dqkv^T x_in
+// in this order (the grouped kernels walk their tiles in item order).  saved / dy: the layer's saved block and the block its data
+// chain left; all of saved, dy, x_in_T, g NULL: the shapes alone (workspace sizes, kernel choice).
+void layer_products(const TimDesc& d, const void* saved, const void* dy, const void* x_in_T, const TimLayerGrads* g,
+                    TimWgradItem it[4]) {
+  const SavedLayout L = saved_layout(d);
+  const DyLayout Y = dy_layout(d);
+  const int E = d.E, FF = d.FF;
+  auto in = [](const void* base, const Field& f) { return base ? (const void*)f.at(base) : nullptr; };
+  it[0] = TimWgradItem{in(dy, Y.df), in(saved, L.h), g ? g->l2_w : nullptr, g ? g->l2_b : nullptr, E, FF, E, FF};
+  it[1] = TimWgradItem{in(dy, Y.du), in(saved, L.x1t), g ? g->l1_w : nullptr, g ? g->l1_b : nullptr, FF, E, FF, E};
+  it[2] = TimWgradItem{in(dy, Y.da), in(saved, L.o), g ? g->out_w : nullptr, g ? g->out_b : nullptr, E, E, E, E};
+  it[3] = TimWgradItem{in(dy, Y.dqkv), x_in_T, g ? g->in_w : nullptr, g ? g->in_b : nullptr, 3 * E, E, 3 * E, E};
 }
 
 int splitk_for(int Mout, int Nout, int Kp) {
@@ -41,64 +71,52 @@ int splitk_for(int Mout, int Nout, int Kp) {
   return sk;
 }
 
-struct WgradWs { size_t tA, tB, slab, total; };
+struct WgradWs { Field tA, tB, slab; size_t total; };
 WgradWs wgrad_ws(int prec, int Nout, int Kout, int M) {
   const size_t Mp = round_up(M, 64), ts = opsize(prec);
-  WgradWs w;
+  Arena a;
+  WgradWs w{};
   if (h16_storage(prec)) {  // transposing-read kernel: no operand copies
-    w.tA = w.tB = w.slab = 0;
     w.total = tim_wgrad_tn_ws(Nout, Kout, M);
     return w;
   }
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-  w.tA = take((size_t)Nout * Mp * ts);
-  w.tB = take((size_t)Kout * Mp * ts);
+  w.tA = a.take((size_t)Nout * Mp * ts);
+  w.tB = a.take((size_t)Kout * Mp * ts);
   const int sk = splitk_for(Nout, Kout, (int)Mp);
-  w.slab = take(sk > 1 ? (size_t)sk * Nout * Kout * 4 : 0);
-  w.total = off;
+  w.slab = a.take(sk > 1 ? (size_t)sk * Nout * Kout * 4 : 0);
+  w.total = a.total();
   return w;
 }
 
+// workspace of the data chain; `wg`: the part the weight gradients run in (timhip_layer_bwd hands it on)
 struct WsLayout {
-  size_t f32a, f32b, Ta, Tb, Tc, tA, tB, attn, lnp, total, wg_bytes;
+  Field f32a, f32b, Tb, Tc, wg, attn, lnp;
+  size_t total;
 };
 
 WsLayout ws_layout(const TimDesc& d) {
   const size_t M = (size_t)d.B * d.S, ts = opsize(d.precision);
-  const size_t Mp = round_up((int)M, 64);
-  const size_t wide = (size_t)(3 * d.E > d.FF ? 3 * d.E : d.FF);
-  const size_t mid = (size_t)(d.FF > d.E ? d.FF : d.E);
-  WsLayout L;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-  L.f32a = take(M * d.E * 4);
-  L.f32b = take(M * d.E * 4);
-  L.Ta = take(M * wide * ts);
-  L.Tb = take(M * d.E * ts);
-  L.Tc = take(M * d.E * ts);
-  {
-    size_t wg = wgrad_ws(d.precision, 3 * d.E, d.E, (int)M).total;
-    size_t w2 = wgrad_ws(d.precision, d.E, d.FF, (int)M).total;
-    size_t w3 = wgrad_ws(d.precision, d.FF, d.E, (int)M).total;
-    if (w2 > wg) wg = w2;
-    if (w3 > wg) wg = w3;
-    if (h16_storage(d.precision)) {   // the grouped launch of timhip_layer_bwd_weights (slabs only when it splits)
-      const TimWgradItem it[4] = {{nullptr, nullptr, nullptr, nullptr, d.E, d.FF, d.E, d.FF},
-                                  {nullptr, nullptr, nullptr, nullptr, d.FF, d.E, d.FF, d.E},
-                                  {nullptr, nullptr, nullptr, nullptr, d.E, d.E, d.E, d.E},
-                                  {nullptr, nullptr, nullptr, nullptr, 3 * d.E, d.E, 3 * d.E, d.E}};
-      const size_t wgp = tim_wgrad_group_ws(it, 4, (int)M);
-      if (wgp > wg) wg = wgp;
-    }
-    L.tA = take(wg);
-    L.tB = L.tA;
-    L.wg_bytes = wg;
+  // the weight gradients: one product at a time (timhip_wgrad) or the grouped launch (slabs only when it splits)
+  TimWgradItem it[4];
+  layer_products(d, nullptr, nullptr, nullptr, nullptr, it);
+  size_t wg = h16_storage(d.precision) ? tim_wgrad_group_ws(it, 4, (int)M) : 0;
+  for (int i = 0; i < 4; ++i) {
+    // (the out-projection is left out, as it always was: the sizes the library reports stay what they were.  Run alone - the
+    //  TIMHIP_DESC_WGRAD_SEPARATE route - it asks for more than the other three at a few shapes, E = 768 / FF = 3072 among them)
+    if (i == 2) continue;
+    const size_t one = wgrad_ws(d.precision, it[i].Nout, it[i].Kout, (int)M).total;
+    if (one > wg) wg = one;
   }
-  (void)Mp; (void)wide; (void)mid;
-  L.attn = take(tim_attention_bwd_ws(d));
-  L.lnp = take(tim_layernorm_bwd_ws((int)M, d.E));
-  L.total = off;
+  Arena a;
+  WsLayout L;
+  L.f32a = a.take(M * d.E * 4);
+  L.f32b = a.take(M * d.E * 4);
+  L.Tb = a.take(M * d.E * ts);
+  L.Tc = a.take(M * d.E * ts);
+  L.wg = a.take(wg);
+  L.attn = a.take(tim_attention_bwd_ws(d));
+  L.lnp = a.take(tim_layernorm_bwd_ws((int)M, d.E));
+  L.total = a.total();
   return L;
 }
 
@@ -121,7 +139,9 @@ TimEpi epi0() {
 }
 
 // dW[Nout, Kout] += dY[M, Nout]^T X[M, Kout]   (+ db[Nout] += colsum dY)
-// Both operands are transposed into K(=M)-contiguous copies, the product runs split-K into fp32
+// 16-bit operands: the transposing-read kernel of wgrad.hip (tim_wgrad_tn_h16), which also knows "=" instead of "+="
+// (accumulate = 0) and a device scalar multiplied into what it writes (out_scale).
+// fp32 / bf16x3 operands: both are transposed into K(=M)-contiguous copies, the product runs split-K into fp32
 // slabs (plain coalesced stores, no atomics) and one reduce kernel adds the slabs into dW.
 int wgrad(int prec, const void* dY, int ldy, int Nout, const void* X, int ldx, int Kout, int M, float* dW, float* db,
           void* ws, size_t ws_bytes, hipStream_t s, int accumulate = 1, const float* out_scale = nullptr) {
@@ -131,7 +151,7 @@ int wgrad(int prec, const void* dY, int ldy, int Nout, const void* X, int ldx, i
   if (h16_storage(prec)) return tim_wgrad_tn_h16(prec, dY, ldy, Nout, X, ldx, Kout, M, dW, db, ws, ws_bytes, s, accumulate, out_scale);
   if (!accumulate || out_scale) return TIMHIP_EUNSUPPORTED;   // the fp32 / bf16x3 route accumulates into dW, unscaled
   char* w = (char*)ws;
-  void* tA = w + W.tA; void* tB = w + W.tB; float* slab = (float*)(w + W.slab);
+  void* tA = W.tA.at(w); void* tB = W.tB.at(w); float* slab = (float*)W.slab.at(w);
   int rc;
   if ((rc = tim_transpose(prec, dY, M, Nout, ldy, tA, Mp, db, s))) return rc;
   if ((rc = tim_transpose(prec, X, M, Kout, ldx, tB, Mp, nullptr, s))) return rc;
@@ -144,6 +164,38 @@ int wgrad(int prec, const void* dY, int ldy, int Nout, const void* X, int ldx, i
   e.out0 = slab; e.ld0 = Kout;
   if ((rc = tim_gemm_nt(prec, TIMHIP_EPI_STORE_F32, tA, Mp, tB, Mp, Nout, Kout, Mp, e, sk, s))) return rc;
   return tim_slab_reduce(slab, (long long)Nout * Kout, sk, dW, s);
+}
+
+// What a pass over a layer takes from the descriptor's flags rather than from its shape.
+struct LayerPass {
+  // fp16: the gradient OPERANDS (df, du, da, Tb, Tc, dqkv, the 16-bit parts of the stream and the attention scratch) carry the
+  // factor S = grad_scale[0]; it enters with the T copies LayerNorm-backward writes (gs_in) and leaves where a product joins
+  // fp32 values (gs_out = &grad_scale[1], 1 / S).  NULL both: no scale
+  const float* gs_in;
+  const float* gs_out;
+  int accumulate;   // weight gradients: 1 "+=", 0 "=" (TIMHIP_DESC_WGRAD_OVERWRITE: the buffers are neither zero-filled nor read)
+  const unsigned long long* akeep;   // the attention dropout's keep-bits (TIMHIP_DESC_ATTN_KEEP_BITS), NULL: the kernels draw their own
+};
+LayerPass layer_pass(const TimDesc& d, const unsigned long long* keep_bits = nullptr) {   // keep_bits: where the saved block has them
+  LayerPass P;
+  P.gs_in = (d.precision == TIMHIP_PREC_F16 && d.grad_scale) ? d.grad_scale : nullptr;
+  P.gs_out = P.gs_in ? P.gs_in + 1 : nullptr;
+  P.accumulate = (d.reserved & TIMHIP_DESC_WGRAD_OVERWRITE) ? 0 : 1;
+  P.akeep = ((d.reserved & TIMHIP_DESC_ATTN_KEEP_BITS) && d.p_drop > 0.f) ? keep_bits : nullptr;
+  return P;
+}
+
+// whether the grouped weight-gradient launches take this layer (else: one timhip_wgrad per product).  Their other condition, four
+// products of a multiple of 4 elements each, holds for every descriptor check_layer_desc lets through (E % 64 == 0)
+bool wgrad_grouped(const TimDesc& d) { return h16_storage(d.precision) && !(d.reserved & TIMHIP_DESC_WGRAD_SEPARATE); }
+
+// One forward Linear: epilogue `epi` of A[M, K] W[N, K]^T.  split: W is a split copy [hi | lo | ..] with row stride 3 K (the
+// descriptor's *_SPLIT flags); the product runs over 2 K with the activation operand read twice (TimEpi.a_wrap_k) - the weight
+// to ~22 bits
+int linear_fwd(int prec, int epi, const void* A, const void* W, int M, int N, int K, bool split, TimEpi e, hipStream_t s) {
+  if (!split) return tim_gemm_nt(prec, epi, A, K, W, K, M, N, K, e, 1, s);
+  e.a_wrap_k = K; e.reserved = 2;
+  return tim_gemm_nt(prec, epi, A, K, W, 3 * K, M, N, 2 * K, e, 1, s);
 }
 
 }  // namespace
@@ -230,7 +282,7 @@ int timhip_attn_keep_bits(const TimDesc* d, int nlayers, void* const* saved, voi
     const int n = nlayers - l0 < 8 ? nlayers - l0 : 8;
     for (int i = 0; i < n; ++i) {
       if (!saved[l0 + i]) return TIMHIP_EINVAL;
-      out[i] = reinterpret_cast<unsigned long long*>((char*)saved[l0 + i] + L.attn_keep);
+      out[i] = reinterpret_cast<unsigned long long*>(L.attn_keep.at(saved[l0 + i]));
     }
     const int rc = tim_attn_keep_bits(*d, l0, n, out, (hipStream_t)stream);
     if (rc) return rc;
@@ -244,21 +296,21 @@ size_t timhip_layer_saved_bytes(const TimDesc* d) { return d ? saved_layout(*d).
 int timhip_layer_saved_field(const TimDesc* d, int field, size_t* offset, size_t* bytes) {
   if (!d || !offset || !bytes) return TIMHIP_EINVAL;
   const SavedLayout L = saved_layout(*d);
-  const size_t M = (size_t)d->B * d->S, ts = opsize(d->precision);
+  const Field* f;
   switch (field) {
-    case TIMHIP_SAVED_QKV: *offset = L.qkv; *bytes = M * 3 * d->E * ts; break;
-    case TIMHIP_SAVED_O: *offset = L.o; *bytes = M * d->E * ts; break;
-    case TIMHIP_SAVED_Y1: *offset = L.y1; *bytes = M * d->E * 4; break;
-    case TIMHIP_SAVED_X1T: *offset = L.x1t; *bytes = M * d->E * ts; break;
-    case TIMHIP_SAVED_H: *offset = L.h; *bytes = M * d->FF * ts; break;
-    case TIMHIP_SAVED_Y2: *offset = L.y2; *bytes = M * d->E * 4; break;
-    case TIMHIP_SAVED_FFN_KEEP_BITS: *offset = L.ffn_mask; *bytes = M * d->FF / 8; break;
-    case TIMHIP_SAVED_ATTN_KEEP_BITS: *offset = L.attn_keep; *bytes = (size_t)d->B * d->H * d->S * 16; break;
+    case TIMHIP_SAVED_QKV: f = &L.qkv; break;
+    case TIMHIP_SAVED_O: f = &L.o; break;
+    case TIMHIP_SAVED_Y1: f = &L.y1; break;
+    case TIMHIP_SAVED_X1T: f = &L.x1t; break;
+    case TIMHIP_SAVED_H: f = &L.h; break;
+    case TIMHIP_SAVED_Y2: f = &L.y2; break;
+    case TIMHIP_SAVED_FFN_KEEP_BITS: f = &L.ffn_mask; break;
+    case TIMHIP_SAVED_ATTN_KEEP_BITS: f = &L.attn_keep; break;
     default: return TIMHIP_EINVAL;
   }
+  *offset = f->off; *bytes = f->bytes;
   return TIMHIP_OK;
 }
-size_t timhip_layer_workspace_bytes(const TimDesc* d);
 
 int timhip_gemm_nt(int precision, int epi, const void* A, int lda, const void* B, int ldb, int M, int N, int K,
                    const TimEpi* e, int splitk, void* stream) {
@@ -305,10 +357,9 @@ struct LayerBufs {
 
 static LayerBufs saved_bufs(const TimDesc& d, void* saved) {
   const SavedLayout L = saved_layout(d);
-  char* sv = (char*)saved;
-  return LayerBufs{sv + L.qkv, sv + L.o, (float*)(sv + L.lse), (float*)(sv + L.y1), (float*)(sv + L.st1), sv + L.x1t, sv + L.u,
-                   sv + L.h, (float*)(sv + L.y2), (float*)(sv + L.st2), (uint8_t*)(sv + L.ffn_mask),
-                   reinterpret_cast<const unsigned long long*>(sv + L.attn_keep)};
+  return LayerBufs{L.qkv.at(saved), L.o.at(saved), (float*)L.lse.at(saved), (float*)L.y1.at(saved), (float*)L.st1.at(saved),
+                   L.x1t.at(saved), L.u.at(saved), L.h.at(saved), (float*)L.y2.at(saved), (float*)L.st2.at(saved),
+                   (uint8_t*)L.ffn_mask.at(saved), reinterpret_cast<const unsigned long long*>(L.attn_keep.at(saved))};
 }
 
 static int layer_fwd_body(const TimDesc& d, const TimLayerParams* w, const float* x_in, const float* x_in_prenorm,
@@ -320,18 +371,13 @@ static int layer_fwd_body(const TimDesc& d, const TimLayerParams* w, const float
   void* u = bufs.u; void* h = bufs.h; float* y2 = bufs.y2; float* st2 = bufs.st2;
 
   // 1. packed in-projection (F._in_projection_packed)
-  // (a *_SPLIT flag: that weight pointer is a split copy [hi | lo | ..] with row stride 3 K; the product runs over 2 K with the
-  //  activation operand read twice - TimEpi.a_wrap_k)
+  // (a *_SPLIT flag: that weight pointer is a split copy, see linear_fwd)
   auto split = [&](int flag) { return (d.reserved & flag) != 0 && h16_storage(prec); };
   TimEpi e = epi0();
   e.out0 = qkv; e.ld0 = 3 * E; e.bias = w->in_b;
-  if (split(TIMHIP_DESC_INPROJ_SPLIT)) {
-    e.a_wrap_k = E; e.reserved = 2;
-    if ((rc = tim_gemm_nt(prec, TIMHIP_EPI_STORE_T, x_in_T, E, w->in_w, 3 * E, Mall, 3 * E, 2 * E, e, 1, s))) return rc;
-  } else if ((rc = tim_gemm_nt(prec, TIMHIP_EPI_STORE_T, x_in_T, E, w->in_w, E, Mall, 3 * E, E, e, 1, s))) return rc;
+  if ((rc = linear_fwd(prec, TIMHIP_EPI_STORE_T, x_in_T, w->in_w, Mall, 3 * E, E, split(TIMHIP_DESC_INPROJ_SPLIT), e, s))) return rc;
   // 2. structured attention (keys and values of all rows; the rows from s0 on)
-  const unsigned long long* akeep = ((d.reserved & TIMHIP_DESC_ATTN_KEEP_BITS) && d.p_drop > 0.f) ? bufs.attn_keep : nullptr;
-  if ((rc = tim_attention_fwd(d, qkv, o, bufs.lse, s, akeep, s0))) return rc;
+  if ((rc = tim_attention_fwd(d, qkv, o, bufs.lse, s, layer_pass(d, bufs.attn_keep).akeep, s0))) return rc;
   // 3. out-projection + dropout1 + residual
   e = epi0();
   e.out0 = y1; e.ld0 = E; e.bias = w->out_b; e.ldres = E;
@@ -354,13 +400,7 @@ static int layer_fwd_body(const TimDesc& d, const TimLayerParams* w, const float
     if (rc == TIMHIP_OK) fused1 = true;
     else if (rc != TIMHIP_EUNSUPPORTED) return rc;
   }
-  if (!fused1) {
-    if (split(TIMHIP_DESC_OUTPROJ_SPLIT)) {
-      // out_w = [w_hi | w_lo | ..] (row stride 3E): o [w_hi | w_lo]^T over K = 2E, o read twice - the weight to ~22 bits
-      e.a_wrap_k = E; e.reserved = 2;
-      if ((rc = tim_gemm_nt(prec, TIMHIP_EPI_DROP_RES_F32, o, E, w->out_w, 3 * E, M, E, 2 * E, e, 1, s))) return rc;
-    } else if ((rc = tim_gemm_nt(prec, TIMHIP_EPI_DROP_RES_F32, o, E, w->out_w, E, M, E, E, e, 1, s))) return rc;
-  }
+  if (!fused1 && (rc = linear_fwd(prec, TIMHIP_EPI_DROP_RES_F32, o, w->out_w, M, E, E, split(TIMHIP_DESC_OUTPROJ_SPLIT), e, s))) return rc;
   // 4. norm1.  The kernel is HBM-bound with idle VALU: it also draws the keep-bits of the FFN dropout (same Philox
   //    stream as the epilogues would use), which the linear1 epilogue and, in the backward, the gelu' epilogue read
   if ((rc = tim_layernorm_fwd(prec, y1, M, E, E, 0, w->n1_w, w->n1_b, nullptr, 0, x1t, E, st1, s, fmask, FF, d.p_drop, d.seed,
@@ -376,10 +416,7 @@ static int layer_fwd_body(const TimDesc& d, const TimLayerParams* w, const float
     e.p_drop = d.p_drop; e.seed = d.seed; e.site = layer_site(d.layer, SITE_L_FFN);
     e.mask = fmask; e.ldmask = FF / 8;
   }
-  if (split(TIMHIP_DESC_L1_SPLIT)) {
-    e.a_wrap_k = E; e.reserved = 2;
-    if ((rc = tim_gemm_nt(prec, epi1, x1t, E, w->l1_w, 3 * E, M, FF, 2 * E, e, 1, s))) return rc;
-  } else if ((rc = tim_gemm_nt(prec, epi1, x1t, E, w->l1_w, E, M, FF, E, e, 1, s))) return rc;
+  if ((rc = linear_fwd(prec, epi1, x1t, w->l1_w, M, FF, E, split(TIMHIP_DESC_L1_SPLIT), e, s))) return rc;
   // 6. linear2 + dropout2 + residual
   e = epi0();
   e.out0 = y2; e.ld0 = E; e.bias = w->l2_b; e.ldres = E;
@@ -392,21 +429,10 @@ static int layer_fwd_body(const TimDesc& d, const TimLayerParams* w, const float
     if (rc == TIMHIP_OK) fused2 = true;
     else if (rc != TIMHIP_EUNSUPPORTED) return rc;
   }
-  if (!fused2) {
-    if (split(TIMHIP_DESC_L2_SPLIT)) {
-      e.a_wrap_k = FF; e.reserved = 2;
-      if ((rc = tim_gemm_nt(prec, TIMHIP_EPI_DROP_RES_F32, h, FF, w->l2_w, 3 * FF, M, E, 2 * FF, e, 1, s))) return rc;
-    } else if ((rc = tim_gemm_nt(prec, TIMHIP_EPI_DROP_RES_F32, h, FF, w->l2_w, FF, M, E, FF, e, 1, s))) return rc;
-  }
+  if (!fused2 && (rc = linear_fwd(prec, TIMHIP_EPI_DROP_RES_F32, h, w->l2_w, M, E, FF, split(TIMHIP_DESC_L2_SPLIT), e, s))) return rc;
   // 7. norm2 (x_out == NULL: only the operand copy and the statistics)
   return tim_layernorm_fwd(prec, y2, M, E, E, 0, w->n2_w, w->n2_b, x_out, E, x_out_T, E, st2, s, nullptr, 0, 0.f, 0, 0,
                            fused2 ? ln_run_if : nullptr);
-}
-
-static int layer_fwd_impl(const TimDesc& d, const TimLayerParams* w, const float* x_in, const float* x_in_prenorm,
-                          const float* x_in_stats, const float* x_in_lnw, const float* x_in_lnb, const void* x_in_T,
-                          float* x_out, void* x_out_T, void* saved, hipStream_t s) {
-  return layer_fwd_body(d, w, x_in, x_in_prenorm, x_in_stats, x_in_lnw, x_in_lnb, x_in_T, x_out, x_out_T, saved_bufs(d, saved), 0, s);
 }
 
 int timhip_layer_fwd(const TimDesc* dp, const TimLayerParams* w, const float* x_in, const void* x_in_T, float* x_out,
@@ -415,7 +441,8 @@ int timhip_layer_fwd(const TimDesc* dp, const TimLayerParams* w, const float* x_
   if (!dp || !w || !x_in || !x_in_T || !x_out_T || !saved) return TIMHIP_EINVAL;
   int rc = check_layer_desc(*dp);
   if (rc) return rc;
-  return layer_fwd_impl(*dp, w, x_in, nullptr, nullptr, nullptr, nullptr, x_in_T, x_out, x_out_T, saved, (hipStream_t)stream);
+  return layer_fwd_body(*dp, w, x_in, nullptr, nullptr, nullptr, nullptr, x_in_T, x_out, x_out_T, saved_bufs(*dp, saved), 0,
+                        (hipStream_t)stream);
 }
 
 int timhip_layer_fwd_chained(const TimDesc* dp, const TimLayerParams* w, const TimLayerParams* prev_w, const void* prev_saved,
@@ -424,9 +451,8 @@ int timhip_layer_fwd_chained(const TimDesc* dp, const TimLayerParams* w, const T
   int rc = check_layer_desc(*dp);
   if (rc) return rc;
   const SavedLayout L = saved_layout(*dp);   // the previous layer has the same shape
-  const char* ps = (const char*)prev_saved;
-  return layer_fwd_impl(*dp, w, nullptr, (const float*)(ps + L.y2), (const float*)(ps + L.st2), prev_w->n2_w, prev_w->n2_b,
-                        x_in_T, x_out, x_out_T, saved, (hipStream_t)stream);
+  return layer_fwd_body(*dp, w, nullptr, (const float*)L.y2.at(prev_saved), (const float*)L.st2.at(prev_saved), prev_w->n2_w,
+                        prev_w->n2_b, x_in_T, x_out, x_out_T, saved_bufs(*dp, saved), 0, (hipStream_t)stream);
 }
 
 // ---- evaluation forward of the whole stack out of one arena (timhip_stack_infer) ---------------------------------------------
@@ -434,24 +460,23 @@ int timhip_layer_fwd_chained(const TimDesc* dp, const TimLayerParams* w, const T
 // plus the operand-dtype rows between two layers and, for the query-row tail, the gathered residual rows.  One copy is enough:
 // a layer reads the previous layer's y2 / st2 (its residual, normalised by the out-projection epilogue) before its own linear2
 // rewrites them, and the previous layer's operand rows (its in-projection) before its own norm2 rewrites those.
-struct InferLayout { size_t qkv, o, y1, st1, x1t, h, y2, st2, xt, resg, stg, total; };
+struct InferLayout { Field qkv, o, y1, st1, x1t, h, y2, st2, xt, resg, stg; size_t total; };
 static InferLayout infer_layout(const TimDesc& d, int tail_only) {
   const size_t M = (size_t)d.B * d.S, Mt = (size_t)d.B * (d.S - d.F), ts = opsize(d.precision);
+  Arena a;
   InferLayout L;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-  L.qkv = take(M * 3 * d.E * ts);
-  L.o = take(M * d.E * ts);
-  L.y1 = take(M * d.E * 4);
-  L.st1 = take(M * 2 * 4);
-  L.x1t = take(M * d.E * ts);
-  L.h = take(M * d.FF * ts);
-  L.y2 = take(M * d.E * 4);
-  L.st2 = take(M * 2 * 4);
-  L.xt = take(M * d.E * ts);
-  L.resg = take(tail_only ? Mt * d.E * 4 : 0);   // fp32 residual rows of the tail's query rows (pre-norm, or x_in's own)
-  L.stg = take(tail_only ? Mt * 2 * 4 : 0);      // their LayerNorm statistics
-  L.total = off;
+  L.qkv = a.take(M * 3 * d.E * ts);
+  L.o = a.take(M * d.E * ts);
+  L.y1 = a.take(M * d.E * 4);
+  L.st1 = a.take(M * 2 * 4);
+  L.x1t = a.take(M * d.E * ts);
+  L.h = a.take(M * d.FF * ts);
+  L.y2 = a.take(M * d.E * 4);
+  L.st2 = a.take(M * 2 * 4);
+  L.xt = a.take(M * d.E * ts);
+  L.resg = a.take(tail_only ? Mt * d.E * 4 : 0);   // fp32 residual rows of the tail's query rows (pre-norm, or x_in's own)
+  L.stg = a.take(tail_only ? Mt * 2 * 4 : 0);      // their LayerNorm statistics
+  L.total = a.total();
   return L;
 }
 
@@ -470,9 +495,9 @@ int timhip_stack_infer(const TimDesc* dp, int nlayers, const TimLayerParams* lay
   const InferLayout L = infer_layout(d, tail_only);
   if (workspace_bytes < L.total) return TIMHIP_EWORKSPACE;
   hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  const LayerBufs bufs{ws + L.qkv, ws + L.o, nullptr, (float*)(ws + L.y1), (float*)(ws + L.st1), ws + L.x1t, nullptr, ws + L.h,
-                       (float*)(ws + L.y2), (float*)(ws + L.st2), nullptr, nullptr};
+  void* ws = workspace;
+  const LayerBufs bufs{L.qkv.at(ws), L.o.at(ws), nullptr, (float*)L.y1.at(ws), (float*)L.st1.at(ws), L.x1t.at(ws), nullptr,
+                       L.h.at(ws), (float*)L.y2.at(ws), (float*)L.st2.at(ws), nullptr, nullptr};
   d.reserved &= ~TIMHIP_DESC_ATTN_KEEP_BITS;
   for (int l = 0; l < nlayers; ++l) {
     const bool last = l == nlayers - 1;
@@ -483,38 +508,23 @@ int timhip_stack_infer(const TimDesc* dp, int nlayers, const TimLayerParams* lay
     const float* pre = l == 0 ? nullptr : bufs.y2;
     const float* pst = l == 0 ? nullptr : bufs.st2;
     if (s0) {   // the tail reads them by compact row index: gather the query rows (fp32; pre-norm rows with their statistics)
-      float* resg = (float*)(ws + L.resg); float* stg = (float*)(ws + L.stg);
+      float* resg = (float*)L.resg.at(ws); float* stg = (float*)L.stg.at(ws);
       if ((rc = timhip_gather_rows(TIMHIP_PREC_FP32, l == 0 ? x_in : pre, d.B, d.S, d.E, s0, d.S - s0, resg, stream))) return rc;
       if (l > 0 && (rc = timhip_gather_rows(TIMHIP_PREC_FP32, pst, d.B, d.S, 2, s0, d.S - s0, stg, stream))) return rc;
       if (l == 0) res = resg; else { pre = resg; pst = stg; }
     }
-    const void* in_T = l == 0 ? x_in_T : (const void*)(ws + L.xt);
+    const void* in_T = l == 0 ? x_in_T : (const void*)L.xt.at(ws);
     if ((rc = layer_fwd_body(d, &layers[l], res, pre, pst, l ? layers[l - 1].n2_w : nullptr, l ? layers[l - 1].n2_b : nullptr, in_T,
-                             last ? x_out : nullptr, last ? x_out_T : (void*)(ws + L.xt), bufs, s0, s))) return rc;
+                             last ? x_out : nullptr, last ? x_out_T : (void*)L.xt.at(ws), bufs, s0, s))) return rc;
   }
   return TIMHIP_OK;
-}
-
-// gradient operands handed from the data chain to the weight-gradient part: df[M,E] | du[M,FF] | da[M,E] | dqkv[M,3E]
-struct DyLayout { size_t df, du, da, dqkv, total; };
-static DyLayout dy_layout(const TimDesc& d) {
-  const size_t M = (size_t)d.B * d.S, ts = opsize(d.precision);
-  DyLayout L;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-  L.df = take(M * d.E * ts);
-  L.du = take(M * d.FF * ts);
-  L.da = take(M * d.E * ts);
-  L.dqkv = take(M * 3 * d.E * ts);
-  L.total = off;
-  return L;
 }
 
 size_t timhip_layer_ln_partial_bytes(const TimDesc* d) { return d ? 2 * tim_layernorm_bwd_ws(d->B * d->S, d->E) : 0; }
 size_t timhip_layer_dy_bytes(const TimDesc* d) { return d ? dy_layout(*d).total : 0; }
 size_t timhip_layer_workspace_bytes(const TimDesc* d) { return d ? ws_layout(*d).total + dy_layout(*d).total : 0; }
 size_t timhip_layer_data_workspace_bytes(const TimDesc* d) { return d ? ws_layout(*d).total : 0; }
-size_t timhip_layer_wgrad_workspace_bytes(const TimDesc* d) { return d ? ws_layout(*d).wg_bytes : 0; }
+size_t timhip_layer_wgrad_workspace_bytes(const TimDesc* d) { return d ? ws_layout(*d).wg.bytes : 0; }
 
 // The data chain.  dx_out_add / dx_in_add (both optional): the SPLIT form of the gradient stream between layers - the
 // gradient of a layer boundary travels as an fp32 part (what LayerNorm-backward wrote) plus a 16-bit part (the input-gradient
@@ -531,20 +541,16 @@ static int layer_bwd_data_impl(const TimDesc& d, const TimLayerParams* w, const 
   const int M = d.B * d.S, E = d.E, FF = d.FF, prec = d.precision;
   const SavedLayout L = saved_layout(d);
   const DyLayout Y = dy_layout(d);
-  const char* sv = (const char*)saved;
-  const void* qkv = sv + L.qkv; const void* o = sv + L.o; const float* lse = (const float*)(sv + L.lse);
-  const float* y1 = (const float*)(sv + L.y1); const float* st1 = (const float*)(sv + L.st1);
-  const void* u = sv + L.u;
-  const float* y2 = (const float*)(sv + L.y2); const float* st2 = (const float*)(sv + L.st2);
-  char* ws = (char*)workspace;
-  float* f32a = (float*)(ws + W.f32a); float* f32b = (float*)(ws + W.f32b);
-  void* Tb = ws + W.Tb; void* Tc = ws + W.Tc;
-  char* yb = (char*)dy;
-  void* df = yb + Y.df; void* du = yb + Y.du; void* da = yb + Y.da; void* dqkv = yb + Y.dqkv;
-  // fp16: the gradient OPERANDS (df, du, da, Tb, Tc, dqkv, the 16-bit parts of the stream and the attention scratch) carry the
-  // factor S = grad_scale[0]; it enters with the T copies LayerNorm-backward writes and leaves where a product joins fp32 values
-  const float* gs_in = (prec == TIMHIP_PREC_F16 && d.grad_scale) ? d.grad_scale : nullptr;
-  const float* gs_out = gs_in ? gs_in + 1 : nullptr;
+  const void* qkv = L.qkv.at(saved); const void* o = L.o.at(saved); const float* lse = (const float*)L.lse.at(saved);
+  const float* y1 = (const float*)L.y1.at(saved); const float* st1 = (const float*)L.st1.at(saved);
+  const void* u = L.u.at(saved);
+  const float* y2 = (const float*)L.y2.at(saved); const float* st2 = (const float*)L.st2.at(saved);
+  void* ws = workspace;
+  float* f32a = (float*)W.f32a.at(ws); float* f32b = (float*)W.f32b.at(ws); float* lnp = (float*)W.lnp.at(ws);
+  void* Tb = W.Tb.at(ws); void* Tc = W.Tc.at(ws);
+  void* df = Y.df.at(dy); void* du = Y.du.at(dy); void* da = Y.da.at(dy); void* dqkv = Y.dqkv.at(dy);
+  const LayerPass P = layer_pass(d, reinterpret_cast<const unsigned long long*>(L.attn_keep.at(saved)));
+  const float* gs_in = P.gs_in; const float* gs_out = P.gs_out;
 
   // the residual part of the stream as 16-bit (TIMHIP_DESC_STREAM16*, fp16 mode only: same scale as the gradient operands)
   const bool s16 = gs_in != nullptr && (d.reserved & TIMHIP_DESC_STREAM16) != 0;
@@ -554,7 +560,7 @@ static int layer_bwd_data_impl(const TimDesc& d, const TimLayerParams* w, const 
   // norm2 backward -> dy2 (fp32; STREAM16: T times S, in f32a's space) and df = dropout2-mask * dy2 (T)
   if ((rc = tim_layernorm_bwd(prec, dx_out, E, y2, E, st2, M, E, 0, w->n2_w, f32a, E, df, E, d.p_drop, d.seed,
                               layer_site(d.layer, SITE_L_DROP2), g->n2_w, g->n2_b,
-                              g->ln_partials ? g->ln_partials : (float*)(ws + W.lnp), s, g->ln_partials != nullptr, gs_in,
+                              g->ln_partials ? g->ln_partials : lnp, s, g->ln_partials != nullptr, gs_in,
                               dx_out_add, E, gs_out, (s16_in ? 1 : 0) | (s16 ? 2 : 0)))) return rc;
   // du = (df W2) * [dropout-mask * gelu'(pre-activation)]
   TimEpi e = epi0();
@@ -577,7 +583,7 @@ static int layer_bwd_data_impl(const TimDesc& d, const TimLayerParams* w, const 
   float* dy1 = dx_in_add ? dx_in : (branch_split ? f32b : f32a);
   if ((rc = tim_layernorm_bwd(prec, ln1_in, E, y1, E, st1, M, E, 0, w->n1_w, dy1, E, da, E, d.p_drop, d.seed,
                               layer_site(d.layer, SITE_L_DROP1), g->n1_w, g->n1_b,
-                              g->ln_partials ? g->ln_partials + tim_layernorm_bwd_ws(M, E) / sizeof(float) : (float*)(ws + W.lnp), s,
+                              g->ln_partials ? g->ln_partials + tim_layernorm_bwd_ws(M, E) / sizeof(float) : lnp, s,
                               g->ln_partials != nullptr, gs_in, branch_split ? Tb : nullptr, E, gs_out,
                               (s16 ? 1 : 0) | (s16_out ? 2 : 0)))) return rc;
   // do = da Wo
@@ -585,9 +591,7 @@ static int layer_bwd_data_impl(const TimDesc& d, const TimLayerParams* w, const 
   e.out0 = Tc; e.ld0 = E;
   if ((rc = tim_gemm_nt(prec, TIMHIP_EPI_STORE_T, da, E, w->out_wt, E, M, E, E, e, 1, s))) return rc;
   // attention backward -> dqkv
-  const unsigned long long* akeep = ((d.reserved & TIMHIP_DESC_ATTN_KEEP_BITS) && d.p_drop > 0.f)
-                                        ? reinterpret_cast<const unsigned long long*>(sv + L.attn_keep) : nullptr;
-  if ((rc = tim_attention_bwd(d, qkv, o, lse, Tc, dqkv, ws + W.attn, W.lnp - W.attn, s, akeep))) return rc;
+  if ((rc = tim_attention_bwd(d, qkv, o, lse, Tc, dqkv, W.attn.at(ws), W.attn.bytes, s, P.akeep))) return rc;
   e = epi0();
   if (dx_in_add) {   // split form: the product stays 16-bit (and scaled); dy1 is already in dx_in
     e.out0 = dx_in_add; e.ld0 = E;
@@ -618,29 +622,17 @@ int timhip_layer_bwd_weights(const TimDesc* dp, const void* x_in_T, const void* 
   const TimDesc& d = *dp;
   int rc = check_layer_desc(d);
   if (rc) return rc;
-  const int M = d.B * d.S, E = d.E, FF = d.FF, prec = d.precision;
+  const int M = d.B * d.S;
   hipStream_t s = (hipStream_t)stream;
-  const SavedLayout L = saved_layout(d);
-  const DyLayout Y = dy_layout(d);
-  const char* sv = (const char*)saved;
-  const char* yb = (const char*)dy;
-  // linear2: dW2 += df^T h ; linear1: dW1 += du^T x1 ; out-proj: dWo += da^T o ; in-proj: dWin += dqkv^T x_in
-  // (TIMHIP_DESC_WGRAD_OVERWRITE: "=" instead of "+=": the gradient buffers are neither zero-filled nor read)
-  const int acc = (d.reserved & TIMHIP_DESC_WGRAD_OVERWRITE) ? 0 : 1;
-  const float* gs_out = (prec == TIMHIP_PREC_F16 && d.grad_scale) ? d.grad_scale + 1 : nullptr;
-  if (h16_storage(prec) && !(d.reserved & TIMHIP_DESC_WGRAD_SEPARATE) && ((size_t)E * E) % 4 == 0 && ((size_t)E * FF) % 4 == 0) {
-    // one grouped launch (wgrad.hip): 12 E^2 / 128^2 tiles with FF = 2E, i.e. 512 at E = 1024 - the contraction is not split
-    const TimWgradItem it[4] = {
-        {yb + Y.df, sv + L.h, g->l2_w, g->l2_b, E, FF, E, FF},
-        {yb + Y.du, sv + L.x1t, g->l1_w, g->l1_b, FF, E, FF, E},
-        {yb + Y.da, sv + L.o, g->out_w, g->out_b, E, E, E, E},
-        {yb + Y.dqkv, x_in_T, g->in_w, g->in_b, 3 * E, E, 3 * E, E}};
-    return tim_wgrad_group_h16(prec, it, 4, M, acc, workspace, workspace_bytes, gs_out, s);
-  }
-  if ((rc = wgrad(prec, yb + Y.df, E, E, sv + L.h, FF, FF, M, g->l2_w, g->l2_b, workspace, workspace_bytes, s, acc, gs_out))) return rc;
-  if ((rc = wgrad(prec, yb + Y.du, FF, FF, sv + L.x1t, E, E, M, g->l1_w, g->l1_b, workspace, workspace_bytes, s, acc, gs_out))) return rc;
-  if ((rc = wgrad(prec, yb + Y.da, E, E, sv + L.o, E, E, M, g->out_w, g->out_b, workspace, workspace_bytes, s, acc, gs_out))) return rc;
-  return wgrad(prec, yb + Y.dqkv, 3 * E, 3 * E, x_in_T, E, E, M, g->in_w, g->in_b, workspace, workspace_bytes, s, acc, gs_out);
+  const LayerPass P = layer_pass(d);
+  TimWgradItem it[4];
+  layer_products(d, saved, dy, x_in_T, g, it);
+  // one grouped launch (wgrad.hip): 12 E^2 / 128^2 tiles with FF = 2E, i.e. 512 at E = 1024 - the contraction is not split
+  if (wgrad_grouped(d)) return tim_wgrad_group_h16(d.precision, it, 4, M, P.accumulate, workspace, workspace_bytes, P.gs_out, s);
+  for (const TimWgradItem& p : it)
+    if ((rc = wgrad(d.precision, p.dY, p.ldy, p.Nout, p.X, p.ldx, p.Kout, M, p.dW, p.db, workspace, workspace_bytes, s, P.accumulate,
+                    P.gs_out))) return rc;
+  return TIMHIP_OK;
 }
 
 // The weight gradients of TWO layers in one grouped launch (round 6): at production batch sizes the eight products are 256 tiles of
@@ -654,25 +646,12 @@ int timhip_layer_bwd_weights_pair(const TimDesc* dp, const void* x_in_T_a, const
   const TimDesc& d = *dp;
   int rc = check_layer_desc(d);
   if (rc) return rc;
-  const int M = d.B * d.S, E = d.E, FF = d.FF, prec = d.precision;
-  if (!h16_storage(prec) || (d.reserved & TIMHIP_DESC_WGRAD_SEPARATE) || ((size_t)E * E) % 4 || ((size_t)E * FF) % 4) return TIMHIP_EUNSUPPORTED;
-  const SavedLayout L = saved_layout(d);
-  const DyLayout Y = dy_layout(d);
-  const int acc = (d.reserved & TIMHIP_DESC_WGRAD_OVERWRITE) ? 0 : 1;
-  const float* gs_out = (prec == TIMHIP_PREC_F16 && d.grad_scale) ? d.grad_scale + 1 : nullptr;
+  if (!wgrad_grouped(d)) return TIMHIP_EUNSUPPORTED;
+  const LayerPass P = layer_pass(d);
   TimWgradItem it[8];
-  const void* xs[2] = {x_in_T_a, x_in_T_b};
-  const char* svs[2] = {(const char*)saved_a, (const char*)saved_b};
-  const char* ybs[2] = {(const char*)dy_a, (const char*)dy_b};
-  const TimLayerGrads* gs[2] = {ga, gb};
-  for (int h = 0; h < 2; ++h) {
-    const char* sv = svs[h]; const char* yb = ybs[h]; const TimLayerGrads* g = gs[h];
-    it[4 * h + 0] = TimWgradItem{yb + Y.df, sv + L.h, g->l2_w, g->l2_b, E, FF, E, FF};
-    it[4 * h + 1] = TimWgradItem{yb + Y.du, sv + L.x1t, g->l1_w, g->l1_b, FF, E, FF, E};
-    it[4 * h + 2] = TimWgradItem{yb + Y.da, sv + L.o, g->out_w, g->out_b, E, E, E, E};
-    it[4 * h + 3] = TimWgradItem{yb + Y.dqkv, xs[h], g->in_w, g->in_b, 3 * E, E, 3 * E, E};
-  }
-  return tim_wgrad_group_h16(prec, it, 8, M, acc, workspace, workspace_bytes, gs_out, (hipStream_t)stream);
+  layer_products(d, saved_a, dy_a, x_in_T_a, ga, it);
+  layer_products(d, saved_b, dy_b, x_in_T_b, gb, it + 4);
+  return tim_wgrad_group_h16(d.precision, it, 8, d.B * d.S, P.accumulate, workspace, workspace_bytes, P.gs_out, (hipStream_t)stream);
 }
 
 // 1: timhip_layer_bwd_weights_pair runs this descriptor's two layers as ONE round of eight-phase tiles (hosts defer a layer's
@@ -680,45 +659,37 @@ int timhip_layer_bwd_weights_pair(const TimDesc* dp, const void* x_in_T_a, const
 int timhip_layer_wgrad_pair_wins(const TimDesc* dp) {
   if (!dp || check_layer_desc(*dp)) return 0;
   const TimDesc& d = *dp;
-  if (!h16_storage(d.precision) || (d.reserved & TIMHIP_DESC_WGRAD_SEPARATE)) return 0;
-  const int E = d.E, FF = d.FF;
+  if (!wgrad_grouped(d)) return 0;
   TimWgradItem it[8];
-  for (int h = 0; h < 2; ++h) {
-    it[4 * h + 0] = TimWgradItem{nullptr, nullptr, nullptr, nullptr, E, FF, E, FF};
-    it[4 * h + 1] = TimWgradItem{nullptr, nullptr, nullptr, nullptr, FF, E, FF, E};
-    it[4 * h + 2] = TimWgradItem{nullptr, nullptr, nullptr, nullptr, E, E, E, E};
-    it[4 * h + 3] = TimWgradItem{nullptr, nullptr, nullptr, nullptr, 3 * E, E, 3 * E, E};
-  }
+  layer_products(d, nullptr, nullptr, nullptr, nullptr, it);
+  layer_products(d, nullptr, nullptr, nullptr, nullptr, it + 4);
   return tim_wgrad_p8_wins(it, 8, d.B * d.S) ? 1 : 0;
 }
 
-// single-stream form: data chain followed by the weight gradients
+// single-stream form: the data chain followed by the weight gradients, `dy` behind the data chain's workspace
+static int layer_bwd_impl(const TimDesc* dp, const TimLayerParams* w, const void* x_in_T, const void* saved, const float* dx_out,
+                          const void* dx_out_add, float* dx_in, void* dx_in_add, const TimLayerGrads* g, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+  const WsLayout W = ws_layout(*dp);
+  if (workspace_bytes < W.total + dy_layout(*dp).total) return TIMHIP_EWORKSPACE;
+  char* ws = (char*)workspace;
+  void* dy = ws + W.total;
+  int rc = timhip_layer_bwd_data_split(dp, w, saved, dx_out, dx_out_add, dx_in, dx_in_add, dy, g, ws, W.total, stream);
+  if (rc) return rc;
+  return timhip_layer_bwd_weights(dp, x_in_T, saved, dy, g, W.wg.at(ws), W.wg.bytes, stream);
+}
+
 int timhip_layer_bwd(const TimDesc* dp, const TimLayerParams* w, const void* x_in_T, const void* saved, float* dx_out,
                      float* dx_in, const TimLayerGrads* g, void* workspace, size_t workspace_bytes, void* stream) {
   if (!dp) return TIMHIP_EINVAL;
-  const WsLayout W = ws_layout(*dp);
-  const size_t need = W.total + dy_layout(*dp).total;
-  if (workspace_bytes < need) return TIMHIP_EWORKSPACE;
-  char* ws = (char*)workspace;
-  void* dy = ws + W.total;
-  int rc = timhip_layer_bwd_data(dp, w, saved, dx_out, dx_in, dy, g, ws, W.total, stream);
-  if (rc) return rc;
-  return timhip_layer_bwd_weights(dp, x_in_T, saved, dy, g, ws + W.tA, W.wg_bytes, stream);
+  return layer_bwd_impl(dp, w, x_in_T, saved, dx_out, nullptr, dx_in, nullptr, g, workspace, workspace_bytes, stream);
 }
-
 
 int timhip_layer_bwd_split(const TimDesc* dp, const TimLayerParams* w, const void* x_in_T, const void* saved, const float* dx_out,
                            const void* dx_out_add, float* dx_in, void* dx_in_add, const TimLayerGrads* g, void* workspace,
                            size_t workspace_bytes, void* stream) {
   if (!dp) return TIMHIP_EINVAL;
-  const WsLayout W = ws_layout(*dp);
-  const size_t need = W.total + dy_layout(*dp).total;
-  if (workspace_bytes < need) return TIMHIP_EWORKSPACE;
-  char* ws = (char*)workspace;
-  void* dy = ws + W.total;
-  int rc = timhip_layer_bwd_data_split(dp, w, saved, dx_out, dx_out_add, dx_in, dx_in_add, dy, g, ws, W.total, stream);
-  if (rc) return rc;
-  return timhip_layer_bwd_weights(dp, x_in_T, saved, dy, g, ws + W.tA, W.wg_bytes, stream);
+  return layer_bwd_impl(dp, w, x_in_T, saved, dx_out, dx_out_add, dx_in, dx_in_add, g, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

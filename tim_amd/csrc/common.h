@@ -25,6 +25,19 @@ typedef short s16x4_t __attribute__((ext_vector_type(4)));
 static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 __host__ __device__ static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// Byte layouts of the library's blocks (a layer's saved block, its workspaces, the evaluation arena): the fields lie back to
+// back in the order they are taken, each on a 256-byte boundary; a layout keeps the Field (where, how many bytes) of each.
+struct Field {
+  size_t off, bytes;
+  char* at(void* base) const { return (char*)base + off; }
+  const char* at(const void* base) const { return (const char*)base + off; }
+};
+struct Arena {
+  size_t off = 0;
+  Field take(size_t bytes) { const Field f{off, bytes}; off = align_up(off + bytes, 256); return f; }
+  size_t total() const { return off; }
+};
+
 // ----------------------------------------------------------------------------
 // operand-type traits
 // ----------------------------------------------------------------------------

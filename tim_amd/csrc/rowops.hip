@@ -1309,6 +1309,10 @@ int tim_layernorm_fwd(int precision, const float* y, int rows, int cols, int ldy
   return TIMHIP_OK;
 }
 
+// what the kernels take for a dropout of probability p: the keep-threshold and the factor of the kept elements (p == 0: keep all)
+struct DropArgs { uint32_t thr; float scale; };
+static DropArgs drop_args(float p) { return p > 0.f ? DropArgs{drop_threshold(p), 1.f / (1.f - p)} : DropArgs{0u, 1.f}; }
+
 // 16 rows per block, more when that would exceed the 768 co-resident blocks (3 per CU at the 154 VGPRs of the encoder's
 // act == 0 kernel): one balanced round.  Round 6: FEWER for small row counts - 1240 rows (C2a at 8 windows per GPU, the reference
 // recipe on 8 GPUs) made 78 blocks of 16 rows on 256 CUs, 12.3 us for 18 MB; 4 / 8 / 12 rows per block keep about 500 blocks
@@ -1368,30 +1372,23 @@ int tim_layernorm_bwd(int precision, const float* dx, int lddx, const float* y, 
   }
   dim3 grid((rows + rpb - 1) / rpb);
   const size_t shmem = (size_t)4 * 2 * cols * sizeof(float);
-  const uint32_t thr = p_drop > 0.f ? drop_threshold(p_drop) : 0u;
-  const float scale = p_drop > 0.f ? 1.f / (1.f - p_drop) : 1.f;
+  const DropArgs dr = drop_args(p_drop);
   const int pair_sw = tim_knobs().ln_pair;
-#define LN_BWD(NV) hipLaunchKernelGGL((ln_bwd_kernel<T, NV>), grid, dim3(256), shmem, s, dx, lddx, y, ldy, stats, rows, \
-                                   cols, act, w, dyf, lddy, (T*)dyt, ldt, thr, scale, seed, site, dgamma, dbeta, rpb, partial_ws, t_scale, \
-                                   (const T*)addt, ldadd, add_scale, sp, pair_sw)
   const int nv = (cols + 255) / 256;
-#define LN_BWD0(NV) hipLaunchKernelGGL((ln_bwd_kernel<T, NV, true>), grid, dim3(256), shmem, s, dx, lddx, y, ldy, stats, rows, \
-                                   cols, act, w, dyf, lddy, (T*)dyt, ldt, thr, scale, seed, site, dgamma, dbeta, rpb, partial_ws, t_scale, \
-                                   (const T*)addt, ldadd, add_scale, sp, pair_sw)
-#define LN_BWD16(NV, SV) hipLaunchKernelGGL((ln_bwd_kernel<HT, NV, true, SV>), grid, dim3(256), shmem, s, dx, lddx, y, ldy, stats, rows, \
-                                   cols, act, w, dyf, lddy, (HT*)dyt, ldt, thr, scale, seed, site, dgamma, dbeta, rpb, partial_ws, t_scale, \
-                                   (const HT*)addt, ldadd, add_scale, sp, pair_sw)
-#define LN_BWD16_NV(SV) do { if (nv <= 1) LN_BWD16(1, SV); else if (nv <= 2) LN_BWD16(2, SV); else if (nv <= 4) LN_BWD16(4, SV); else LN_BWD16(8, SV); } while (0)
+  // ACT0 / S16: ln_bwd_kernel's third and fourth template argument
+#define LN_BWD(T_, NV, ACT0, S16) hipLaunchKernelGGL((ln_bwd_kernel<T_, NV, ACT0, S16>), grid, dim3(256), shmem, s, dx, lddx, y, ldy, stats, \
+                                   rows, cols, act, w, dyf, lddy, (T_*)dyt, ldt, dr.thr, dr.scale, seed, site, dgamma, dbeta, rpb, partial_ws, \
+                                   t_scale, (const T_*)addt, ldadd, add_scale, sp, pair_sw)
+#define LN_BWD_NV(T_, ACT0, S16) do { if (nv <= 1) LN_BWD(T_, 1, ACT0, S16); else if (nv <= 2) LN_BWD(T_, 2, ACT0, S16); \
+                                      else if (nv <= 4) LN_BWD(T_, 4, ACT0, S16); else LN_BWD(T_, 8, ACT0, S16); } while (0)
   if (stream16) {
-    DISPATCH_H16(precision, { if (stream16 == 1) LN_BWD16_NV(1); else if (stream16 == 2) LN_BWD16_NV(2); else LN_BWD16_NV(3); });
+    DISPATCH_H16(precision, { if (stream16 == 1) LN_BWD_NV(HT, true, 1); else if (stream16 == 2) LN_BWD_NV(HT, true, 2); else LN_BWD_NV(HT, true, 3); });
   } else if (act == 0 && nv == 4) {
-    DISPATCH_T(precision, LN_BWD0(4));
+    DISPATCH_T(precision, LN_BWD(T, 4, true, 0));
   } else {
-    DISPATCH_T(precision, if (nv <= 1) LN_BWD(1); else if (nv <= 2) LN_BWD(2); else if (nv <= 4) LN_BWD(4); else LN_BWD(8));
+    DISPATCH_T(precision, LN_BWD_NV(T, false, 0));
   }
-#undef LN_BWD16_NV
-#undef LN_BWD16
-#undef LN_BWD0
+#undef LN_BWD_NV
 #undef LN_BWD
   TIM_CHECK_LAUNCH();
   if (partial_ws && (dgamma || dbeta) && !defer_colsum) {
@@ -1472,11 +1469,10 @@ int timhip_colsum(int precision, const void* src, int rows, int cols, int ld, fl
 int timhip_cast_rows(int precision, const float* src, int rows, int cols, int lds_, void* dst, int ld, float p_drop,
                      uint64_t seed, uint32_t site, const float* vscale, void* stream) {
   if (!src || !dst || rows <= 0 || cols <= 0 || ld < cols || ld % 4) return TIMHIP_EINVAL;
-  const uint32_t thr = p_drop > 0.f ? drop_threshold(p_drop) : 0u;
-  const float scale = p_drop > 0.f ? 1.f / (1.f - p_drop) : 1.f;
+  const DropArgs dr = drop_args(p_drop);
   dim3 grid((ld / 4 + 255) / 256, rows);
   DISPATCH_T(precision, hipLaunchKernelGGL(cast_rows_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, src, rows,
-                                           cols, lds_, (T*)dst, ld, thr, scale, seed, site, vscale));
+                                           cols, lds_, (T*)dst, ld, dr.thr, dr.scale, seed, site, vscale));
   TIM_CHECK_LAUNCH();
   return TIMHIP_OK;
 }
@@ -1484,11 +1480,10 @@ int timhip_cast_rows(int precision, const float* src, int rows, int cols, int ld
 int timhip_dropout_rows_bwd(const float* g, int rows, int cols, int ldg, float* dx, int ldx, float p_drop,
                             uint64_t seed, uint32_t site, void* stream) {
   if (!g || !dx || rows <= 0 || cols <= 0) return TIMHIP_EINVAL;
-  const uint32_t thr = p_drop > 0.f ? drop_threshold(p_drop) : 0u;
-  const float scale = p_drop > 0.f ? 1.f / (1.f - p_drop) : 1.f;
+  const DropArgs dr = drop_args(p_drop);
   dim3 grid(((cols + 3) / 4 + 255) / 256, rows);
-  hipLaunchKernelGGL(drop_bwd_rows_kernel, grid, dim3(256), 0, (hipStream_t)stream, g, rows, cols, ldg, dx, ldx, thr,
-                     scale, seed, site);
+  hipLaunchKernelGGL(drop_bwd_rows_kernel, grid, dim3(256), 0, (hipStream_t)stream, g, rows, cols, ldg, dx, ldx, dr.thr,
+                     dr.scale, seed, site);
   TIM_CHECK_LAUNCH();
   return TIMHIP_OK;
 }
@@ -1539,11 +1534,10 @@ int timhip_cast_rows_pair(int precision, const float* const* src, const int* col
     cp.src[i] = src[i]; cp.dst[i] = dst[i]; cp.cols[i] = cols[i]; cp.ld[i] = ld[i]; cp.site[i] = sites[i];
     maxq = ld[i] / 4 > maxq ? ld[i] / 4 : maxq;
   }
-  const uint32_t thr = p_drop > 0.f ? drop_threshold(p_drop) : 0u;
-  const float scale = p_drop > 0.f ? 1.f / (1.f - p_drop) : 1.f;
+  const DropArgs dr = drop_args(p_drop);
   dim3 grid((maxq + 255) / 256, rows, 2);
-  DISPATCH_T(precision, hipLaunchKernelGGL(cast_rows_pair_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, cp, rows, thr, scale,
-                                           TimSeed(seed)));
+  DISPATCH_T(precision, hipLaunchKernelGGL(cast_rows_pair_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, cp, rows, dr.thr,
+                                           dr.scale, TimSeed(seed)));
   TIM_CHECK_LAUNCH();
   return TIMHIP_OK;
 }
@@ -1587,10 +1581,9 @@ static int assemble_fwd_launch(int precision, const TimSeqRow* rows, int B, int 
                                int n_e_rows, const SeqVecs& sv, const float* te, int T_, float p_seq_drop, uint64_t seed,
                                uint32_t site, float* x, void* x_T, void* stream) {
   if (!rows || !te || !x || !x_T || B <= 0 || S <= 0 || d % 4) return TIMHIP_EINVAL;
-  const uint32_t thr = p_seq_drop > 0.f ? drop_threshold(p_seq_drop) : 0u;
-  const float scale = p_seq_drop > 0.f ? 1.f / (1.f - p_seq_drop) : 1.f;
+  const DropArgs dr = drop_args(p_seq_drop);
   DISPATCH_T(precision, hipLaunchKernelGGL(assemble_fwd_kernel<T>, dim3(B * S), dim3(256), 0, (hipStream_t)stream,
-                                           rows, B, S, d, e0, e1, n_e_rows, sv, te, T_, thr, scale, seed, site, x,
+                                           rows, B, S, d, e0, e1, n_e_rows, sv, te, T_, dr.thr, dr.scale, seed, site, x,
                                            (T*)x_T));
   TIM_CHECK_LAUNCH();
   return TIMHIP_OK;
@@ -1621,15 +1614,14 @@ static int assemble_bwd_launch(const TimSeqRow* rows, int B, int S, int d, const
                                float p_seq_drop, uint64_t seed, uint32_t site, float* d_e0, float* d_e1, const SeqVecGrads& sg,
                                float* d_te, void* stream) {
   if (!rows || !dx || B <= 0 || S <= 0 || d % 4) return TIMHIP_EINVAL;
-  const uint32_t thr = p_seq_drop > 0.f ? drop_threshold(p_seq_drop) : 0u;
-  const float scale = p_seq_drop > 0.f ? 1.f / (1.f - p_seq_drop) : 1.f;
+  const DropArgs dr = drop_args(p_seq_drop);
   const int G = S >= 256 ? (S + 127) / 128 : 1;   // token rows per block: about 128 row groups, one atomic per group, vector and column
   hipLaunchKernelGGL(assemble_bwd_kernel, dim3((S + G - 1) / G, (2 * d + 255) / 256), dim3(256), 0, (hipStream_t)stream, rows, B, S, d, dx,
-                     n_e_rows, thr, scale, seed, site, d_e0, d_e1, sg, G);
+                     n_e_rows, dr.thr, dr.scale, seed, site, d_e0, d_e1, sg, G);
   TIM_CHECK_LAUNCH();
   if (d_te) {
     hipLaunchKernelGGL(assemble_bwd_te_kernel, dim3(T_, B >= 32 ? 16 : (B >= 8 ? 4 : 1)), dim3(128), 0, (hipStream_t)stream, rows, B, S, d, dx, T_,
-                       thr, scale, seed, site, d_te);
+                       dr.thr, dr.scale, seed, site, d_te);
     TIM_CHECK_LAUNCH();
   }
   return TIMHIP_OK;
@@ -1662,27 +1654,30 @@ int timhip_gather_rows(int precision, const void* x_T, int B, int S, int E, int 
   return TIMHIP_OK;
 }
 
-static int fill_ranges(RowRanges& rr, int count, const int* s0, const int* n) {
-  if (count < 1 || count > RR_MAX || !s0 || !n) return TIMHIP_EINVAL;
+// The one argument check of the range entry points: `count` (min_count .. RR_MAX) token ranges of n[i] > 0 rows from s0[i], each with
+// a buffer of its own, non-NULL and aligned to `align` bytes.  Fills rr: the ranges, the prefix sums of n, and the buffers as
+// rr.src (scatter: they are read) or rr.dst (they are written).
+static int fill_ranges(RowRanges& rr, int count, const int* s0, const int* n, const void* const* bufs, bool scatter,
+                       int min_count = 1, uintptr_t align = 1) {
+  if (count < min_count || count > RR_MAX || (count > 0 && (!s0 || !n || !bufs))) return TIMHIP_EINVAL;
   rr.count = count;
   rr.joff[0] = 0;
   for (int i = 0; i < RR_MAX; ++i) {
-    rr.s0[i] = i < count ? s0[i] : 0;
-    rr.n[i] = i < count ? n[i] : 0;
-    if (i < count && n[i] <= 0) return TIMHIP_EINVAL;
+    const bool on = i < count;
+    if (on && (n[i] <= 0 || !bufs[i] || ((uintptr_t)bufs[i] & (align - 1)))) return TIMHIP_EINVAL;
+    rr.s0[i] = on ? s0[i] : 0;
+    rr.n[i] = on ? n[i] : 0;
     rr.joff[i + 1] = rr.joff[i] + rr.n[i];
-    rr.src[i] = nullptr; rr.dst[i] = nullptr;
+    rr.src[i] = on && scatter ? bufs[i] : nullptr;
+    rr.dst[i] = on && !scatter ? const_cast<void*>(bufs[i]) : nullptr;
   }
   return TIMHIP_OK;
 }
 
 int timhip_gather_ranges(int precision, const void* x_T, int B, int S, int E, int count, const int* s0, const int* n,
                          void* const* rows_T, void* stream) {
-  if (!x_T || !rows_T || B <= 0 || E % 4) return TIMHIP_EINVAL;
   RowRanges rr;
-  int rc = fill_ranges(rr, count, s0, n);
-  if (rc) return rc;
-  for (int i = 0; i < count; ++i) { if (!rows_T[i]) return TIMHIP_EINVAL; rr.dst[i] = rows_T[i]; }
+  if (!x_T || B <= 0 || E % 4 || fill_ranges(rr, count, s0, n, rows_T, false)) return TIMHIP_EINVAL;
   DISPATCH_T(precision, hipLaunchKernelGGL(gather_ranges_kernel<T>, dim3(B * rr.joff[count]), dim3(256), 0,
                                            (hipStream_t)stream, (const T*)x_T, B, S, E, rr));
   TIM_CHECK_LAUNCH();
@@ -1691,11 +1686,8 @@ int timhip_gather_ranges(int precision, const void* x_T, int B, int S, int E, in
 
 int timhip_gather_split3_ranges(int precision, const float* x, int B, int S, int E, int count, const int* s0, const int* n,
                                 void* const* rows3_T, void* stream) {
-  if (!x || !rows3_T || B <= 0 || E % 64 || !h16_storage(precision)) return TIMHIP_EINVAL;
   RowRanges rr;
-  int rc = fill_ranges(rr, count, s0, n);
-  if (rc) return rc;
-  for (int i = 0; i < count; ++i) { if (!rows3_T[i] || ((uintptr_t)rows3_T[i] & 7)) return TIMHIP_EINVAL; rr.dst[i] = rows3_T[i]; }
+  if (!x || B <= 0 || E % 64 || !h16_storage(precision) || fill_ranges(rr, count, s0, n, rows3_T, false, 1, 8)) return TIMHIP_EINVAL;
   DISPATCH_H16(precision, hipLaunchKernelGGL(gather_split3_ranges_kernel<HT>, dim3(B * rr.joff[count]), dim3(256), 0,
                                              (hipStream_t)stream, x, B, S, E, rr));
   TIM_CHECK_LAUNCH();
@@ -1704,11 +1696,8 @@ int timhip_gather_split3_ranges(int precision, const float* x, int B, int S, int
 
 int timhip_scatter_ranges_add(int B, int S, int E, int count, const int* s0, const int* n, const float* const* d_rows,
                               float* dx, void* stream) {
-  if (!d_rows || !dx || B <= 0 || E % 4) return TIMHIP_EINVAL;
   RowRanges rr;
-  int rc = fill_ranges(rr, count, s0, n);
-  if (rc) return rc;
-  for (int i = 0; i < count; ++i) { if (!d_rows[i]) return TIMHIP_EINVAL; rr.src[i] = d_rows[i]; }
+  if (!dx || B <= 0 || E % 4 || fill_ranges(rr, count, s0, n, (const void* const*)d_rows, true)) return TIMHIP_EINVAL;
   hipLaunchKernelGGL(scatter_ranges_add_kernel, dim3(B * rr.joff[count]), dim3(256), 0, (hipStream_t)stream, B, S, E, dx, rr);
   TIM_CHECK_LAUNCH();
   return TIMHIP_OK;
@@ -1731,21 +1720,17 @@ int timhip_dx_init(int B, int S, int F, int E, const float* feats_cot, int count
 
 int timhip_dx_init_slabs(int B, int S, int F, int E, const float* feats_cot, int count, const int* s0, const int* n,
                          const float* const* d_rows, const int* nslab, float* dx, void* stream) {
-  if (!dx || B <= 0 || S <= 0 || F < 0 || F > S || E % 4 || count < 0 || count > RR_MAX) return TIMHIP_EINVAL;
-  RowRanges rr;
-  rr.count = 0; rr.joff[0] = 0;
-  for (int i = 0; i < RR_MAX; ++i) { rr.s0[i] = 0; rr.n[i] = 0; rr.joff[i + 1] = 0; rr.src[i] = nullptr; rr.dst[i] = nullptr; }
-  if (count > 0) {
-    if (!s0 || !n || !d_rows) return TIMHIP_EINVAL;
-    for (int i = 0; i < count; ++i) {
-      if (!d_rows[i] || n[i] <= 0 || s0[i] < F || s0[i] + n[i] > S) return TIMHIP_EINVAL;
-      for (int j = 0; j < i; ++j)
-        if (s0[i] < s0[j] + n[j] && s0[j] < s0[i] + n[i]) return TIMHIP_EINVAL;   // overlapping ranges: the caller adds instead
-      rr.s0[i] = s0[i]; rr.n[i] = n[i]; rr.src[i] = d_rows[i];
-      rr.joff[i] = nslab ? nslab[i] : 1;
-      if (rr.joff[i] < 1 || rr.joff[i] > 16) return TIMHIP_EINVAL;
-    }
-    rr.count = count;
+  RowRanges rr;   // (no range at all: feature rows and zeros)
+  if (!dx || B <= 0 || S <= 0 || F < 0 || F > S || E % 4 || fill_ranges(rr, count, s0, n, (const void* const*)d_rows, true, 0))
+    return TIMHIP_EINVAL;
+  for (int i = 0; i < count; ++i) {   // query rows only, and no token row twice
+    if (s0[i] < F || s0[i] + n[i] > S) return TIMHIP_EINVAL;
+    for (int j = 0; j < i; ++j)
+      if (s0[i] < s0[j] + n[j] && s0[j] < s0[i] + n[i]) return TIMHIP_EINVAL;   // overlapping ranges: the caller adds instead
+  }
+  for (int i = 0; i <= RR_MAX; ++i) {   // dx_init_kernel reads joff[i] as the number of slabs of range i
+    rr.joff[i] = i < count ? (nslab ? nslab[i] : 1) : 0;
+    if (i < count && (rr.joff[i] < 1 || rr.joff[i] > 16)) return TIMHIP_EINVAL;
   }
   hipLaunchKernelGGL(dx_init_kernel, dim3(B * S), dim3(256), 0, (hipStream_t)stream, B, S, F, E, feats_cot, dx, rr);
   TIM_CHECK_LAUNCH();
