@@ -630,7 +630,11 @@ int timhip_smooth_one_hot(const int64_t* qlabels, int ld, int col, int64_t rows,
  * utils/mixup.py:24-39:  loss = lam * mean_{r: ta[r] != -1} CE(logits[r], ta[r]) + (1-lam) * mean_{r: tb[r] != -1}
  * CE(logits[r], tb[r]),  CE with label smoothing `smoothing` (torch.nn.CrossEntropyLoss(label_smoothing, ignore_index=-1)).
  * target_b may be NULL (plain criterion, lam = 1).  stats [rows,4] and accum [4] are scratch kept for the backward;
- * loss is a device scalar.  dlogits = grad_out[0] * d loss / d logits (grad_out: device scalar or NULL = 1). */
+ * loss is a device scalar.  dlogits = grad_out[0] * d loss / d logits (grad_out: device scalar or NULL = 1).
+ * logits is [rows, C] with row pitch ld >= C, dlogits [rows, C] with row pitch ldd >= C (elements; columns from C on are neither
+ * read nor written); no alignment beyond that of a float.  rows >= 1, 0 <= smoothing < 1, else TIMHIP_EINVAL.  A target outside
+ * [0, C) is ignored like -1; a side without a valid row contributes 0 and its rows get no gradient.  stats[r] = (logsumexp,
+ * mean, CE_a or -1, CE_b or -1), accum = (sum_a, n_a, sum_b, n_b); no atomics: two calls give the same bits. */
 int timhip_ce_mixup_fwd(const float* logits, int rows, int C, int ld, const int64_t* target_a, const int64_t* target_b,
                         float lam, float smoothing, float* stats, float* accum, float* loss, void* stream);
 int timhip_ce_mixup_bwd(const float* logits, int rows, int C, int ld, const int64_t* target_a, const int64_t* target_b,
@@ -640,7 +644,11 @@ int timhip_ce_mixup_bwd(const float* logits, int rows, int C, int ld, const int6
 /* DRLoc sample collection (models/helpers/losses/drloc.py:11-15,24-26,37-39): out[(b*m+i), 0:D] = x1[b, pos1[b,i], :],
  * out[.., D:2D] = x2[b, pos2[b,i], :], cast to the operand dtype ([n*m, ld] GEMM operand of drloc_mlp.0).
  * x1, x2: fp32 [n, l, D] views with element strides (batch_stride, row_stride, 1).  The scatter adds the gradient
- * of that operand back: dx1[b, pos1[b,i], :] += d_pts[(b*m+i), 0:D] (fp32 atomics; positions repeat). */
+ * of that operand back: dx1[b, pos1[b,i], :] += d_pts[(b*m+i), 0:D] (fp32 atomics; positions repeat).
+ * gather: D, ld, batch_stride and row_stride are multiples of 4, ld >= 2D (else TIMHIP_EINVAL); x1, x2 and out are 16-byte
+ * aligned (else TIMHIP_EALIGN); columns of out from 2D on are not written; x1 and x2 may overlap or coincide.  scatter: d_pts has
+ * row pitch ldg >= 2D; dx1 / dx2 are accumulated onto (not zeroed) and may overlap or coincide; no alignment rule.  Positions must
+ * lie in [0, l): they are not checked. */
 int timhip_drloc_gather(int precision, const float* x1, const float* x2, int64_t batch_stride, int64_t row_stride,
                         int n, int l, int D, const int64_t* pos1, const int64_t* pos2, int m, void* out, int ld,
                         void* stream);
@@ -652,7 +660,11 @@ int timhip_drloc_scatter_add(const float* d_pts, int ldg, float* dx1, float* dx2
 /* sigmoid focal loss (detection models/helpers/losses/sigmoid.py:5-52) under get_loss(.., weights, reduction="sum")
  * (losses/loss.py:5-14):  loss_sum = sum_{r: valid[r]} w[r] * sum_c focal(logits[r,c], targets[r,c]);  targets are the
  * smoothed one-hot floats of det tim.py:157-184; row_weights / row_valid may be NULL; loss_elem (optional, [rows,C])
- * receives the weighted per-element terms (reduction "none").  bwd: dlogits = grad_out[0] * d loss_sum / d logits. */
+ * receives the weighted per-element terms (reduction "none").  bwd: dlogits = grad_out[0] * d loss_sum / d logits.
+ * logits, targets, loss_elem and dlogits are dense [rows, C] (no pitch argument), float aligned; rows with row_valid == 0 give
+ * exactly 0 in loss_elem and dlogits.  alpha < 0: no alpha weighting; any gamma >= 0 (gamma == 2 takes a multiply instead of powf;
+ * where 1 - p_t is 0 the gradient's second term is its limit 0).  rows == 0: loss_sum is zeroed, nothing else is written.
+ * loss_sum is joined with one atomic per block: its last bits depend on the order. */
 int timhip_focal_loss_fwd(const float* logits, const float* targets, int rows, int C, const float* row_weights,
                           const uint8_t* row_valid, float alpha, float gamma, float* loss_sum, float* loss_elem,
                           void* stream);
@@ -660,7 +672,10 @@ int timhip_focal_loss_bwd(const float* logits, const float* targets, int rows, i
                           const uint8_t* row_valid, float alpha, float gamma, const float* grad_out, float* dlogits,
                           void* stream);
 /* 1-D centre-offset DIoU loss (losses/iou.py:4-65), summed over the valid rows; offsets are [n,2] = (left, right).
- * loss_sum and/or dpred (= grad_out[0] * d loss / d pred) are produced when non-NULL. */
+ * loss_sum and/or dpred (= grad_out[0] * d loss / d pred) are produced when non-NULL; both NULL is TIMHIP_EINVAL; n == 0 zeroes
+ * loss_sum and writes nothing else.  Dense [n,2] arrays, float aligned; rows with row_valid == 0 give 0.  The gradient follows the
+ * compiled TorchScript form of the reference: min / max pass a gradient under strict comparison only (nothing to the tied side of
+ * an exact tie), clamp(min=eps) where its input >= eps. */
 int timhip_diou_1d(const float* pred_offsets, const float* target_offsets, int n, const uint8_t* row_valid, float eps,
                    const float* grad_out, float* loss_sum, float* dpred, void* stream);
 /* One modality side of the detection training loss (det scripts/train.py:222-349) with the row flags derived where they are used:
@@ -669,7 +684,11 @@ int timhip_diou_1d(const float* pred_offsets, const float* target_offsets, int n
  *   normaliser <- momentum * normaliser + (1 - momentum) * max(positives, 1)      (device scalar, in / out)
  *   loss = focal / (nheads * normaliser) + (positives > 0 ? lambda_reg * DIoU / normaliser : 0)
  * block (device float[8], out) = {loss, focal sum, DIoU sum, positives, normaliser used, 0, 0, 0}; the backward reads it.
- * logits / targets / dlogits: host arrays of device pointers, [rows, C[k]] each; dlogits[k] may be NULL, dreg may be NULL. */
+ * logits / targets / dlogits: host arrays of device pointers, dense [rows, C[k]] each; dlogits[k] may be NULL, dreg may be NULL.
+ * 1 <= nheads <= 4, and with rows > 0 every head that is read (forward: all; backward: those with dlogits[k] != NULL) has logits[k],
+ * targets[k] and C[k] >= 1, else TIMHIP_EINVAL; every argument is checked before the first launch, so a refused call writes nothing.
+ * Rows with iou < 0 get exactly 0 in every dlogits[k], non-positive rows exactly 0 in dreg (same tie / clamp rule as
+ * timhip_diou_1d).  grad_out: device scalar or NULL = 1.  All arrays float aligned; block is 8 floats, all of them written. */
 int timhip_det_side_loss_fwd(const float* const* logits, const float* const* targets, const int* C, int nheads, int rows,
                              const float* iou, const float* offsets, const float* reg_pred, float iou_threshold, float alpha,
                              float gamma, float eps, float lambda_reg, float momentum, float* normaliser, float* block,

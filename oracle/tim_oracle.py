@@ -381,8 +381,10 @@ def focal_loss(x, t, weights=None, alpha=0.25, gamma=2.0, reduction="sum"):
 def diou_1d(pred, tgt, eps=1e-8):
     """detection models/helpers/losses/iou.py:4-65 ("sum").  The reference function is TorchScript; once compiled its
     autodiff gives min / max a gradient only under STRICT inequality and clamp(min) only where the input >= min (its first,
-    profiling calls split exact ties like eager torch) - the torch.where forms below are the compiled behaviour; the golden
-    vectors contain no exact ties."""
+    profiling calls split exact ties like eager torch) - the torch.where forms below are the compiled behaviour.
+    tests/golden/loss_det_ties.npz holds the reference's compiled-call loss and gradient on rows with exact ties, zeros and
+    unions / enclosing lengths on either side of eps (tests/test_loss_oracle.py pins this function to it); the other
+    loss_det_*.npz vectors contain no exact ties."""
     lp, rp, lg, rg = pred[:, 0], pred[:, 1], tgt[:, 0].detach(), tgt[:, 1].detach()
     smin = lambda a, b: torch.where(a < b, a, b)
     smax = lambda a, b: torch.where(a > b, a, b)

@@ -1,7 +1,7 @@
 """Golden vectors for the loss tail from the reference's own functions (build container only).
 
     python tests/golden/make_golden_loss.py              (recognition: mixup CE, DRLoc)
-    python tests/golden/make_golden_loss.py detection    (detection: focal, DIoU)
+    python tests/golden/make_golden_loss.py detection    (detection: focal, DIoU, DIoU at exact ties)
 
 Imports utils/mixup.py and models/helpers/losses/drloc.py of /root/reference/recognition (torch + numpy only) and the
 reference TIM module (for its drloc_mlp), feeds them inputs that `tim_amd.synth` regenerates from a seed, and stores
@@ -124,7 +124,68 @@ def det_case(name, rows, C, n_reg, seed):
     print(name, "focal", loss.item(), "diou", reg.item())
 
 
+def save_npz_fixed(path, **arrays):
+    """np.savez with a fixed member timestamp: the same numbers give the same bytes on every run"""
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_STORED) as z:
+        for k, v in arrays.items():
+            with z.open(zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0)), "w") as f:
+                np.lib.format.write_array(f, np.asanyarray(v), allow_pickle=False)
+
+
+def diou_tie_rows(seed):
+    """(pred | off) rows [n, 4] for the tie / clamp rules of ctr_diou_loss_1d: every kind of exact tie, zeros, values that put
+    the union and the enclosing length well below eps = 1e-8 (2^-30) and just above it (2^-23, 2^-22), ordinary rows in between.
+    Every special value is a power of two or a small dyadic number, so fp32 and fp64 see the same comparisons; U and Lc stay
+    a factor of more than 4 away from eps on either side, or are exactly 0."""
+    a, b, c = 2.0 ** -31, 2.0 ** -32, 2.0 ** -24
+    special = [
+        (0.5, 0.75, 0.5, 0.25), (1.25, 0.5, 1.25, 2.0),            # lp == lg only
+        (0.25, 1.0, 0.75, 1.0), (3.0, 0.125, 0.5, 0.125),          # rp == rg only
+        (0.5, 0.5, 0.5, 0.5), (1.5, 0.25, 1.5, 0.25),              # both
+        (0.0, 0.0, 0.0, 0.0),                                      # U = Lc = 0: both clamps hold the gradient back
+        (0.0, 0.5, 0.0, 0.25), (0.5, 0.0, 0.25, 0.0),              # one side 0 in both (a tie at 0)
+        (0.0, 0.5, 0.25, 0.5), (0.75, 0.0, 0.75, 0.5),             # one value 0, a tie on the other side
+        (0.0, 0.0, 0.5, 0.25), (0.5, 0.25, 0.0, 0.0),              # prediction all 0 / target all 0: I = 0
+        (0.0, 0.375, 0.625, 0.0),                                  # opposite zeros: I = 0, no tie
+        (a, b, b, a), (a, a, a, a), (b, a, b, b),                  # U, Lc = 2^-30 .. 2^-31 < eps / 4, with and without ties
+        (c, 2 * c, 2 * c, c), (c, c, c, c), (2 * c, c, 2 * c, 4 * c),   # U, Lc = 2^-23 .. 2^-21 > 4 eps
+        (0.5, a, 0.5, b), (c, 1.0, 0.0, 1.0),                      # tiny against ordinary
+    ]
+    rnd = synth.uniform(seed, "diou_ties", (len(special), 4), 0.0, 2.0).astype(np.float32)
+    rows = []
+    for s, r in zip(special, rnd):                                 # ordinary rows in between
+        rows.append(np.asarray(s, dtype=np.float32))
+        rows.append(r)
+    return np.stack(rows)
+
+
+def det_ties_case(name, seed):
+    """ctr_diou_loss_1d ("sum") on rows with exact ties and clamped denominators.  The function is TorchScript: its first call
+    runs the profiling executor (eager autograd: ties split their gradient), the later ones the differentiated graph (strict
+    comparisons).  Four calls on fresh leaves; calls 2-4 must agree bit for bit and are what is stored."""
+    from time_interval_machine.models.helpers.losses.iou import ctr_diou_loss_1d
+    v = diou_tie_rows(seed)
+    off = torch.from_numpy(v[:, 2:].copy())
+    out = []
+    for _ in range(4):
+        pred = torch.from_numpy(v[:, :2].copy()).requires_grad_(True)
+        loss = ctr_diou_loss_1d(pred, off, reduction="sum")
+        loss.backward()
+        out.append((loss.detach().numpy().copy(), pred.grad.numpy().copy()))
+    for l, g in out[2:]:
+        assert l.tobytes() == out[1][0].tobytes() and g.tobytes() == out[1][1].tobytes(), "compiled calls disagree"
+    rowloss = ctr_diou_loss_1d(torch.from_numpy(v[:, :2].copy()), off, reduction="none").numpy()
+    save_npz_fixed(os.path.join(HERE, "loss_det_%s.npz" % name), seed=np.int64(seed), pred=v[:, :2], off=v[:, 2:],
+                   diou=out[1][0], dpred=out[1][1], rowloss=rowloss, dpred_first_call=out[0][1])
+    print(name, "diou", float(out[1][0]), "rows", len(v), "first call differs in",
+          int((out[0][1] != out[1][1]).any(1).sum()), "rows")
+
+
 if __name__ == "__main__" and VARIANT == "detection":
+    # first: its first call must be the process's first call of the TorchScript function.  (The cases after it then take their DIoU
+    # gradient from the compiled graph; they hold no ties, and it equals the first call's to one fp32 rounding.)
+    det_ties_case("ties", 33)
     det_case("small", 29, 13, 9, 31)
     det_case("verb", 399 * 2, 97, 40, 32)
 

@@ -13,7 +13,8 @@ from tim_amd.config import named_config
 from tests.helpers import GOLDEN
 
 CE_CASES = sorted(os.path.basename(f) for f in glob.glob(os.path.join(GOLDEN, "loss_ce_*.npz")))
-DET_CASES = sorted(os.path.basename(f) for f in glob.glob(os.path.join(GOLDEN, "loss_det_*.npz")))
+DIOU_TIE_CASES = ["loss_det_ties.npz"]            # DIoU only: exact ties and clamped denominators (make_golden_loss.py det_ties_case)
+DET_CASES = sorted(set(os.path.basename(f) for f in glob.glob(os.path.join(GOLDEN, "loss_det_*.npz"))) - set(DIOU_TIE_CASES))
 DR_CASES = sorted(os.path.basename(f) for f in glob.glob(os.path.join(GOLDEN, "loss_drloc_*.npz")))
 
 
@@ -91,3 +92,29 @@ def test_detection_losses_oracle_matches_reference(case):
     reg.backward()
     assert abs(reg.item() - float(g["diou"])) <= 1e-6 * abs(float(g["diou"]))
     assert np.abs(pred.grad.numpy() - g["dpred"]).max() <= 1e-6
+
+
+@pytest.mark.parametrize("case", DIOU_TIE_CASES)
+def test_diou_oracle_matches_reference_on_ties(case):
+    """The compiled form of the reference's ctr_diou_loss_1d (its second and later calls) on rows with lp == lg, rp == rg, zeros
+    and unions / enclosing lengths on either side of eps: min / max pass a gradient under strict comparison only, clamp(min=eps)
+    where its input >= eps.  The reference computes in fp32: its gradient is held to 8 fp32 roundings of the sum of the
+    magnitudes of its terms, 2 / max(U, eps) + 1 / max(Lc, eps) per row (values reach 1e8 where a clamp is active)."""
+    g = np.load(os.path.join(GOLDEN, case))
+    pred = torch.from_numpy(g["pred"]).double().requires_grad_(True)
+    off = torch.from_numpy(g["off"]).double()
+    reg = O.diou_1d(pred, off)
+    reg.backward()
+    assert abs(reg.item() - float(g["diou"])) <= 1e-6 * abs(float(g["diou"]))
+    lp, rp, lg, rg = pred.detach()[:, 0], pred.detach()[:, 1], off[:, 0], off[:, 1]
+    inter = torch.minimum(lp, lg) + torch.minimum(rp, rg)
+    union = (lp + rp) + (lg + rg) - inter
+    len_c = torch.maximum(lp, lg) + torch.maximum(rp, rg)
+    scale = 2.0 / union.clamp(min=1e-8) + 1.0 / len_c.clamp(min=1e-8)
+    err = (pred.grad - torch.from_numpy(g["dpred"]).double()).abs()
+    assert bool((err <= 8 * 2.0 ** -24 * scale[:, None]).all()), (err / scale[:, None]).max().item()
+    # the fixture does contain what it is for: ties on either side, on both, all-zero rows, both clamps on either side of eps
+    assert bool(((lp == lg) & (rp != rg)).any() and ((lp != lg) & (rp == rg)).any() and ((lp == lg) & (rp == rg)).any())
+    assert bool(((union == 0) & (len_c == 0)).any() and ((union > 0) & (union < 2.5e-9)).any() and ((union > 4e-8) & (union < 1e-6)).any())
+    # and the first (profiling) call of the reference, which splits ties, is a different gradient: a split-tie implementation fails
+    assert np.abs(g["dpred_first_call"] - g["dpred"]).max() > 0.1

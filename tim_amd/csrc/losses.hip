@@ -365,11 +365,12 @@ int timhip_det_side_loss_fwd(const float* const* logits, const float* const* tar
                              void* stream) {
   if (!logits || !targets || !C || nheads < 1 || nheads > 4 || rows < 0 || !iou || !offsets || !reg_pred || !normaliser || !block)
     return TIMHIP_EINVAL;
+  for (int k = 0; k < nheads && rows > 0; ++k)     // every head is checked before the first launch: a refused call writes nothing
+    if (!logits[k] || !targets[k] || C[k] <= 0) return TIMHIP_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(det_zero_kernel, dim3(1), dim3(64), 0, s, block);
   if (rows > 0) {
     for (int k = 0; k < nheads; ++k) {
-      if (!logits[k] || !targets[k] || C[k] <= 0) return TIMHIP_EINVAL;
       const long long n = (long long)rows * C[k];
       const int blocks = (int)((n + 255) / 256 > 512 ? 512 : (n + 255) / 256);   // one atomic per block on a single address
       hipLaunchKernelGGL(det_focal_fwd_kernel, dim3(blocks), dim3(256), 0, s, logits[k], targets[k], n, C[k], iou, iou_threshold,
@@ -389,6 +390,8 @@ int timhip_det_side_loss_bwd(const float* const* logits, const float* const* tar
                              float* const* dlogits, float* dreg, void* stream) {
   if (!logits || !targets || !C || nheads < 1 || nheads > 4 || rows < 0 || !iou || !offsets || !reg_pred || !block || !dlogits)
     return TIMHIP_EINVAL;
+  for (int k = 0; k < nheads && rows > 0; ++k)     // (a head whose gradient is not asked for is not read)
+    if (dlogits[k] && (!logits[k] || !targets[k] || C[k] <= 0)) return TIMHIP_EINVAL;
   if (rows == 0) return TIMHIP_OK;
   hipStream_t s = (hipStream_t)stream;
   for (int k = 0; k < nheads; ++k) {
