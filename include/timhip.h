@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define TIMHIP_VERSION 6   /* 6, additive (no layout or signature change, so no new number): timhip_det_candidates_{count,emit}, timhip_stack_infer, timhip_stack_infer_workspace_bytes, timhip_attention_fwd_rows, TIMHIP_EPI_GELU_T, lse = NULL in timhip_attention_fwd; 6 (round 6): timhip_timing_stop_families; 5 (round 5): timhip_assemble_{fwd,bwd}_p (token / modality vectors by pointer), timhip_dx_init_slabs, timhip_det_side_loss_{fwd,bwd}, timhip_sigmoid_bwd_rows, timhip_time_l1_fwd_split3, timhip_gather_split3_ranges, TIMHIP_EPI_RELU_SPLIT3_T, timhip_layernorm_{fwd,bwd}2, timhip_cast_rows_pair; 4 (round 4): 8-word timhip_grad_scale block + non-finite flag, TIMHIP_DESC_STREAM16*, timhip_dx_init, timhip_reload_env */
+#define TIMHIP_VERSION 6   /* 6, additive (no layout or signature change, so no new number): timhip_rec_{accumulate,finalize,counts}, timhip_det_candidates_{count,emit}, timhip_stack_infer, timhip_stack_infer_workspace_bytes, timhip_attention_fwd_rows, TIMHIP_EPI_GELU_T, lse = NULL in timhip_attention_fwd; 6 (round 6): timhip_timing_stop_families; 5 (round 5): timhip_assemble_{fwd,bwd}_p (token / modality vectors by pointer), timhip_dx_init_slabs, timhip_det_side_loss_{fwd,bwd}, timhip_sigmoid_bwd_rows, timhip_time_l1_fwd_split3, timhip_gather_split3_ranges, TIMHIP_EPI_RELU_SPLIT3_T, timhip_layernorm_{fwd,bwd}2, timhip_cast_rows_pair; 4 (round 4): 8-word timhip_grad_scale block + non-finite flag, TIMHIP_DESC_STREAM16*, timhip_dx_init, timhip_reload_env */
 
 enum {
   TIMHIP_OK = 0,
@@ -744,6 +744,47 @@ int timhip_det_candidates_emit(const float* logits, int64_t ld_logits, const flo
                                const int32_t* row_offsets, const int32_t* video_index, int R, int C, int Nq,
                                float score_threshold, int64_t capacity, float* seg, float* score, int64_t* key,
                                int32_t* row, void* stream);
+
+/* ---------------------------------------------------------------- recognition scores and accuracies */
+/* The inference tail behind the recognition heads, as the reference computes it on the host in
+ * recognition/time_interval_machine/utils/meters.py (InferenceMeter / FeatureMeter: index_add_ of the valid query rows into
+ * per-action accumulators, division by the seen count, softmax) and utils/metrics.py (accuracy, multitask_accuracy).
+ *
+ * State, all persistent device buffers the caller zero-fills (labels_state: -1) before the first batch: per head
+ * sum [num_actions, pitch] fp32 (pitch >= C; a multiple of 64 aligns the stores), seen [num_actions] fp32 (one vector for
+ * all modalities, as in the reference), and per modality labels_state [num_actions, n_labels] int32, touched [num_actions]
+ * bytes; one int32 error word.
+ *
+ * rec_accumulate: one batch of one modality.  heads: HOST array of n_heads (<= TIMHIP_REC_MAX_HEADS) heads that share the id
+ *   vector; logits [R, C] fp32 with row stride ld (elements, >= C: a strided view needs no copy).  ids [R] int64.  A row is
+ *   valid iff valid[r] != 0, or with valid = NULL iff labels[r * ld_labels + valid_col] != -1; labels [R, n_labels] int64
+ *   (NULL with a valid vector: labels_state is left alone).  Invalid rows are not read.  A valid row whose id is outside
+ *   [0, num_actions) is skipped and ORs 1 into *err.  For every id of the batch: sum[id] = (((sum[id] + x_r0) + x_r1) + ...)
+ *   in fp32 over its valid rows in ascending row order - what a serial index_add_ leaves - so the state does not depend on
+ *   how a stream is cut into batches; seen[id] += the number of those rows; labels_state[id] = the labels of the last of
+ *   them; touched[id] = 1.  work: 3 * R int32 of scratch.  Three launches on `stream`, no floating-point atomics, no
+ *   allocation, no host read: replayable in a HIP graph.
+ * rec_finalize: one head over the touched actions.  mean = sum / seen (fp32, correctly rounded);
+ *   rank[a] = #{c : mean_c > mean_l} + #{c < l : mean_c == mean_l} for l = labels_state[a, label_col] (0x7fffffff for an
+ *   untouched action, a label outside [0, C) or labels_state = NULL); with prob != NULL also
+ *   prob[a, c] = (float)(exp((double)mean_c - max) / sum of those exps in double) for c < C, [num_actions, pitch]; rows of
+ *   untouched actions are not written.
+ * rec_counts: counts[0] = #(r < 1), counts[1] = #(r < 5), counts[2] = #touched over the touched actions, r = rank_a or, with
+ *   rank_b != NULL, max(rank_a, rank_b) (the multitask accuracy). */
+#define TIMHIP_REC_MAX_HEADS 3
+typedef struct TimRecHead {
+  const float* logits;
+  float* sum;
+  int64_t ld;
+  int32_t C, pitch;
+} TimRecHead;
+int timhip_rec_accumulate(const TimRecHead* heads, int n_heads, const int64_t* ids, const uint8_t* valid,
+                          const int64_t* labels, int64_t ld_labels, int n_labels, int valid_col, int R, int num_actions,
+                          float* seen, int32_t* labels_state, uint8_t* touched, int32_t* err, int32_t* work, void* stream);
+int timhip_rec_finalize(const float* sum, int pitch, int C, const float* seen, const int32_t* labels_state, int n_labels,
+                        int label_col, const uint8_t* touched, int num_actions, float* prob, int32_t* rank, void* stream);
+int timhip_rec_counts(const int32_t* rank_a, const int32_t* rank_b, const uint8_t* touched, int num_actions, int32_t* counts,
+                      void* stream);
 
 /* ---------------------------------------------------------------- sliding-window batch assembly */
 /* recognition datasets/sliding_window.py:341-421 (__getitem__) for a batch, on feature stores resident in HBM.

@@ -22,6 +22,9 @@ def __getattr__(name):  # lazy: importing the package must not require torch on 
     if name == "DetectionCollector":
         from .detect import DetectionCollector
         return DetectionCollector
+    if name == "RecognitionCollector":
+        from .recog import RecognitionCollector
+        return RecognitionCollector
     if name == "optim":
         import importlib
         return importlib.import_module(".optim", __name__)

@@ -88,6 +88,12 @@ class TimGemmItem(C.Structure):
                 ("e", TimEpi)]
 
 
+class TimRecHead(C.Structure):
+    _fields_ = [("logits", vp), ("sum", vp), ("ld", C.c_int64), ("C", i32), ("pitch", i32)]
+
+
+REC_MAX_HEADS = 3   # include/timhip.h: TIMHIP_REC_MAX_HEADS
+
 _SIGS = {
     "timhip_version": (C.c_int, []),
     "timhip_strerror": (C.c_char_p, [C.c_int]),
@@ -157,6 +163,9 @@ _SIGS = {
     "timhip_nms_1d": (C.c_int, [vp, vp, vp, i32, f32, vp, vp, vp, vp]),
     "timhip_det_candidates_count": (C.c_int, [vp, C.c_int64, vp, vp, f32, vp, i32, i32, i32, f32, vp, vp, vp, vp]),
     "timhip_det_candidates_emit": (C.c_int, [vp, C.c_int64, vp, vp, vp, vp, i32, i32, i32, f32, C.c_int64, vp, vp, vp, vp, vp]),
+    "timhip_rec_accumulate": (C.c_int, [vp, i32, vp, vp, vp, C.c_int64, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+    "timhip_rec_finalize": (C.c_int, [vp, i32, i32, vp, vp, i32, i32, vp, i32, vp, vp, vp]),
+    "timhip_rec_counts": (C.c_int, [vp, vp, vp, i32, vp, vp]),
     "timhip_window_gather": (C.c_int, [vp, i32, i32, vp, vp, i32, vp, i32, vp, vp, vp]),
     "timhip_window_times": (C.c_int, [vp, i32, vp, vp, i32, vp, vp, i32, vp, i32, vp, i32, vp, i32, vp, f32, vp, vp]),
     "timhip_gemm_timing_start": (C.c_int, [i32, C.c_double]),
