@@ -343,8 +343,8 @@ int timhip_grad_scale(const float* const* cot, const long long* counts, int n, f
 /* fp32 -> T with optional dropout (p_drop > 0) and zero padding to ld; scale: optional device scalar multiplied in */
 int timhip_cast_rows(int precision, const float* src, int rows, int cols, int lds, void* dst, int ld,
                      float p_drop, uint64_t seed, uint32_t site, const float* scale, void* stream);
-/* timhip_cast_rows for TWO contiguous fp32 matrices with the same row count in one launch (the two embedders' inputs: widths
- * cols[i], operand rows of stride ld[i], dropout site sites[i]; same masks as two timhip_cast_rows calls) */
+/* timhip_cast_rows for TWO contiguous fp32 matrices with the same row count in one launch of the same kernel (the two embedders'
+ * inputs: widths cols[i], operand rows of stride ld[i], dropout site sites[i]; same masks as two timhip_cast_rows calls) */
 int timhip_cast_rows_pair(int precision, const float* const* src, const int* cols, void* const* dst, const int* ld, int rows,
                           float p_drop, uint64_t seed, const uint32_t* sites, void* stream);
 
@@ -576,12 +576,12 @@ int timhip_assemble_bwd_p(const TimSeqRow* rows, int B, int S, int d, const floa
  * per access - with TIMHIP_PREC_FP32 as the element type also the fp32 rows and [rows, 2] statistics of the evaluation tail) */
 int timhip_gather_rows(int precision, const void* x_T, int B, int S, int E, int s0, int n,
                        void* rows_T, void* stream);
-/* dx[b, s0+i, :] += d_rows[b*n+i, :]  (fp32) */
+/* dx[b, s0+i, :] += d_rows[b*n+i, :]  (fp32; E % 4 == 0) */
 int timhip_scatter_rows_add(const float* d_rows, int B, int S, int E, int s0, int n, float* dx,
                             void* stream);
-/* The same moves for up to 6 token ranges in one launch (the four classification heads; the ranges of a scatter must be
- * DISJOINT - heads that share token rows, as in the detection model, go through timhip_scatter_rows_add one by one), and the
- * fp32 -> operand-dtype
+/* The same moves for up to 6 token ranges in one launch (the four classification heads; the two entry points above are the
+ * one-range calls of these kernels; E % 4 == 0, B > 0; the ranges of a scatter must be DISJOINT - heads that share token rows,
+ * as in the detection model, go into separate launches), and the fp32 -> operand-dtype
  * cast of several cotangent matrices (dst[i] is [rows[i], ld[i]], zero padded beyond cols[i]) in one launch. */
 int timhip_gather_ranges(int precision, const void* x_T, int B, int S, int E, int count, const int* s0, const int* n,
                          void* const* rows_T, void* stream);

@@ -539,6 +539,53 @@ def test_gather_rows_narrow(prec):
         assert o.guards_intact() and same_bits(o.v.cpu(), x[:, 14:19].reshape(B * 5, E))
 
 
+ONE_RANGE = [(0, 1), (4, 3), (6, 1)]   # of S = 7 token rows: the first row, a range that ends at S, the last row alone
+
+
+@pytest.mark.parametrize("prec", PRECS)
+def test_gather_single_entry_is_the_one_range_entry(prec):
+    """timhip_gather_rows and timhip_gather_ranges with one range are one kernel: both equal x[b, s0:s0+n] bit for bit (a copy: no
+    tolerance); E = 260 walks a second column step with a ragged end; E % 4 != 0 is the single entry's alone"""
+    B, S, T = 2, 7, DT[prec]
+    for E in (4, 8, 260) + ((2, 6) if prec == "fp32" else ()):
+        x = rn(B, S, E, seed=E).to(T)
+        xd = x.to(DEV)
+        for s0, n in ONE_RANGE:
+            want = x[:, s0:s0 + n].reshape(B * n, E)
+            o1 = Out(B * n, E, T)
+            L.call("timhip_gather_rows", L.PRECISIONS[prec], L.ptr(xd), B, S, E, s0, n, o1.ptr, st())
+            o = Out(B * n, E, T)
+            rc = L.load().timhip_gather_ranges(L.PRECISIONS[prec], L.ptr(xd), B, S, E, 1, ia([s0]), ia([n]), pa([o.v]), st())
+            sync()
+            assert o1.guards_intact() and same_bits(o1.v.cpu(), want), (E, s0, n)
+            if E % 4:
+                assert rc == -1 and same_bits(o.whole, o.before)      # TIMHIP_EINVAL, nothing written
+            else:
+                assert rc == 0 and o.guards_intact() and same_bits(o.v.cpu(), want), (E, s0, n)
+        assert same_bits(xd.cpu(), x)
+
+
+def test_scatter_single_entry_is_the_one_range_entry():
+    """timhip_scatter_rows_add and timhip_scatter_ranges_add with one range: one fp32 addition per element of the range onto a
+    pre-filled stream, equal to the same addition on the host and to each other bit for bit; every other row bit-unchanged"""
+    B, S = 2, 7
+    for E in (4, 260):
+        for s0, n in ONE_RANGE:
+            rows = rn(B * n, E, seed=E + s0)
+            rows_d = rows.to(DEV)
+            dx1, dx = Out(B * S, E, fill="acc"), Out(B * S, E, fill="acc")
+            want = dx.pre.cpu().view(B, S, E).clone()
+            want[:, s0:s0 + n] += rows.view(B, n, E)
+            L.call("timhip_scatter_rows_add", L.ptr(rows_d), B, S, E, s0, n, dx1.ptr, st())
+            L.call("timhip_scatter_ranges_add", B, S, E, 1, ia([s0]), ia([n]), pa([rows_d]), dx.ptr, st())
+            sync()
+            assert dx1.guards_intact() and dx.guards_intact()
+            assert same_bits(dx1.v, dx.v) and same_bits(dx.v.cpu(), want.view(B * S, E)), (E, s0, n)
+            outside = [s for s in range(S) if not s0 <= s < s0 + n]
+            assert same_bits(dx.v.view(B, S, E)[:, outside], dx.pre.view(B, S, E)[:, outside])
+            assert same_bits(rows_d.cpu(), rows)
+
+
 @pytest.mark.parametrize("prec", ["bf16", "fp16"])
 @pytest.mark.parametrize("B", [1, 3])
 @pytest.mark.parametrize("E", [64, 1024])
@@ -648,6 +695,68 @@ def test_cast_rows_many(prec):
                 assert same_bits(o.v.cpu(), want.to(T)), (r, c, ld)
             assert blk is None or same_bits(blk, scale_block(0, sv))
     assert all(same_bits(a.cpu(), b) for a, b in zip(src_d, src))
+
+
+def _cast_check(got, src, cols, ld, T, p, seed, site, vs):
+    """got == the torch restatement of timhip_cast_rows: T(x * mask / (1 - p) * vs), zero from `cols` to `ld`; the mask is
+    timhip_dropout_mask's at a row pitch of `cols` rounded up to a multiple of 4 (the kernel draws per column quad).  Equal as
+    values everywhere, no tolerance; bit for bit wherever the mask keeps (a dropped x < 0 is x * 0 = -0 on most paths and +0 where
+    the compiler fuses the fp16 conversion into a multiply-add with a +0 addend: the sign of that zero is nobody's contract)"""
+    rows = src.shape[0]
+    v = src[:, :cols].cpu()
+    kept = torch.ones(rows, ld, dtype=torch.bool)
+    if p > 0:
+        pitch = (cols + 3) // 4 * 4
+        mk = torch.empty((rows, pitch), dtype=torch.uint8, device=DEV)
+        L.call("timhip_dropout_mask", seed, site, p, rows, pitch, L.ptr(mk), st())
+        sync()
+        kept[:, :cols] = mk.cpu()[:, :cols] != 0
+        v = v * (kept[:, :cols].float() / (1 - p))
+    want = torch.zeros(rows, ld, dtype=T)
+    want[:, :cols] = (v * vs).to(T)
+    got = got.cpu()
+    return torch.equal(got, want) and same_bits(got[kept], want[kept])
+
+
+CAST_SHAPES = [(5, 5, 8), (8, 12, 8), (8, 8, 64), (1, 1, 64)]
+#  (cols, lds, ld): scalar tail; strided source, 16-byte path; zero padding out to ld; the loss path's one column
+
+
+@pytest.mark.parametrize("prec", PRECS)
+def test_cast_rows_one_item_and_pair(prec):
+    """timhip_cast_rows and timhip_cast_rows_pair are one kernel over one or two items: a round-to-nearest cast of x * mask / (1 - p)
+    * scale with p = 0.5 and scale = 0.5 (both products exact), so every case equals the torch restatement bit for bit; the pair
+    equals two single calls bit for bit"""
+    T, rows, seed = DT[prec], 3, 0x1234567
+    half = torch.tensor([0.5], device=DEV)
+    for cols, lds, ld, off in [c + (0,) for c in CAST_SHAPES] + [(8, 12, 8, 1)]:   # off = 1: the source starts 4 bytes past a
+        flat = rn(rows * lds + off, seed=cols + lds + ld).to(DEV)                   # 16-byte boundary: element by element
+        src = flat[off:].view(rows, lds)
+        assert src.data_ptr() % 16 == 4 * off
+        for p in (0.0, 0.5):
+            for vs in (None, half):
+                o = Out(rows, ld, T)
+                L.call("timhip_cast_rows", L.PRECISIONS[prec], L.ptr(src), rows, cols, lds, o.ptr, ld, p, seed, L.SITE_FEAT_V,
+                       L.ptr(vs), st())
+                sync()
+                assert o.guards_intact(), (cols, lds, ld, off, p, vs is not None)
+                assert _cast_check(o.v, src, cols, ld, T, p, seed, L.SITE_FEAT_V, 0.5 if vs is not None else 1.0), \
+                    (cols, lds, ld, off, p, vs is not None)
+                assert bool((o.v[:, cols:] == 0).all())
+    assert same_bits(half.cpu(), torch.tensor([0.5]))
+    # the pair: two contiguous matrices of different widths and sites
+    cols, lds_out, sites = (5, 8), (8, 64), (L.SITE_FEAT_V, L.SITE_FEAT_A)
+    srcs = [rn(rows, c, seed=40 + c).to(DEV) for c in cols]
+    for p in (0.0, 0.5):
+        pair = [Out(rows, ld, T) for ld in lds_out]
+        L.call("timhip_cast_rows_pair", L.PRECISIONS[prec], pa(srcs), ia(cols), pa([o.v for o in pair]), ia(lds_out), rows, p, seed,
+               (C.c_uint32 * 2)(*sites), st())
+        for x, c, ld, site, o2 in zip(srcs, cols, lds_out, sites, pair):
+            o1 = Out(rows, ld, T)
+            L.call("timhip_cast_rows", L.PRECISIONS[prec], L.ptr(x), rows, c, c, o1.ptr, ld, p, seed, site, None, st())
+            sync()
+            assert o1.guards_intact() and o2.guards_intact() and same_bits(o1.v, o2.v), (c, p)
+            assert _cast_check(o2.v, x, c, ld, T, p, seed, site, 1.0), (c, p)
 
 
 @pytest.mark.parametrize("prec", PRECS)

@@ -214,18 +214,21 @@ __global__ void slab_reduce_kernel(const float* __restrict__ slab, long long n, 
   }
 }
 
-// fp32 rows -> T rows with optional dropout and zero padding
+// fp32 rows -> T rows with optional dropout and zero padding, for one matrix or two with the same row count in one launch
+// (blockIdx.z = item; the two modality embedders' inputs: different widths, different dropout sites)
+struct CastRows { const float* src[2]; void* dst[2]; int cols[2], lds[2], ld[2]; uint32_t site[2]; };
 template <typename T>
-__global__ void cast_rows_kernel(const float* __restrict__ src, int rows, int cols, int lds_, T* __restrict__ dst,
-                                 int ld, uint32_t thr, float scale, TimSeed seed, uint32_t site,
-                                 const float* __restrict__ vscale) {
-  const int r = blockIdx.y;
+__global__ void cast_rows_kernel(CastRows cr, int rows, uint32_t thr, float scale, TimSeed seed, const float* __restrict__ vscale) {
+  const int z = blockIdx.z, r = blockIdx.y;
+  const float* __restrict__ src = cr.src[z];
+  T* __restrict__ dst = (T*)cr.dst[z];
+  const int cols = cr.cols[z], lds_ = cr.lds[z], ld = cr.ld[z];
   const float vs = vscale ? *vscale : 1.f;   // factor on the values (gradient scale of the fp16 mode)
   const int colsq = (cols + 3) >> 2;
   const bool vec = (lds_ & 3) == 0 && ((((uintptr_t)src) & 15) == 0) && ((((uintptr_t)dst) & 15) == 0);   // (ld % 4 == 0 always)
   for (int q = blockIdx.x * blockDim.x + threadIdx.x; q * 4 < ld; q += gridDim.x * blockDim.x) {
     float k[4] = {1.f, 1.f, 1.f, 1.f};
-    if (thr != 0u && q < colsq) drop_mask4(seed, site, (uint64_t)r * colsq + q, thr, scale, k[0], k[1], k[2], k[3]);
+    if (thr != 0u && q < colsq) drop_mask4(seed, cr.site[z], (uint64_t)r * colsq + q, thr, scale, k[0], k[1], k[2], k[3]);
     if (vec && q * 4 + 3 < cols) {   // 16-byte load, one 8- / 16-byte store
       const float4 v = *reinterpret_cast<const float4*>(src + (size_t)r * lds_ + q * 4);
       store4<T>(dst + (size_t)r * ld + q * 4, v.x * k[0] * vs, v.y * k[1] * vs, v.z * k[2] * vs, v.w * k[3] * vs);
@@ -235,32 +238,6 @@ __global__ void cast_rows_kernel(const float* __restrict__ src, int rows, int co
     for (int j = 0; j < 4; ++j) {
       const int c = q * 4 + j;
       if (c < ld) dst[(size_t)r * ld + c] = OpT<T>::from_f(c < cols ? src[(size_t)r * lds_ + c] * k[j] * vs : 0.f);
-    }
-  }
-}
-
-// two matrices with the same row count in one launch (blockIdx.z): the two modality embedders' inputs - same arithmetic and the same
-// mask indexing as cast_rows_kernel (row * quads-per-row + quad, per site), contiguous fp32 rows
-struct CastPair { const float* src[2]; void* dst[2]; int cols[2], ld[2]; uint32_t site[2]; };
-template <typename T>
-__global__ void cast_rows_pair_kernel(CastPair cp, int rows, uint32_t thr, float scale, TimSeed seed) {
-  const int z = blockIdx.z, r = blockIdx.y;
-  const float* __restrict__ src = cp.src[z];
-  T* __restrict__ dst = (T*)cp.dst[z];
-  const int cols = cp.cols[z], ld = cp.ld[z], colsq = (cols + 3) >> 2;
-  const bool vec = (cols & 3) == 0 && ((((uintptr_t)src) & 15) == 0) && ((((uintptr_t)dst) & 15) == 0);
-  for (int q = blockIdx.x * blockDim.x + threadIdx.x; q * 4 < ld; q += gridDim.x * blockDim.x) {
-    float k[4] = {1.f, 1.f, 1.f, 1.f};
-    if (thr != 0u && q < colsq) drop_mask4(seed, cp.site[z], (uint64_t)r * colsq + q, thr, scale, k[0], k[1], k[2], k[3]);
-    if (vec && q * 4 + 3 < cols) {
-      const float4 v = *reinterpret_cast<const float4*>(src + (size_t)r * cols + q * 4);
-      store4<T>(dst + (size_t)r * ld + q * 4, v.x * k[0], v.y * k[1], v.z * k[2], v.w * k[3]);
-      continue;
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int c = q * 4 + j;
-      if (c < ld) dst[(size_t)r * ld + c] = OpT<T>::from_f(c < cols ? src[(size_t)r * cols + c] * k[j] : 0.f);
     }
   }
 }
@@ -943,12 +920,31 @@ __global__ __launch_bounds__(128) void assemble_bwd_te_kernel(const TimSeqRow* _
   }
 }
 
+// ---- row moves between the [B,S,E] stream and per-head buffers, for up to RR_MAX token ranges in one launch (the classification
+// heads: 4 ranges per direction; timhip_gather_rows / timhip_scatter_rows_add: one range) ----
+constexpr int RR_MAX = 6;
+struct RowRanges {
+  const void* src[RR_MAX]; void* dst[RR_MAX];   // per range: gathered / per-head buffer on one side, the [B,S,E] stream on the other
+  int s0[RR_MAX], n[RR_MAX], joff[RR_MAX + 1];  // token range, prefix of n
+  int count;
+};
+// block `blk` of B * joff[count] -> batch item b, range r and row j of that range (one range: blk = b * n + j)
+__device__ __forceinline__ void range_row(const RowRanges& rr, int blk, int& b, int& r, int& j) {
+  const int per = rr.joff[rr.count];
+  b = blk / per;
+  const int jg = blk % per;
+  r = 0;
+#pragma unroll
+  for (int k = 1; k < RR_MAX; ++k)
+    if (k < rr.count && jg >= rr.joff[k]) r = k;
+  j = jg - rr.joff[r];
+}
 template <typename T>
-__global__ void gather_rows_kernel(const T* __restrict__ xt, int B, int S, int E, int s0, int n, T* __restrict__ out) {
-  const int i = blockIdx.x;  // b*n + j
-  const int b = i / n, j = i % n;
-  const T* src = xt + ((size_t)b * S + s0 + j) * E;
-  T* dst = out + (size_t)i * E;
+__global__ void gather_ranges_kernel(const T* __restrict__ xt, int B, int S, int E, RowRanges rr) {
+  int b, r, j;
+  range_row(rr, blockIdx.x, b, r, j);
+  const T* src = xt + ((size_t)b * S + rr.s0[r] + j) * E;
+  T* dst = (T*)rr.dst[r] + ((size_t)b * rr.n[r] + j) * E;
   if (E & 3) {   // narrow rows (the [rows, 2] LayerNorm statistics of timhip_stack_infer's query-row tail): element by element
     for (int c = threadIdx.x; c < E; c += blockDim.x) dst[c] = src[c];
     return;
@@ -959,55 +955,12 @@ __global__ void gather_rows_kernel(const T* __restrict__ xt, int B, int S, int E
     store4<T>(dst + c, a0, a1, a2, a3);
   }
 }
-__global__ void scatter_rows_add_kernel(const float* __restrict__ d_rows, int B, int S, int E, int s0, int n,
-                                        float* __restrict__ dx) {
-  const int i = blockIdx.x;
-  const int b = i / n, j = i % n;
-  const float* src = d_rows + (size_t)i * E;
-  float* dst = dx + ((size_t)b * S + s0 + j) * E;
-  for (int c = threadIdx.x * 4; c < E; c += blockDim.x * 4) {
-    const float4 a = *reinterpret_cast<const float4*>(src + c);
-    float4 o = *reinterpret_cast<float4*>(dst + c);
-    o.x += a.x; o.y += a.y; o.z += a.z; o.w += a.w;
-    *reinterpret_cast<float4*>(dst + c) = o;
-  }
-}
-
-// ---- the same row moves for several token ranges in one launch (the classification heads: 4 ranges per direction) ----
-constexpr int RR_MAX = 6;
-struct RowRanges {
-  const void* src[RR_MAX]; void* dst[RR_MAX];   // per range: gathered / per-head buffer on one side, the [B,S,E] stream on the other
-  int s0[RR_MAX], n[RR_MAX], joff[RR_MAX + 1];  // token range, prefix of n
-  int count;
-};
-template <typename T>
-__global__ void gather_ranges_kernel(const T* __restrict__ xt, int B, int S, int E, RowRanges rr) {
-  const int per = rr.joff[rr.count];
-  const int b = blockIdx.x / per, jg = blockIdx.x % per;
-  int r = 0;
-#pragma unroll
-  for (int k = 1; k < RR_MAX; ++k)
-    if (k < rr.count && jg >= rr.joff[k]) r = k;
-  const int j = jg - rr.joff[r];
-  const T* src = xt + ((size_t)b * S + rr.s0[r] + j) * E;
-  T* dst = (T*)rr.dst[r] + ((size_t)b * rr.n[r] + j) * E;
-  for (int c = threadIdx.x * 4; c < E; c += blockDim.x * 4) {
-    float a0, a1, a2, a3;
-    load4<T>(src + c, a0, a1, a2, a3);
-    store4<T>(dst + c, a0, a1, a2, a3);
-  }
-}
 // the gathered fp32 rows written straight as split operands [hi | lo | hi] (three 16-bit column blocks of width E, row stride 3 E):
 // gather_ranges + split3 (mode 0) of the classification heads' fp16 path in one launch, without the fp32 row buffers
 template <typename T>
 __global__ void gather_split3_ranges_kernel(const float* __restrict__ x, int B, int S, int E, RowRanges rr) {
-  const int per = rr.joff[rr.count];
-  const int b = blockIdx.x / per, jg = blockIdx.x % per;
-  int r = 0;
-#pragma unroll
-  for (int k = 1; k < RR_MAX; ++k)
-    if (k < rr.count && jg >= rr.joff[k]) r = k;
-  const int j = jg - rr.joff[r];
+  int b, r, j;
+  range_row(rr, blockIdx.x, b, r, j);
   const float* src = x + ((size_t)b * S + rr.s0[r] + j) * E;
   T* dst = (T*)rr.dst[r] + ((size_t)b * rr.n[r] + j) * 3 * E;
   for (int c = threadIdx.x * 4; c < E; c += blockDim.x * 4) {
@@ -1022,13 +975,8 @@ __global__ void gather_split3_ranges_kernel(const float* __restrict__ x, int B, 
   }
 }
 __global__ void scatter_ranges_add_kernel(int B, int S, int E, float* __restrict__ dx, RowRanges rr) {
-  const int per = rr.joff[rr.count];
-  const int b = blockIdx.x / per, jg = blockIdx.x % per;
-  int r = 0;
-#pragma unroll
-  for (int k = 1; k < RR_MAX; ++k)
-    if (k < rr.count && jg >= rr.joff[k]) r = k;
-  const int j = jg - rr.joff[r];
+  int b, r, j;
+  range_row(rr, blockIdx.x, b, r, j);
   const float* src = (const float*)rr.src[r] + ((size_t)b * rr.n[r] + j) * E;
   float* dst = dx + ((size_t)b * S + rr.s0[r] + j) * E;
   for (int c = threadIdx.x * 4; c < E; c += blockDim.x * 4) {
@@ -1085,6 +1033,7 @@ __global__ void sigmoid_bwd_rows_kernel(const float* __restrict__ g, const float
 }
 
 // fp32 [rows, cols] -> T [rows, ld] (zero padded) for several matrices in one launch (blockIdx.z = matrix)
+// (kept apart from cast_rows_kernel: per-matrix row counts, any ld, no dropout - and its loop runs inside the timed step)
 struct CastMany {
   const float* src[RR_MAX]; void* dst[RR_MAX];
   int rows[RR_MAX], cols[RR_MAX], ld[RR_MAX];
@@ -1466,15 +1415,29 @@ int timhip_colsum(int precision, const void* src, int rows, int cols, int ld, fl
   return tim_colsum(precision, src, rows, cols, ld, out, (hipStream_t)stream);
 }
 
-int timhip_cast_rows(int precision, const float* src, int rows, int cols, int lds_, void* dst, int ld, float p_drop,
-                     uint64_t seed, uint32_t site, const float* vscale, void* stream) {
-  if (!src || !dst || rows <= 0 || cols <= 0 || ld < cols || ld % 4) return TIMHIP_EINVAL;
+// the one launch of the row casts: `count` (1 or 2) matrices of `rows` rows; grid.x sized by the widest
+static int cast_rows_launch(int precision, int count, const float* const* src, const int* cols, const int* lds_, void* const* dst,
+                            const int* ld, int rows, float p_drop, uint64_t seed, const uint32_t* sites, const float* vscale,
+                            void* stream) {
+  if (rows <= 0) return TIMHIP_EINVAL;
+  CastRows cr = {};
+  int maxq = 0;
+  for (int i = 0; i < count; ++i) {
+    if (!src[i] || !dst[i] || cols[i] <= 0 || ld[i] < cols[i] || ld[i] % 4) return TIMHIP_EINVAL;
+    cr.src[i] = src[i]; cr.dst[i] = dst[i]; cr.cols[i] = cols[i]; cr.lds[i] = lds_[i]; cr.ld[i] = ld[i]; cr.site[i] = sites[i];
+    maxq = ld[i] / 4 > maxq ? ld[i] / 4 : maxq;
+  }
   const DropArgs dr = drop_args(p_drop);
-  dim3 grid((ld / 4 + 255) / 256, rows);
-  DISPATCH_T(precision, hipLaunchKernelGGL(cast_rows_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, src, rows,
-                                           cols, lds_, (T*)dst, ld, dr.thr, dr.scale, seed, site, vscale));
+  dim3 grid((maxq + 255) / 256, rows, count);
+  DISPATCH_T(precision, hipLaunchKernelGGL(cast_rows_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, cr, rows, dr.thr,
+                                           dr.scale, TimSeed(seed), vscale));
   TIM_CHECK_LAUNCH();
   return TIMHIP_OK;
+}
+
+int timhip_cast_rows(int precision, const float* src, int rows, int cols, int lds_, void* dst, int ld, float p_drop,
+                     uint64_t seed, uint32_t site, const float* vscale, void* stream) {
+  return cast_rows_launch(precision, 1, &src, &cols, &lds_, &dst, &ld, rows, p_drop, seed, &site, vscale, stream);
 }
 
 int timhip_dropout_rows_bwd(const float* g, int rows, int cols, int ldg, float* dx, int ldx, float p_drop,
@@ -1523,23 +1486,11 @@ int timhip_layernorm_bwd2(int precision, const float* dx, int lddx, const float*
                            nullptr, (hipStream_t)stream, false, t_scale, nullptr, 0, nullptr, 0, split_row, w2, dgamma2, dbeta2);
 }
 
-// two feature matrices (the two modality embedders' inputs: different widths, different dropout sites) cast in one launch
+// two contiguous feature matrices (the two modality embedders' inputs: different widths, different dropout sites) cast in one launch
 int timhip_cast_rows_pair(int precision, const float* const* src, const int* cols, void* const* dst, const int* ld, int rows,
                           float p_drop, uint64_t seed, const uint32_t* sites, void* stream) {
-  if (!src || !cols || !dst || !ld || !sites || rows <= 0) return TIMHIP_EINVAL;
-  CastPair cp;
-  int maxq = 0;
-  for (int i = 0; i < 2; ++i) {
-    if (!src[i] || !dst[i] || cols[i] <= 0 || ld[i] < cols[i] || ld[i] % 4) return TIMHIP_EINVAL;
-    cp.src[i] = src[i]; cp.dst[i] = dst[i]; cp.cols[i] = cols[i]; cp.ld[i] = ld[i]; cp.site[i] = sites[i];
-    maxq = ld[i] / 4 > maxq ? ld[i] / 4 : maxq;
-  }
-  const DropArgs dr = drop_args(p_drop);
-  dim3 grid((maxq + 255) / 256, rows, 2);
-  DISPATCH_T(precision, hipLaunchKernelGGL(cast_rows_pair_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, cp, rows, dr.thr,
-                                           dr.scale, TimSeed(seed)));
-  TIM_CHECK_LAUNCH();
-  return TIMHIP_OK;
+  if (!src || !cols || !dst || !ld || !sites) return TIMHIP_EINVAL;
+  return cast_rows_launch(precision, 2, src, cols, cols, dst, ld, rows, p_drop, seed, sites, nullptr, stream);
 }
 
 int timhip_time_l1_fwd(int precision, const float* times, int rows, int d, const float* w, const float* b, void* h,
@@ -1646,14 +1597,6 @@ int timhip_assemble_bwd_p(const TimSeqRow* rows, int B, int S, int d, const floa
   return assemble_bwd_launch(rows, B, S, d, dx, n_e_rows, T_, p_seq_drop, seed, site, d_e0, d_e1, sg, d_te, stream);
 }
 
-int timhip_gather_rows(int precision, const void* x_T, int B, int S, int E, int s0, int n, void* rows_T, void* stream) {
-  if (!x_T || !rows_T || n <= 0 || E <= 0) return TIMHIP_EINVAL;   // (E % 4 != 0: the element-wise form)
-  DISPATCH_T(precision, hipLaunchKernelGGL(gather_rows_kernel<T>, dim3(B * n), dim3(256), 0, (hipStream_t)stream,
-                                           (const T*)x_T, B, S, E, s0, n, (T*)rows_T));
-  TIM_CHECK_LAUNCH();
-  return TIMHIP_OK;
-}
-
 // The one argument check of the range entry points: `count` (min_count .. RR_MAX) token ranges of n[i] > 0 rows from s0[i], each with
 // a buffer of its own, non-NULL and aligned to `align` bytes.  Fills rr: the ranges, the prefix sums of n, and the buffers as
 // rr.src (scatter: they are read) or rr.dst (they are written).
@@ -1671,6 +1614,15 @@ static int fill_ranges(RowRanges& rr, int count, const int* s0, const int* n, co
     rr.src[i] = on && scatter ? bufs[i] : nullptr;
     rr.dst[i] = on && !scatter ? const_cast<void*>(bufs[i]) : nullptr;
   }
+  return TIMHIP_OK;
+}
+
+int timhip_gather_rows(int precision, const void* x_T, int B, int S, int E, int s0, int n, void* rows_T, void* stream) {
+  RowRanges rr;   // (E % 4 != 0: the element-wise form)
+  if (!x_T || E <= 0 || fill_ranges(rr, 1, &s0, &n, &rows_T, false)) return TIMHIP_EINVAL;
+  DISPATCH_T(precision, hipLaunchKernelGGL(gather_ranges_kernel<T>, dim3(B * n), dim3(256), 0, (hipStream_t)stream,
+                                           (const T*)x_T, B, S, E, rr));
+  TIM_CHECK_LAUNCH();
   return TIMHIP_OK;
 }
 
@@ -1699,6 +1651,14 @@ int timhip_scatter_ranges_add(int B, int S, int E, int count, const int* s0, con
   RowRanges rr;
   if (!dx || B <= 0 || E % 4 || fill_ranges(rr, count, s0, n, (const void* const*)d_rows, true)) return TIMHIP_EINVAL;
   hipLaunchKernelGGL(scatter_ranges_add_kernel, dim3(B * rr.joff[count]), dim3(256), 0, (hipStream_t)stream, B, S, E, dx, rr);
+  TIM_CHECK_LAUNCH();
+  return TIMHIP_OK;
+}
+
+int timhip_scatter_rows_add(const float* d_rows, int B, int S, int E, int s0, int n, float* dx, void* stream) {
+  RowRanges rr;
+  if (!dx || E % 4 || fill_ranges(rr, 1, &s0, &n, (const void* const*)&d_rows, true)) return TIMHIP_EINVAL;
+  hipLaunchKernelGGL(scatter_ranges_add_kernel, dim3(B * n), dim3(256), 0, (hipStream_t)stream, B, S, E, dx, rr);
   TIM_CHECK_LAUNCH();
   return TIMHIP_OK;
 }
@@ -1766,13 +1726,6 @@ int timhip_ln_partials_reduce(const float* partials, int nsets, int rows, int co
   const long long stride = (long long)(tim_layernorm_bwd_ws(rows, cols) / sizeof(float));
   hipLaunchKernelGGL(partial_colsum_sets_kernel, dim3((2 * cols + 255) / 256, 32, nsets), dim3(256), 0, (hipStream_t)stream,
                      partials, stride, nblk, cols, ls);
-  TIM_CHECK_LAUNCH();
-  return TIMHIP_OK;
-}
-
-int timhip_scatter_rows_add(const float* d_rows, int B, int S, int E, int s0, int n, float* dx, void* stream) {
-  if (!d_rows || !dx || n <= 0 || E % 4) return TIMHIP_EINVAL;
-  hipLaunchKernelGGL(scatter_rows_add_kernel, dim3(B * n), dim3(256), 0, (hipStream_t)stream, d_rows, B, S, E, s0, n, dx);
   TIM_CHECK_LAUNCH();
   return TIMHIP_OK;
 }

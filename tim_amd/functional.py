@@ -701,14 +701,26 @@ OUT_SLOTS = ("verb", "noun", "action", "audio", "feats", "reg_visual", "reg_audi
 
 
 def _gather_head_rows(rt, x, B, S, E, ranges, st, prec=None):
-    """ranges: [(s0, n, rows[B*n, E])]: rows = x[b, s0 + i, :] (x: [B*S, E]; element type of precision `prec`, default rt's)"""
+    """ranges: [(s0, n, rows[B*n, E])]: rows = x[b, s0 + i, :] (x: [B*S, E], E % 4 == 0; element type of precision `prec`, default
+    rt's); one launch per 6 ranges"""
     prec = rt.prec if prec is None else prec
-    if 2 <= len(ranges) <= 6:
-        call("timhip_gather_ranges", prec, ptr(x), B, S, E, len(ranges), _iarr([r[0] for r in ranges]),
-             _iarr([r[1] for r in ranges]), _parr([r[2] for r in ranges]), st)
-    else:
-        for s0, n, rows in ranges:
-            call("timhip_gather_rows", prec, ptr(x), B, S, E, s0, n, ptr(rows), st)
+    for i0 in range(0, len(ranges), 6):
+        grp = ranges[i0:i0 + 6]
+        call("timhip_gather_ranges", prec, ptr(x), B, S, E, len(grp), _iarr([r[0] for r in grp]), _iarr([r[1] for r in grp]),
+             _parr([r[2] for r in grp]), st)
+
+
+def _scatter_head_rows(B, S, E, items, dx, st):
+    """items: [(d_rows[B*n, E], s0, n)]: dx[b, s0 + i, :] += d_rows[b*n + i, :], in the order given; one launch per run of at most 6
+    items whose token ranges are disjoint (heads that share token rows, as in the detection model, go into separate launches)"""
+    groups = []
+    for it in items:
+        if not groups or len(groups[-1]) == 6 or any(it[1] < g[1] + g[2] and g[1] < it[1] + it[2] for g in groups[-1]):
+            groups.append([])
+        groups[-1].append(it)
+    for grp in groups:
+        call("timhip_scatter_ranges_add", B, S, E, len(grp), _iarr([g[1] for g in grp]), _iarr([g[2] for g in grp]),
+             _parr([g[0] for g in grp]), ptr(dx), st)
 
 
 class _Pass:
@@ -895,7 +907,7 @@ def _reg_heads_fwd(q, P, xL_t, outs, row0=0):
         h2 = rt.out_op(B * n, hid, dev)
         y = torch.empty((B * n, 2), dtype=torch.float32, device=dev)
         if n > 0:
-            call("timhip_gather_rows", rt.prec, ptr(xL_t), B, q.S - row0, E, s0 - row0, n, ptr(rows), q.st)
+            _gather_head_rows(rt, xL_t, B, q.S - row0, E, [(s0 - row0, n, rows)], q.st)
             rt.gemm(L.EPI_RELU_T, rows, rt.weight(P[pre + "0.weight"]), B * n, hid, E, h1, h1.shape[1],
                     bias=_f32c(P[pre + "0.bias"]))
             rt.gemm(L.EPI_RELU_T, h1, rt.weight(P[pre + "2.weight"]), B * n, hid, hid, h2, h2.shape[1],
@@ -964,9 +976,8 @@ def _heads_bwd(q, k, heads, g, dx):
             dx3[:, :q.F].zero_()
         if S > q.F:
             dx3[:, q.F:].zero_()
-        for d_rows, s0, n, ns in scatter:
-            for j in range(ns):
-                call("timhip_scatter_rows_add", ptr(d_rows[j] if ns > 1 else d_rows), B, S, E, s0, n, ptr(dx), st)
+        slabs = [(d_rows[j] if ns > 1 else d_rows, s0, n) for d_rows, s0, n, ns in scatter for j in range(ns)]
+        _scatter_head_rows(B, S, E, slabs, dx, st)
     return wg_items
 
 
@@ -974,7 +985,7 @@ def _reg_heads_bwd(q, k, regs, g, dx):
     """regression heads: their input gradients added into `dx` -> their weight-gradient items"""
     rt, dev, st, B, E = q.rt, q.dev, q.st, q.B, q.E
     P, G, hid = k.P, k.G, E // 2
-    wg_items = []
+    wg_items, scatter = [], []
     for r in regs:
         go, n, h1, h2 = g[r.slot], r.n, r.h1, r.h2
         if go is None or n == 0:
@@ -994,7 +1005,8 @@ def _reg_heads_bwd(q, k, regs, g, dx):
         wg_items.append((dh1, hid, r.rows, E, B * n, G[pre + "0.weight"], G[pre + "0.bias"]))
         d_rows = torch.empty((B * n, E), dtype=torch.float32, device=dev)
         rt.gemm(L.EPI_ADD_F32, dh1, rt.weight(P[pre + "0.weight"], True), B * n, E, hid, d_rows, E, acc_scale=k.gs_out)
-        call("timhip_scatter_rows_add", ptr(d_rows), B, q.S, E, r.s0, n, ptr(dx), st)
+        scatter.append((d_rows, r.s0, n))
+    _scatter_head_rows(B, q.S, E, scatter, dx, st)
     return wg_items
 
 
