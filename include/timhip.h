@@ -786,6 +786,40 @@ int timhip_rec_finalize(const float* sum, int pitch, int C, const float* seen, c
 int timhip_rec_counts(const int32_t* rank_a, const int32_t* rank_b, const uint8_t* touched, int num_actions, int32_t* counts,
                       void* stream);
 
+/* ---------------------------------------------------------------- detection scoring: detections to AP */
+/* The ActivityNet-style interpolated average precision of the reference's scoring script (detection/eval_detection/
+ * evaluate_detection_json.py: compute_average_precision_detection, segment_iou, interpolated_prec_rec), on tables the caller
+ * has sorted and grouped (tim_amd/detmap.py does it with device sorts).  All segment arithmetic is in double.
+ *
+ * timhip_det_match: pred_seg [n_pred, 2]: the predictions ordered by class, inside a class by descending score; a
+ *   prediction's row is its position.  gt_seg [n_gt, 2]: the ground-truth segments grouped by (class, video); group g holds
+ *   rows [group_gt_off[g], group_gt_off[g + 1]) (n_groups + 1 values).  group_pred [n_pred]: the predictions' positions
+ *   grouped the same way, ascending inside a group; group g's predictions are group_pred[group_pred_lo[g] ..
+ *   group_pred_hi[g]) (an empty range: the group has none), group_pos0[g] the position of the first prediction of g's class.
+ *   For every prediction, in the order of its group's range, and every threshold t < T: tiou = inter / union with
+ *   inter = max(min(pe, ge) - max(ps, gs), 0), union = (ge - gs) + (pe - ps) - inter against each segment of the group; the
+ *   segment with the largest tiou among those with tiou >= thresholds[t] that no earlier prediction took at t (equal tiou:
+ *   the higher row) is taken: tp[t, position] = 1 and lock[t, segment row] = position - group_pos0[g], the prediction's rank
+ *   inside its class.  tp [T, n_pred] must be zero-filled and lock [T, n_gt] filled with -1 by the caller: a prediction
+ *   that takes nothing (or belongs to no group: no ground truth of its class in its video) keeps 0 - a false positive, the
+ *   false-positive flag is 1 - tp.  work: n_gt uint32 of scratch (lock bits of groups of more than 256 segments; need not
+ *   be cleared).  One launch, one wavefront per group, no atomics; does not allocate, synchronise or read device memory on
+ *   the host.
+ * timhip_det_ap: tp as above, class c's predictions are positions [class_off[c], class_off[c + 1]) (n_classes + 1 values),
+ *   npos[c] its number of ground-truth segments.  ap[t, c] ([T, n_classes] double) = the sum over the true positives k of
+ *   the class of (tpc_k / npos - (tpc_k - 1) / npos) * max_{j >= k} tpc_j / (j + 1), tpc the inclusive count of true
+ *   positives and k the rank inside the class: interpolated_prec_rec.  A class without predictions gets 0.  One launch.
+ * Both return TIMHIP_EINVAL on T outside 1 .. TIMHIP_DET_MAX_THRESHOLDS, a negative count or (with work to do) a null
+ * pointer, TIMHIP_EUNSUPPORTED on counts beyond int32; with no group, no prediction or no class they launch nothing and
+ * leave their outputs as the caller filled them. */
+#define TIMHIP_DET_MAX_THRESHOLDS 16
+int timhip_det_match(const double* pred_seg, int64_t n_pred, const int32_t* group_pred, const int32_t* group_pred_lo,
+                     const int32_t* group_pred_hi, const int32_t* group_pos0, const double* gt_seg, int64_t n_gt,
+                     const int32_t* group_gt_off, int n_groups, const double* thresholds, int T, uint8_t* tp, int32_t* lock,
+                     uint32_t* work, void* stream);
+int timhip_det_ap(const uint8_t* tp, int64_t n_pred, const int32_t* class_off, const int32_t* npos, int n_classes, int T,
+                  double* ap, void* stream);
+
 /* ---------------------------------------------------------------- sliding-window batch assembly */
 /* recognition datasets/sliding_window.py:341-421 (__getitem__) for a batch, on feature stores resident in HBM.
  * feats [sum_v N_feat(v) * num_aug, C] fp32: every video's [N_feat, num_aug, C] array, concatenated;
