@@ -106,7 +106,8 @@ typedef struct TimDesc {
 } TimDesc;
 /* TimDesc.reserved flags */
 #define TIMHIP_DESC_ATTN_FP32 1        /* run the attention in fp32 arithmetic (reference kernels) */
-#define TIMHIP_DESC_ATTN_BWD_ONE_KERNEL 2 /* single-kernel MFMA attention backward */
+#define TIMHIP_DESC_ATTN_BWD_ONE_KERNEL 2 /* accepted and ignored: the single-kernel backward was removed; the fused and two-kernel
+                                             forms give the same result */
 #define TIMHIP_DESC_WGRAD_OVERWRITE 4  /* bf16 only: timhip_layer_bwd_split / _bwd_weights[_pair] WRITE the weight and bias gradients of the four
                                           Linears (dW = ..., not +=): those buffers need no zero fill and are not read */
 #define TIMHIP_DESC_WGRAD_SEPARATE 8   /* bf16 only: four timhip_wgrad launches per layer instead of the grouped one (A/B knob) */
@@ -389,6 +390,10 @@ int timhip_attention_fwd_rows(const TimDesc* d, const void* qkv, int s0, void* o
  * TIMHIP_EUNSUPPORTED (the caller leaves TIMHIP_DESC_ATTN_KEEP_BITS off): everything but 16-bit precisions with 128-wide heads and
  * 97 .. 128 feature keys (the geometry whose kernels read the bits), and evaluation mode (p_drop = 0). */
 int timhip_attn_keep_bits(const TimDesc* d, int nlayers, void* const* saved, void* stream);
+/* Backward of timhip_attention_fwd: dqkv[B*S, 3E] (T) from d_o[B*S, E] (T), with the forward's qkv, o and lse.  16-bit precisions run
+ * the matrix-core kernels (fused, or rows + keys through the workspace) for head widths 128 / 64 / 32 with E a multiple of 8 and
+ * B * H <= 65535; every other shape - a 16-bit backward with B * H > 65535 included - runs the fp32-arithmetic kernel, as under
+ * TIMHIP_DESC_ATTN_FP32.  workspace: timhip_attention_bwd_workspace_bytes (TIMHIP_EWORKSPACE if smaller). */
 int timhip_attention_bwd(const TimDesc* d, const void* qkv, const void* o, const float* lse,
                          const void* d_o, void* dqkv, void* workspace, size_t workspace_bytes,
                          void* stream);

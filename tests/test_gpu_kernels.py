@@ -614,9 +614,38 @@ def test_attention_structured(prec, B, S, F, H, Dh):
 @pytest.mark.parametrize("B,S,F,H,Dh,p", [(2, 499, 100, 8, 128, 0.1), (1, 499, 100, 2, 128, 0.0), (3, 260, 50, 2, 64, 0.1)])
 def test_attention_long_sequence_row_split(prec, B, S, F, H, Dh, p):
     """detection's sequence (S = 499: 100 feature tokens + 399 queries, 16 row blocks) with few (window, head) pairs: the row
-    blocks of a pair are spread over several workgroups (attention_mfma.hip: attn_row_split) in the forward and in the row kernel
+    blocks of a pair are spread over several workgroups (attention.h: attn_row_split) in the forward and in the row kernel
     of the backward - 4 parts of 4 row blocks at S = 499, ragged last part at S = 260 (9 row blocks); with attention dropout"""
     _attn_case(prec, B, S, F, H, Dh, p=p)
+
+
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("B,S,F,H,Dh,p", [(1, 40, 33, 1, 32, 0.0),     # (32, 2)
+                                          (1, 36, 34, 1, 64, 0.0),     # (64, 2): the f32 modes reach it nowhere else
+                                          (1, 100, 97, 1, 64, 0.0),    # (64, 4)
+                                          (1, 35, 32, 2, 128, 0.0),    # (128, 1), no padding keys
+                                          (1, 70, 65, 1, 128, 0.0),    # (128, 3)
+                                          (1, 70, 65, 1, 128, 0.1)])
+def test_attention_shape_table_entries(prec, B, S, F, H, Dh, p):
+    """the (head width, 32-key blocks) pairs of the one shape table (attention.h: attn_for_shape) that no other test reaches, in
+    every family that dispatches through it - with test_attention_structured every entry has a case; one entry with dropout"""
+    _attn_case(prec, B, S, F, H, Dh, p=p)
+
+
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("B,S,F,H,Dh", [(1, 70, 66, 1, 64),      # three key blocks at head width 64: not in the table
+                                        (1, 20, 12, 2, 16)])     # head width 16
+def test_attention_shapes_outside_the_table(prec, B, S, F, H, Dh):
+    """shapes outside the shape table are still right.  (By tim_attention_fwd / _bwd's rule they run attn_fwd_simple /
+    attn_bwd_simple of attention.hip; the test sees the results, not which kernel produced them)"""
+    _attn_case(prec, B, S, F, H, Dh)
+
+
+def test_attention_more_than_65535_window_heads():
+    """B * H = 65536 is still right, forward and backward.  (By the dispatch rule the 16-bit forward stays on the matrix-core
+    kernel - its grid is one-dimensional - and the backward, whose key kernel puts (window, head) on the grid's z axis, runs
+    attn_bwd_simple: include/timhip.h, timhip_attention_bwd.  The test sees the results, not which kernel produced them)"""
+    _attn_case("fp16", 8192, 4, 3, 8, 32)
 
 
 @pytest.mark.parametrize("prec", PRECS)

@@ -93,6 +93,37 @@ def test_stack_infer_checks_its_arguments_before_any_launch():
     assert lib.timhip_attention_fwd_rows(C.byref(d), fake, -1, fake, None) == EINVAL
 
 
+def test_attention_checks_its_descriptor_before_its_pointers():
+    """timhip_attention_fwd / _bwd judge the descriptor first, then the pointers, then launch: none of the pointers below is followed"""
+    lib = L.load()
+    fake = C.c_void_p(0x1000)
+
+    def fwd(d, qkv=fake):
+        return lib.timhip_attention_fwd(C.byref(d), qkv, fake, fake, None)
+
+    def bwd(d, qkv=fake):
+        return lib.timhip_attention_bwd(C.byref(d), qkv, fake, fake, fake, fake, fake, 1 << 20, None)
+    for prec in sorted(L.PRECISIONS):
+        for flags in (0, L.DESC_ATTN_BWD_ONE_KERNEL):
+            wide = _desc("C2a", 8, prec, flags=flags)
+            wide.S, wide.F = 200, 193                              # more feature keys than any attention kernel holds
+            late = _desc("C2a", 8, prec, flags=flags)
+            late.F = late.S + 1
+            ragged = _desc("C2a", 8, prec, flags=flags)
+            ragged.H = 7
+            assert ragged.E % ragged.H != 0
+            for call in (fwd, bwd):
+                assert call(wide) == L.EUNSUPPORTED, (prec, flags)
+                assert call(late) == EINVAL, (prec, flags)
+                assert call(ragged) == EINVAL, (prec, flags)
+                assert call(_desc("C2a", 8, prec, flags=flags), qkv=None) == EINVAL, (prec, flags)
+            # TIMHIP_DESC_ATTN_BWD_ONE_KERNEL is accepted and ignored: a sound descriptor of the rows + keys form (64 feature keys) with
+            # a workspace of a few bytes is refused for the workspace, flag or no flag - no kernel runs without one any more
+            small = _desc("C2a", 8, prec, flags=flags)
+            small.F = 64
+            assert lib.timhip_attention_bwd(C.byref(small), fake, fake, fake, fake, fake, fake, 16, None) == EWORKSPACE, (prec, flags)
+
+
 def test_route_switch_is_read_per_call(monkeypatch):
     """`functional.encoder` picks the evaluation route from the model's mode, the grad mode and TIM_AMD_INFER - nothing cached"""
     import torch

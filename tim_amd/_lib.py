@@ -53,6 +53,7 @@ class TimLayerGrads(C.Structure):
 
 DESC_ATTN_FP32, DESC_ATTN_BWD_ONE_KERNEL, DESC_WGRAD_OVERWRITE, DESC_WGRAD_SEPARATE, DESC_OUTPROJ_SPLIT = 1, 2, 4, 8, 16
 DESC_INPROJ_SPLIT, DESC_L1_SPLIT, DESC_L2_SPLIT = 32, 64, 128   # TimDesc.reserved flags
+# (DESC_ATTN_BWD_ONE_KERNEL: accepted and ignored: the single-kernel backward was removed; the fused and two-kernel forms give the same result)
 DESC_STREAM16, DESC_STREAM16_IN, DESC_STREAM16_OUT = 0x10000, 0x20000, 0x40000   # 16-bit residual gradient stream (fp16 backward)
 EUNSUPPORTED = -2                # include/timhip.h: TIMHIP_EUNSUPPORTED
 DESC_ATTN_KEEP_BITS = 0x80000   # the saved block carries the layer's attention keep-bits (timhip_attn_keep_bits)

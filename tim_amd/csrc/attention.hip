@@ -7,16 +7,9 @@
 // This file holds the fp32-arithmetic kernels (operand storage T = fp32 or
 // bf16): they are the TIMHIP_PREC_FP32 path and the reference point for the
 // MFMA kernels in attention_mfma.hip.
-#include "common.h"
+#include "attention.h"
 
 namespace {
-
-struct AttnArgs {
-  int S, F, E, H, Dh, LP;  // LP = round_up(F + 1, 8): row pitch of the probability dropout stream
-  int s0;                  // first token row computed and stored; rows land compactly, S - s0 per window (0: all rows)
-  float scale;
-  uint32_t thr; float dscale; TimSeed seed; uint32_t site;
-};
 
 __device__ __forceinline__ float attn_keep(const AttnArgs& a, int b, int h, int row, int j) {
   if (a.thr == 0u) return 1.f;
@@ -212,17 +205,6 @@ __global__ __launch_bounds__(256) void attn_bwd_simple(const T* __restrict__ qkv
   }
 }
 
-AttnArgs make_args(const TimDesc& d) {
-  AttnArgs a;
-  a.S = d.S; a.F = d.F; a.E = d.E; a.H = d.H; a.Dh = d.E / d.H; a.LP = round_up(d.F + 1, 8);
-  a.scale = 1.f / sqrtf((float)a.Dh);
-  a.thr = d.p_drop > 0.f ? drop_threshold(d.p_drop) : 0u;
-  a.dscale = d.p_drop > 0.f ? 1.f / (1.f - d.p_drop) : 1.f;
-  a.seed = d.seed; a.site = layer_site(d.layer, SITE_L_ATTN);
-  a.s0 = 0;
-  return a;
-}
-
 size_t simple_lds(const TimDesc& d, int nrowbuf) {
   const int Dh = d.E / d.H;
   const size_t ts = opsize(d.precision);
@@ -237,18 +219,6 @@ int check_desc(const TimDesc& d) {
 }
 
 }  // namespace
-
-int tim_attention_fwd_mfma(const TimDesc& d, const void* qkv, void* o, float* lse, hipStream_t s, const unsigned long long* kbits, int s0);
-int tim_attention_bwd_mfma(const TimDesc& d, const void* qkv, const void* o, const float* lse, const void* d_o,
-                           void* dqkv, hipStream_t s);
-int tim_attention_bwd2_mfma(const TimDesc& d, const void* qkv, const void* o, const float* lse, const void* d_o,
-                            void* dqkv, void* ws, size_t ws_bytes, hipStream_t s, const unsigned long long* kbits);
-size_t tim_attention_bwd2_ws(const TimDesc& d);
-// attention_f32.hip: exact-fp32 MFMA kernels for the fp32 / bf16x3 modes
-int tim_attention_fwd_f32(const TimDesc& d, const void* qkv, void* o, float* lse, hipStream_t s, int s0);
-int tim_attention_bwd_f32(const TimDesc& d, const void* qkv, const void* o, const float* lse, const void* d_o, void* dqkv,
-                          void* ws, size_t ws_bytes, hipStream_t s);
-size_t tim_attention_f32_bwd_ws(const TimDesc& d);
 
 int tim_attention_fwd(const TimDesc& d, const void* qkv, void* o, float* lse, hipStream_t s, const unsigned long long* kbits, int s0) {
   int rc = check_desc(d);
@@ -266,7 +236,7 @@ int tim_attention_fwd(const TimDesc& d, const void* qkv, void* o, float* lse, hi
   }
   const size_t lds = simple_lds(d, 1);
   if (lds > 160 * 1024) return TIMHIP_EUNSUPPORTED;
-  AttnArgs a = make_args(d);
+  AttnArgs a = make_attn_args(d);
   a.s0 = s0;
   DISPATCH_T(d.precision,
     (void)hipFuncSetAttribute((const void*)attn_fwd_simple<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -291,11 +261,7 @@ int tim_attention_bwd(const TimDesc& d, const void* qkv, const void* o, const fl
   // (qkv, o, dO read; dqkv written)
   TimGemmScope timing((double)d.B * d.S * d.E * 8 * (h16_storage(d.precision) ? 2 : 4), s, 1);
   if (h16_storage(d.precision) && !(d.reserved & 1)) {
-    if (!(d.reserved & 2)) {  // reserved bit 1: force the single-kernel MFMA backward
-      rc = tim_attention_bwd2_mfma(d, qkv, o, lse, d_o, dqkv, ws, ws_bytes, s, kbits);
-      if (rc != TIMHIP_EUNSUPPORTED) return rc;
-    }
-    rc = tim_attention_bwd_mfma(d, qkv, o, lse, d_o, dqkv, s);
+    rc = tim_attention_bwd2_mfma(d, qkv, o, lse, d_o, dqkv, ws, ws_bytes, s, kbits);
     if (rc != TIMHIP_EUNSUPPORTED) return rc;
   }
   if (f32_storage(d.precision) && !(d.reserved & 1)) {
@@ -305,7 +271,7 @@ int tim_attention_bwd(const TimDesc& d, const void* qkv, const void* o, const fl
   if (ws_bytes < tim_attention_bwd_ws(d)) return TIMHIP_EWORKSPACE;
   const size_t lds = simple_lds(d, 2);
   if (lds > 160 * 1024) return TIMHIP_EUNSUPPORTED;
-  AttnArgs a = make_args(d);
+  AttnArgs a = make_attn_args(d);
   DISPATCH_T(d.precision,
     (void)hipFuncSetAttribute((const void*)attn_bwd_simple<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(attn_bwd_simple<T>, dim3(d.B * d.H), dim3(256), lds, s, (const T*)qkv, (const T*)o, lse, (const T*)d_o,

@@ -6,23 +6,16 @@
 //   attn_bwd_keys  : dK = dS^T Q and dV = P~^T dO for the F feature keys: a batched "TN" product whose
 //                    contraction runs over the token rows, with both operands read in their natural layout and
 //                    transposed by ds_read_b64_tr_b16 (same scheme as wgrad.hip).
-// Compared with the single-kernel version (attn_bwd_mfma) nothing is recomputed in the transposed orientation:
-// no second exp / Philox pass, and the row kernel runs one wave per row block.
+// Nothing is recomputed in the transposed orientation (the key side reads dS and P~ instead of forming them a second time: no
+// second exp / Philox pass), and the row kernel runs one wave per row block.
 #include <stdlib.h>
 
-#include "common.h"
+#include "attention.h"
 #include "mfma_tiles.h"
 
 namespace {
 
-struct AttnArgsM {
-  int S, F, E, H, LP;
-  float scale;
-  uint32_t thr; float dscale; TimSeed seed; uint32_t site;
-  int abl;  // tuning builds only (TimDesc.reserved >> 8): 1 no scratch stores, 2 no dqkv stores, 4 operand rows alias row 0
-  int rsplit, rper;   // two-kernel form: the row blocks of a (window, head) over rsplit workgroups of rper row blocks (attention_mfma.hip)
-  const unsigned long long* kbits;   // keep-bits drawn ahead of the layer (attention_mfma.hip: tim_attn_keep_bits), or nullptr
-};
+// ATT_ABL / ATT_STAMP: ablation hooks of the tuning build (AttnArgs.abl = TimDesc.reserved >> 8)
 #ifdef TIMHIP_TUNING
 #define ATT_ABL(a, bit) (((a).abl & (bit)) != 0)
 // (tuning, abl bit 16, fused form: wave 0's shader-clock stamps per block into the workspace - tools/attn_one.py prints the phases)
@@ -36,36 +29,12 @@ struct AttnArgsM {
 #define ATT_STAMP(i) do { } while (0)
 #endif
 
-__device__ __forceinline__ void keep4(const AttnArgsM& a, uint64_t rowbase, int key, float& k0, float& k1, float& k2,
-                                      float& k3) {
-  drop_mask4(a.seed, a.site, (rowbase + (uint64_t)key) >> 2, a.thr, a.dscale, k0, k1, k2, k3);
-}
-__device__ __forceinline__ float keep1(const AttnArgsM& a, uint64_t rowbase, int key) {
-  float k[4];
-  drop_mask4(a.seed, a.site, (rowbase + (uint64_t)key) >> 2, a.thr, a.dscale, k[0], k[1], k[2], k[3]);
-  const int c = (int)((rowbase + (uint64_t)key) & 3);
-  return c == 0 ? k[0] : (c == 1 ? k[1] : (c == 2 ? k[2] : k[3]));
-}
-
 // FUSED (DH = 128, FP = 128, S <= 192): dS and P~ of the (window, head) stay in LDS ([S rounded up to 32][128 keys] each,
 // 80 KB at S = 155) and the block computes dK / dV of its feature keys itself after its row blocks are done (phase 2: the
 // key-side TN product of attn_bwd_keys on the block's own tiles, Q and dO staged over the K / V space) - no scratch round
 // trip through HBM (41 MB written and read back per layer at C2a), no second launch.  (Measured alternative: the three waves
 // without a row block prefetching Q / dO into registers during phase 1 - slower, 81 vs 74 us: their loads compete with the
 // K / V staging and the row blocks' own operand loads at the start of the block.)
-// keep factors of one lane pair's 16 keys kb .. kb+15 (kb a multiple of 16, rowbase of 8): lane g owns keys kb + 8t + 4g .. +3
-// for t = 0, 1.  Counter t covers keys kb + 8t .. +7: lane g draws counter t = g and passes its partner (lane ^ 32) the half
-// that lane owns - one Philox call and two exchanges per lane instead of two calls (common.h: 16-bit draws)
-__device__ __forceinline__ void keep_pair(const AttnArgsM& a, uint64_t rowbase, int kb, int g, float (&k0)[4], float (&k1)[4]) {
-  const Philox4 r = philox4x32_7(a.seed, a.site, ((rowbase + (uint64_t)kb) >> 3) + (uint64_t)g);
-  // v_permlane32_swap (x, z) and (y, w): lane g = 0 ends with (own x, partner's x), lane g = 1 with (partner's z, own z) - the
-  // words of counter 0 first and of counter 1 second in both lanes, no select
-  const auto xz = __builtin_amdgcn_permlane32_swap(r.x, r.z, false, false);
-  const auto yw = __builtin_amdgcn_permlane32_swap(r.y, r.w, false, false);
-  drop_mask4_words(xz[0], yw[0], a.thr, a.dscale, k0[0], k0[1], k0[2], k0[3]);
-  drop_mask4_words(xz[1], yw[1], a.thr, a.dscale, k1[0], k1[1], k1[2], k1[3]);
-}
-
 // KS (round 5, fused form only): phase 1 as a pipeline over the 32-row blocks on all EIGHT waves (the one-wave-per-row-block
 // form left three waves idle at S = 155 and read every operand row with one lane per row: 32 cache lines per load instruction).
 //   top      every request in arrival order: K / V tiles, the Q / dO rows of all sweeps by coalesced loads (16 lanes per row; kept
@@ -81,7 +50,7 @@ template <typename HT, int DH, int NJB, bool FUSED = false, bool KS = false, boo
 __global__ __launch_bounds__(512) void attn_bwd_rows(const HT* __restrict__ qkv, const HT* __restrict__ o,
                                                      const float* __restrict__ lse, const HT* __restrict__ d_o,
                                                      HT* __restrict__ dqkv, HT* __restrict__ dS_scr,
-                                                     HT* __restrict__ Pt_scr, AttnArgsM a) {
+                                                     HT* __restrict__ Pt_scr, AttnArgs a) {
   constexpr int FP = NJB * 32, NKK = DH / 16, NDB = DH / 32;
   static_assert(!FUSED || (DH == 128 && FP == 128), "the fused form is written for 128 x 128 tiles");
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -738,27 +707,6 @@ __global__ __launch_bounds__(256) void attn_bwd_keys(const HT* __restrict__ dS_s
   }
 }
 
-AttnArgsM make_args2(const TimDesc& d) {
-  AttnArgsM a;
-  a.S = d.S; a.F = d.F; a.E = d.E; a.H = d.H; a.LP = round_up(d.F + 1, 8);
-  a.scale = 1.f / sqrtf((float)(d.E / d.H));
-  a.thr = d.p_drop > 0.f ? drop_threshold(d.p_drop) : 0u;
-  a.dscale = d.p_drop > 0.f ? 1.f / (1.f - d.p_drop) : 1.f;
-  a.seed = d.seed; a.site = layer_site(d.layer, SITE_L_ATTN);
-  a.abl = (d.reserved >> 8) & 0xff;
-  a.rsplit = 1; a.rper = (d.S + 31) / 32;
-  a.kbits = nullptr;
-  return a;
-}
-
-static inline int rows_waves(int S) {
-  int n = (S + 31) / 32;
-  n = n < 1 ? 1 : (n > 8 ? 8 : n);
-  const int w = tim_knobs().attn_waves;   // (A/B knob, as in attention_mfma.hip)
-  if (w >= 1 && w <= 8) n = w;
-  return n;
-}
-
 // fused form: DH = 128, 97..128 feature keys, K / V / dS / P~ within the 160 KB of LDS: S <= 192 for the one-wave-per-row-block
 // form; the key-split pipeline (KS) keeps 12 bytes of per-row scalars more and fits S <= 160
 static inline bool fused_fits(const TimDesc& d, bool ks) {
@@ -773,7 +721,7 @@ int launch_bwd_fused(const TimDesc& d, const void* qkv, const void* o, const flo
                      hipStream_t s, const unsigned long long* kbits) {
   const int SP = (d.S + 31) & ~31;
   const size_t lds = (size_t)2 * 128 * 128 * 2 + (size_t)2 * SP * 128 * 2 + (KS ? (size_t)SP * 12 : 0);
-  AttnArgsM a = make_args2(d);
+  AttnArgs a = make_attn_args(d);
   if constexpr (KS) {
     if (kbits && a.thr != 0u) {
       a.kbits = kbits;
@@ -799,16 +747,9 @@ int launch_bwd2(const TimDesc& d, const void* qkv, const void* o, const float* l
   (void)hipFuncSetAttribute((const void*)attn_bwd_rows<HT, DH, NJB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
   // long sequences with few (window, head) pairs (detection: B * H = 128, 16 row blocks): the row blocks of a pair over several
   // workgroups of four waves, two workgroups per CU (the kernel takes 256 VGPRs: eight wave slots per CU)
-  AttnArgsM a = make_args2(d);
-  {
-    const int nrb = (d.S + 31) / 32, bh = d.B * d.H;
-    int want = bh >= 512 ? 1 : (512 + bh - 1) / bh;
-    if (want > nrb / 4) want = nrb / 4;
-    if (want < 1) want = 1;
-    a.rper = (nrb + want - 1) / want;
-    a.rsplit = (nrb + a.rper - 1) / a.rper;
-  }
-  const int waves = a.rsplit > 1 ? rows_waves(32 * (a.rper < 4 ? a.rper : 4)) : rows_waves(d.S);
+  AttnArgs a = make_attn_args(d);
+  attn_row_split(d, 0, 4, a.rsplit, a.rper);
+  const int waves = attn_waves(a.rsplit > 1 ? 32 * (a.rper < 4 ? a.rper : 4) : d.S, 8, true);
   hipLaunchKernelGGL((attn_bwd_rows<HT, DH, NJB>), dim3(d.B * d.H * a.rsplit), dim3(64 * waves), lds1, s, (const HT*)qkv,
                      (const HT*)o, lse, (const HT*)d_o, (HT*)dqkv, dS, Pt, a);
   if (hipGetLastError() != hipSuccess) return TIMHIP_ELAUNCH;
@@ -837,15 +778,7 @@ int tim_attention_bwd2_mfma(const TimDesc& d, const void* qkv, const void* o, co
     DISPATCH_H16(d.precision, return (launch_bwd_fused<HT, false>(d, qkv, o, lse, d_o, dqkv, stamps, s, nullptr)));
   }
   if (!ws || ws_bytes < tim_attention_bwd2_ws(d)) return TIMHIP_EUNSUPPORTED;
-  const int DHv = d.E / d.H, NJBv = (d.F + 31) / 32;
-#define B2(DHc, NJBc) DISPATCH_H16(d.precision, return (launch_bwd2<HT, DHc, NJBc>(d, qkv, o, lse, d_o, dqkv, ws, s)))
-  if (DHv == 128) {
-    switch (NJBv) { case 1: B2(128, 1); case 2: B2(128, 2); case 3: B2(128, 3); case 4: B2(128, 4); case 5: B2(128, 5); default: break; }
-  } else if (DHv == 64) {
-    switch (NJBv) { case 1: B2(64, 1); case 2: B2(64, 2); case 4: B2(64, 4); default: break; }
-  } else if (DHv == 32) {
-    switch (NJBv) { case 1: B2(32, 1); case 2: B2(32, 2); default: break; }
-  }
-#undef B2
-  return TIMHIP_EUNSUPPORTED;
+  return attn_for_shape(d.E / d.H, (d.F + 31) / 32, [&](auto dh, auto njb) {
+    DISPATCH_H16(d.precision, return (launch_bwd2<HT, decltype(dh)::value, decltype(njb)::value>(d, qkv, o, lse, d_o, dqkv, ws, s)));
+  });
 }

@@ -12,27 +12,9 @@
 //   * key contractions use key(step (q,t), g) = 32 jb + 8q + 4g + t, which is exactly the accumulator register 4q + t of the
 //     S^T tile in the same lane: probabilities feed the second product straight from the accumulators.
 // One LDS tile [FP][DH] fp32 (16-byte chunks XOR-swizzled with the row) holds K, then V (then K again in the backward).
-#include "common.h"
+#include "attention.h"
 
 namespace {
-
-struct AttnArgsF {
-  int S, F, E, H, LP;
-  int s0;   // forward: first token row computed and stored; rows land compactly, S - s0 per window (0: all rows)
-  float scale;
-  uint32_t thr; float dscale; TimSeed seed; uint32_t site;
-};
-
-__device__ __forceinline__ void keep4f(const AttnArgsF& a, uint64_t rowbase, int key, float& k0, float& k1, float& k2,
-                                       float& k3) {
-  drop_mask4(a.seed, a.site, (rowbase + (uint64_t)key) >> 2, a.thr, a.dscale, k0, k1, k2, k3);
-}
-__device__ __forceinline__ float keep1f(const AttnArgsF& a, uint64_t rowbase, int key) {
-  float k[4];
-  drop_mask4(a.seed, a.site, (rowbase + (uint64_t)key) >> 2, a.thr, a.dscale, k[0], k[1], k[2], k[3]);
-  const int c = (int)((rowbase + (uint64_t)key) & 3);
-  return c == 0 ? k[0] : (c == 1 ? k[1] : (c == 2 ? k[2] : k[3]));
-}
 
 // byte offset of element (row, col) of the [rows][DH] fp32 tile
 template <int DH>
@@ -106,7 +88,7 @@ __device__ __forceinline__ void mix_tile(f32x16_t& out, const char* tile, int jb
 // ---------------------------------------------------------------------------------------------------------------------
 template <int DH, int NJB>
 __global__ __launch_bounds__(512) void attn_fwd_f32(const float* __restrict__ qkv, float* __restrict__ o,
-                                                    float* __restrict__ lse, AttnArgsF a) {
+                                                    float* __restrict__ lse, AttnArgs a) {
   constexpr int FP = NJB * 32, NDB = DH / 32;
   extern __shared__ __attribute__((aligned(16))) char tile[];
   const int b = blockIdx.x / a.H, h = blockIdx.x % a.H;
@@ -171,11 +153,11 @@ __global__ __launch_bounds__(512) void attn_fwd_f32(const float* __restrict__ qk
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         float k0 = 1.f, k1 = 1.f, k2 = 1.f, k3 = 1.f;
-        if (a.thr != 0u) keep4f(a, rowbase, jb * 32 + 8 * q + 4 * g, k0, k1, k2, k3);
+        if (a.thr != 0u) keep4(a, rowbase, jb * 32 + 8 * q + 4 * g, k0, k1, k2, k3);
         sc[jb][4 * q] *= inv * k0; sc[jb][4 * q + 1] *= inv * k1; sc[jb][4 * q + 2] *= inv * k2; sc[jb][4 * q + 3] *= inv * k3;
       }
     float pself = pself_un * inv;
-    if (isq && a.thr != 0u) pself *= keep1f(a, rowbase, F);
+    if (isq && a.thr != 0u) pself *= keep1(a, rowbase, F);
 
     __syncthreads();                             // K tile no longer needed
     stage_f32<DH>(tile, base + 2 * E, ld, FP, F, tid, blockDim.x);
@@ -209,7 +191,7 @@ template <int DH, int NJB>
 __global__ __launch_bounds__(512) void attn_bwd_rows_f32(const float* __restrict__ qkv, const float* __restrict__ o,
                                                          const float* __restrict__ lse, const float* __restrict__ d_o,
                                                          float* __restrict__ dqkv, float* __restrict__ dS_scr,
-                                                         float* __restrict__ Pt_scr, AttnArgsF a) {
+                                                         float* __restrict__ Pt_scr, AttnArgs a) {
   constexpr int FP = NJB * 32, NDB = DH / 32;
   extern __shared__ __attribute__((aligned(16))) char tile[];
   const int b = blockIdx.x / a.H, h = blockIdx.x % a.H;
@@ -266,7 +248,7 @@ __global__ __launch_bounds__(512) void attn_bwd_rows_f32(const float* __restrict
     }
     if (isq) {
       const float p = expf(ds_self * a.scale - l);
-      const float keep = a.thr != 0u ? keep1f(a, rowbase, F) : 1.f;
+      const float keep = a.thr != 0u ? keep1(a, rowbase, F) : 1.f;
       ds_self = p * (pt_self * keep - delta) * a.scale;
       pt_self = p * keep;
     } else {
@@ -277,7 +259,7 @@ __global__ __launch_bounds__(512) void attn_bwd_rows_f32(const float* __restrict
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         float k[4] = {1.f, 1.f, 1.f, 1.f};
-        if (a.thr != 0u) keep4f(a, rowbase, jb * 32 + 8 * q + 4 * g, k[0], k[1], k[2], k[3]);
+        if (a.thr != 0u) keep4(a, rowbase, jb * 32 + 8 * q + 4 * g, k[0], k[1], k[2], k[3]);
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
           const int r = 4 * q + t;
@@ -394,26 +376,13 @@ __global__ __launch_bounds__(256) void attn_bwd_keys_f32(const float* __restrict
   }
 }
 
-AttnArgsF make_args_f(const TimDesc& d) {
-  AttnArgsF a;
-  a.S = d.S; a.F = d.F; a.E = d.E; a.H = d.H; a.LP = round_up(d.F + 1, 8);
-  a.scale = 1.f / sqrtf((float)(d.E / d.H));
-  a.thr = d.p_drop > 0.f ? drop_threshold(d.p_drop) : 0u;
-  a.dscale = d.p_drop > 0.f ? 1.f / (1.f - d.p_drop) : 1.f;
-  a.seed = d.seed; a.site = layer_site(d.layer, SITE_L_ATTN);
-  a.s0 = 0;
-  return a;
-}
-
-static inline int waves_for(int S) { const int n = (S + 31) / 32; return n < 1 ? 1 : (n > 8 ? 8 : n); }
-
 template <int DH, int NJB>
 int launch_fwd(const TimDesc& d, const void* qkv, void* o, float* lse, hipStream_t s, int s0) {
   const size_t lds = (size_t)NJB * 32 * DH * 4;
-  AttnArgsF a = make_args_f(d);
+  AttnArgs a = make_attn_args(d);
   a.s0 = s0;
   (void)hipFuncSetAttribute((const void*)attn_fwd_f32<DH, NJB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((attn_fwd_f32<DH, NJB>), dim3(d.B * d.H), dim3(64 * waves_for(d.S - (s0 & ~31))), lds, s, (const float*)qkv,
+  hipLaunchKernelGGL((attn_fwd_f32<DH, NJB>), dim3(d.B * d.H), dim3(64 * attn_waves(d.S - (s0 & ~31), 8, false)), lds, s, (const float*)qkv,
                      (float*)o, lse, a);
   return hipGetLastError() == hipSuccess ? TIMHIP_OK : TIMHIP_ELAUNCH;
 }
@@ -426,8 +395,8 @@ int launch_bwd(const TimDesc& d, const void* qkv, const void* o, const float* ls
   float* Pt = dS + (size_t)d.B * d.H * d.S * FP;
   const size_t lds = (size_t)FP * DH * 4;
   (void)hipFuncSetAttribute((const void*)attn_bwd_rows_f32<DH, NJB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((attn_bwd_rows_f32<DH, NJB>), dim3(d.B * d.H), dim3(64 * waves_for(d.S)), lds, s, (const float*)qkv,
-                     (const float*)o, lse, (const float*)d_o, (float*)dqkv, dS, Pt, make_args_f(d));
+  hipLaunchKernelGGL((attn_bwd_rows_f32<DH, NJB>), dim3(d.B * d.H), dim3(64 * attn_waves(d.S, 8, false)), lds, s, (const float*)qkv,
+                     (const float*)o, lse, (const float*)d_o, (float*)dqkv, dS, Pt, make_attn_args(d));
   if (hipGetLastError() != hipSuccess) return TIMHIP_ELAUNCH;
   hipLaunchKernelGGL(attn_bwd_keys_f32, dim3((d.F + 127) / 128, 2, d.B * d.H), dim3(256), 0, s, dS, Pt, (const float*)qkv,
                      (const float*)d_o, (float*)dqkv, d.S, d.F, FP, d.E, d.H, DH);
@@ -440,28 +409,19 @@ size_t tim_attention_f32_bwd_ws(const TimDesc& d) {
   return (size_t)2 * d.B * d.H * d.S * round_up(d.F, 32) * sizeof(float);
 }
 
-#define F32_DISPATCH(CALL)                                                                                             \
-  const int DHv = d.E / d.H, NJBv = (d.F + 31) / 32;                                                                   \
-  if (!f32_storage(d.precision) || (d.E % 4) != 0 || d.B * d.H > 65535) return TIMHIP_EUNSUPPORTED;                    \
-  if (DHv == 128) {                                                                                                    \
-    switch (NJBv) { case 1: CALL(128, 1); case 2: CALL(128, 2); case 3: CALL(128, 3); case 4: CALL(128, 4); case 5: CALL(128, 5); default: break; } \
-  } else if (DHv == 64) {                                                                                              \
-    switch (NJBv) { case 1: CALL(64, 1); case 2: CALL(64, 2); case 4: CALL(64, 4); default: break; }                   \
-  } else if (DHv == 32) {                                                                                              \
-    switch (NJBv) { case 1: CALL(32, 1); case 2: CALL(32, 2); default: break; }                                        \
-  }                                                                                                                    \
-  return TIMHIP_EUNSUPPORTED;
-
+// TIMHIP_EUNSUPPORTED: the caller uses the fp32-arithmetic kernels of attention.hip
 int tim_attention_fwd_f32(const TimDesc& d, const void* qkv, void* o, float* lse, hipStream_t s, int s0) {
-#define FWD(DHc, NJBc) return launch_fwd<DHc, NJBc>(d, qkv, o, lse, s, s0)
-  F32_DISPATCH(FWD)
-#undef FWD
+  if (!f32_storage(d.precision) || (d.E % 4) != 0 || d.B * d.H > 65535) return TIMHIP_EUNSUPPORTED;
+  return attn_for_shape(d.E / d.H, (d.F + 31) / 32, [&](auto dh, auto njb) {
+    return launch_fwd<decltype(dh)::value, decltype(njb)::value>(d, qkv, o, lse, s, s0);
+  });
 }
 
 int tim_attention_bwd_f32(const TimDesc& d, const void* qkv, const void* o, const float* lse, const void* d_o, void* dqkv,
                           void* ws, size_t ws_bytes, hipStream_t s) {
   if (!ws || ws_bytes < tim_attention_f32_bwd_ws(d)) return TIMHIP_EUNSUPPORTED;
-#define BWD(DHc, NJBc) return launch_bwd<DHc, NJBc>(d, qkv, o, lse, d_o, dqkv, ws, s)
-  F32_DISPATCH(BWD)
-#undef BWD
+  if (!f32_storage(d.precision) || (d.E % 4) != 0 || d.B * d.H > 65535) return TIMHIP_EUNSUPPORTED;
+  return attn_for_shape(d.E / d.H, (d.F + 31) / 32, [&](auto dh, auto njb) {
+    return launch_bwd<decltype(dh)::value, decltype(njb)::value>(d, qkv, o, lse, d_o, dqkv, ws, s);
+  });
 }
