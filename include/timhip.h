@@ -750,6 +750,41 @@ int timhip_det_candidates_emit(const float* logits, int64_t ld_logits, const flo
                                float score_threshold, int64_t capacity, float* seg, float* score, int64_t* key,
                                int32_t* row, void* stream);
 
+/* ---------------------------------------------------------------- two-stream detection fusion */
+/* The fusion of a verb stream and a noun stream over the same proposals into (verb, noun) action candidates, per batch, as
+ * the reference computes it on the host in detection/eval_detection/format_two_stream_predictions_epic.py (main).  Scores
+ * and decoded proposals are those of the detection candidates above, per stream, the proposals unrounded:
+ * prop = (double)(clamp(reg, 0, *max_time) * window_size) + window_start[w].  Of each row the top_k classes of either stream
+ * are selected on the fp32 score (equal scores: the lower class first; a NaN ranks above every number).  Pair (i, j) of the
+ * i-th verb (score vs) and the j-th noun (score ns), both by descending score, is a candidate iff vs > thr, ns > thr,
+ * score = (float)pow(vs, alpha32) * (float)pow(ns, beta32) > thr (fp32 compares, the powers in fp64 rounded once) and the
+ * segment w * prop_verb + (1 - w) * prop_noun, w = vs / (vs + ns) in fp32, products and sum in fp64, rounded to three
+ * decimals as numpy.round does, has a width > 0.  The caller passes alpha32 = (float)alpha and beta32 = (float)(1.0 - alpha).
+ * Candidates are listed proposal by proposal, pair i * top_k + j ascending inside a proposal; that order is part of the
+ * result.
+ *
+ * timhip_ts_candidates_count: verb_logits [R, Cv] / noun_logits [R, Cn] fp32 with row strides ld_v / ld_n (elements, >= C:
+ *   a head's slice needs no copy), verb_reg / noun_reg [R, 2] fp32, window_start [R / Nq] fp64, max_time: DEVICE pointer to
+ *   one float.  Writes the per-row records - sel_idx [R, 2, top_k] and sel_score [R, 2, top_k] (verbs, then nouns),
+ *   pair_score [R, top_k^2], pair_seg [R, top_k^2, 2] (fp32), pair_mask [R] (bit p: pair p is a candidate) - and
+ *   row_offsets [R + 1]: row r's candidates occupy output slots [row_offsets[r], row_offsets[r + 1]), row_offsets[R] is
+ *   their total.  Two launches (select, scan).  R == 0 is a valid empty call that still writes row_offsets[0] = 0.
+ * timhip_ts_candidates_emit: reads the records only; writes candidate j of row r at row_offsets[r] + j: seg [N, 2],
+ *   score [N], key [N] = video_index[w] * (Cv * Cn) + verb * Cn + noun, row [N] = r.  `capacity` = the number of candidates
+ *   the four output buffers hold; a slot at or beyond it (or beyond its row's range) is not written, so a worst-case-sized
+ *   output (R * top_k^2) makes the pair replayable in a HIP graph.  One launch.
+ * Neither call allocates, synchronises or reads device memory on the host.  TIMHIP_EINVAL: a null pointer with R > 0,
+ * top_k < 1, top_k > min(Cv, Cn), R not a multiple of Nq, ld < C.  TIMHIP_EUNSUPPORTED: top_k > 8 (one lane per pair),
+ * Cv + Cn > 4096 (a block's scores live in 64 KiB of LDS), R * top_k^2 beyond int32. */
+int timhip_ts_candidates_count(const float* verb_logits, int64_t ld_v, const float* noun_logits, int64_t ld_n,
+                               const float* verb_reg, const float* noun_reg, const double* window_start, float window_size,
+                               const float* max_time, int R, int Cv, int Cn, int Nq, int top_k, float score_threshold,
+                               float alpha32, float beta32, int32_t* sel_idx, float* sel_score, float* pair_score,
+                               float* pair_seg, uint64_t* pair_mask, int32_t* row_offsets, void* stream);
+int timhip_ts_candidates_emit(const int32_t* sel_idx, const float* pair_score, const float* pair_seg, const uint64_t* pair_mask,
+                              const int32_t* row_offsets, const int32_t* video_index, int R, int Cv, int Cn, int Nq, int top_k,
+                              int64_t capacity, float* seg, float* score, int64_t* key, int32_t* row, void* stream);
+
 /* ---------------------------------------------------------------- recognition scores and accuracies */
 /* The inference tail behind the recognition heads, as the reference computes it on the host in
  * recognition/time_interval_machine/utils/meters.py (InferenceMeter / FeatureMeter: index_add_ of the valid query rows into

@@ -22,6 +22,9 @@ def __getattr__(name):  # lazy: importing the package must not require torch on 
     if name == "DetectionCollector":
         from .detect import DetectionCollector
         return DetectionCollector
+    if name == "TwoStreamCollector":
+        from .twostream import TwoStreamCollector
+        return TwoStreamCollector
     if name == "DetectionScorer":
         from .detmap import DetectionScorer
         return DetectionScorer

@@ -164,6 +164,9 @@ _SIGS = {
     "timhip_nms_1d": (C.c_int, [vp, vp, vp, i32, f32, vp, vp, vp, vp]),
     "timhip_det_candidates_count": (C.c_int, [vp, C.c_int64, vp, vp, f32, vp, i32, i32, i32, f32, vp, vp, vp, vp]),
     "timhip_det_candidates_emit": (C.c_int, [vp, C.c_int64, vp, vp, vp, vp, i32, i32, i32, f32, C.c_int64, vp, vp, vp, vp, vp]),
+    "timhip_ts_candidates_count": (C.c_int, [vp, C.c_int64, vp, C.c_int64, vp, vp, vp, f32, vp, i32, i32, i32, i32, i32, f32, f32, f32,
+                                             vp, vp, vp, vp, vp, vp, vp]),
+    "timhip_ts_candidates_emit": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, C.c_int64, vp, vp, vp, vp, vp]),
     "timhip_det_match": (C.c_int, [vp, C.c_int64, vp, vp, vp, vp, vp, C.c_int64, vp, i32, vp, i32, vp, vp, vp, vp]),
     "timhip_det_ap": (C.c_int, [vp, C.c_int64, vp, vp, i32, i32, vp, vp]),
     "timhip_rec_accumulate": (C.c_int, [vp, i32, vp, vp, vp, C.c_int64, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),

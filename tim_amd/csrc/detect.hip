@@ -8,7 +8,7 @@
 // reference's order - proposal by proposal, ascending class inside a proposal - by count + scan + emit:
 //   det_count_kernel   one wavefront per proposal row: decode + round the segment (fp32 / fp64 split below), count the
 //                      classes over the threshold -> row_offsets[r + 1]
-//   det_scan_kernel    one block: in-place inclusive scan -> row_offsets[r] = first output slot of row r, [R] = total
+//   det_scan_kernel    (row_scan.h) one block: in-place inclusive scan -> row_offsets[r] = first output slot of row r, [R] = total
 //   det_emit_kernel    the same walk; candidate k of row r lands at row_offsets[r] + k (__ballot + popcount of the lower
 //                      lanes inside a 64-class chunk, a running base across chunks)
 // No atomics and no look-back between workgroups: nothing depends on dispatch order.
@@ -40,6 +40,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "row_scan.h"
 
 #pragma clang fp contract(off)
 
@@ -101,35 +102,6 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void det_count_kernel(
       seg_ok[r] = ok ? 1 : 0;
       row_offsets[r + 1] = n;
     }
-  }
-}
-
-// row_offsets[1 .. R] hold the counts: inclusive scan in place, row_offsets[0] = 0.  One block, 1024 elements per round with
-// a carry; the order of the additions is fixed (integers anyway).
-__global__ __launch_bounds__(1024) void det_scan_kernel(int* __restrict__ row_offsets, int R) {
-  __shared__ int wsum[16];
-  __shared__ int carry_s;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  if (tid == 0) { row_offsets[0] = 0; carry_s = 0; }
-  __syncthreads();
-  for (int base = 0; base < R; base += 1024) {
-    const int i = base + tid;
-    int v = i < R ? row_offsets[i + 1] : 0;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int u = __shfl_up(v, o, 64);
-      if (lane >= o) v += u;
-    }
-    if (lane == 63) wsum[w] = v;
-    __syncthreads();
-    int before = carry_s;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) if (k < w) before += wsum[k];
-    v += before;
-    if (i < R) row_offsets[i + 1] = v;
-    __syncthreads();                       // every thread has read carry_s and wsum
-    if (tid == 1023) carry_s = v;
-    __syncthreads();
   }
 }
 

@@ -41,6 +41,7 @@ BUDGET = {
     "rowops.hip": [(r"ln_fwd8", 0), (r"ln_bwd_kernel", 0)],
     "optim.hip": [(r"optim_norm_kernel", 0), (r"optim_update_kernel", 0)],   # streaming kernels: scratch traffic would share their HBM budget
     "detect.hip": [(r"det_count_kernel", 0), (r"det_scan_kernel", 0), (r"det_emit_kernel", 0)],   # streaming: one read of the logits each
+    "twostream.hip": [(r"ts_select_kernel", 0), (r"det_scan_kernel", 0), (r"ts_emit_kernel", 0)],   # streaming: both rows of logits once
     "detmap.hip": [(r"det_match_kernel", 0), (r"det_ap_kernel", 0)],   # a wave's segments and lock words live in registers
     "recog.hip": [(r"rec_eid_kernel", 0), (r"rec_link_kernel", 0), (r"rec_accumulate_kernel", 0), (r"rec_finalize_kernel", 0),
                   (r"rec_counts_kernel", 0)],   # streaming: the logits once, the accumulator chunk once in and once out
