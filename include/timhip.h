@@ -877,6 +877,73 @@ int timhip_window_times(const float* v_feat_times, int v_ld, const int64_t* v_ro
                         const float* v_queries, int max_v, const float* a_queries, int max_a, const float* start_sec,
                         float window_size, float* times, void* stream);
 
+/* ---------------------------------------------------------------- AVGA pooling of the AVE recipe (additive to ABI 6) */
+/* Audio-guided visual attention pooling (reference helpers/pool.py:6-43, models/tim.py:137-144): per pooled row r (one time step
+ * of one window) with cells X[r] : [S, Cv] and audio a[r] : [Ca]
+ *   hv = relu(X W_video^T + b_video) [S, H]      ha = relu(W_audio a + b_audio) [H]      g = W_g ha [S]  (indexed by the CELL)
+ *   c[s, j] = (W_v hv[s])[j] + g[s]              z[s] = sum_j w_h[j] tanh(c[s, j])        alpha = softmax_s(z)
+ *   out[r] = sum_s alpha[s] X[r, s]              [Cv]
+ * TimAvga describes one call: video = fp32 cells, row r at video + r * pitch floats ([S, Cv] contiguous inside a row; pitch >=
+ * S * Cv, a multiple of 4: a [B, T, 7, 7, Cv] tensor is read in place); audio [R, ld_audio >= Ca] fp32 with ANY row stride and
+ * the 4-byte alignment of a float (the kernels make their own zero-padded operand copy of it); the weights as operand-dtype
+ * copies [N, ld] (K-contiguous, ld a multiple of 64, zero padded: what timhip_cast_weights writes) - w_video [H, >= Cv],
+ * w_audio [H, >= Ca], w_v [S, >= H], w_g [S, >= H]; the backward also takes the TRANSPOSED copies w_v_t, w_g_t [H, >= 64] and, in
+ * the 16-bit precisions, the SPLIT copies w_video_s [H, ld = 3 ru(Cv)], w_audio_s [H, ld = 3 ru(Ca)] as timhip_split3_many writes them in
+ * mode 1 ([hi | hi | lo]; the leading dimension is exactly three blocks, anything else is TIMHIP_EALIGN) (all NULL in a forward); fp32 b_video [H], b_audio [H], w_h [S].
+ * Supported: 1 <= S <= 64 with S == map_size, H == Cv, Cv a multiple of 64 in [64, 1024], Ca >= 1, R >= 1 with R * S * Cv < 2^31,
+ * TIMHIP_PREC_BF16 / _F16 / _FP32 - everything else TIMHIP_EUNSUPPORTED (TIMHIP_PREC_BF16X3 included); NULL pointers, a pitch
+ * below S * Cv or a leading dimension below its width TIMHIP_EINVAL; pitches / leading dimensions / pointers off their
+ * alignment (16 bytes, audio 4; weight ld % 64) TIMHIP_EALIGN; a workspace below timhip_avga_workspace_bytes TIMHIP_EWORKSPACE. */
+typedef struct TimAvga {
+  const float* video;
+  const float* audio;
+  const void* w_video;
+  const void* w_audio;
+  const void* w_v;
+  const void* w_g;
+  const void* w_v_t;
+  const void* w_g_t;
+  const void* w_video_s;
+  const void* w_audio_s;
+  const float* b_video;
+  const float* b_audio;
+  const float* w_h;
+  int64_t pitch;
+  int32_t R, S, Cv, Ca, H, map_size;
+  int32_t ld_audio, ld_w_video, ld_w_audio, ld_w_v, ld_w_g, ld_w_v_t, ld_w_g_t, ld_w_video_s, ld_w_audio_s, reserved;
+} TimAvga;
+/* the seven parameter gradients, fp32, contiguous, shaped like the parameters */
+typedef struct TimAvgaGrads {
+  float* w_video;   /* [H, Cv] */
+  float* b_video;   /* [H] */
+  float* w_audio;   /* [H, Ca] */
+  float* b_audio;   /* [H] */
+  float* w_v;       /* [S, H] */
+  float* w_g;       /* [S, H] */
+  float* w_h;       /* [S] */
+} TimAvgaGrads;
+/* bytes of workspace for one call (backward != 0: timhip_avga_bwd); 0 for a shape or precision outside the supported set */
+size_t timhip_avga_workspace_bytes(int precision, int R, int S, int Cv, int Ca, int backward);
+/* out [R, ldo >= Cv] fp32 (ldo % 4 == 0) and, when alpha != NULL, alpha [R, ld_alpha >= S] fp32.  One fused kernel over the
+ * pooled rows behind two [R]-row products (ha, g: timhip_gemm_nt into the workspace): hv and c never reach memory, nothing with
+ * R * S rows is written.  16-bit precisions round X, W_video, hv, W_v, a, W_audio, ha, W_g to the operand dtype where the
+ * matrix cores read them; the weighted sum over the cells reads the fp32 cells.  Deterministic (no atomics). */
+int timhip_avga_fwd(int precision, const TimAvga* p, float* out, int ldo, float* alpha, int ld_alpha, void* workspace,
+                    size_t workspace_bytes, void* stream);
+/* PARAMETER gradients of timhip_avga_fwd for the cotangent d_out [R, ldd >= Cv] fp32: all seven tensors of `grads` are WRITTEN
+ * (not accumulated) at true scale; no input gradient.  Nothing of the forward is needed: hv, c and alpha are recomputed per row.
+ * Two [R * S, Cv] operand-dtype intermediates live in the workspace (d_pre and the cast cells; timhip_wgrad's kernels turn them
+ * into dW_video / db_video).  16-bit precisions: the relu MASKS of the backward (hv > 0, ha > 0) are taken from split products
+ * (x_hi w_hi + x_lo w_hi + x_hi w_lo, about twice the operand's mantissa) - with 16-bit operands alone, pre-activations that
+ * rounding moves across zero flip mask bits, each a full-size term of dW_video / dW_audio; hv and ha themselves stay the
+ * forward's.  grad_scale: NULL, or (TIMHIP_PREC_F16 only) the 8-word block of timhip_grad_scale - the 16-bit
+ * gradient operands are stored times S, the outputs multiplied by 1/S, and word 4 is ORed when a gradient written is inf / nan.
+ * ORDER OF ADDITIONS: dW_v and dw_h are summed over the pooled rows with float atomics (one add per element per row), so their
+ * last bits vary from call to call, as timhip_colsum's do; the other five gradients are reduced in a fixed order in the 16-bit
+ * precisions (TIMHIP_PREC_FP32: db_video and db_audio end in the transposing kernel's atomics as well). */
+int timhip_avga_bwd(int precision, const TimAvga* p, const float* d_out, int ldd, const TimAvgaGrads* grads,
+                    const float* grad_scale, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------- measurement hook (bench.py roofline) */
 /* While armed, every NT / TN GEMM launch of at least min_flops algorithmic FLOPs (2*M*N*K) is bracketed by two HIP events
  * recorded on the stream it is launched on (up to `capacity` launches).  stop() waits for them and returns the summed

@@ -55,7 +55,7 @@ DESC_ATTN_FP32, DESC_ATTN_BWD_ONE_KERNEL, DESC_WGRAD_OVERWRITE, DESC_WGRAD_SEPAR
 DESC_INPROJ_SPLIT, DESC_L1_SPLIT, DESC_L2_SPLIT = 32, 64, 128   # TimDesc.reserved flags
 # (DESC_ATTN_BWD_ONE_KERNEL: accepted and ignored: the single-kernel backward was removed; the fused and two-kernel forms give the same result)
 DESC_STREAM16, DESC_STREAM16_IN, DESC_STREAM16_OUT = 0x10000, 0x20000, 0x40000   # 16-bit residual gradient stream (fp16 backward)
-EUNSUPPORTED = -2                # include/timhip.h: TIMHIP_EUNSUPPORTED
+EINVAL, EUNSUPPORTED, EWORKSPACE, ELAUNCH, EALIGN = -1, -2, -3, -4, -5   # include/timhip.h: TIMHIP_E*
 DESC_ATTN_KEEP_BITS = 0x80000   # the saved block carries the layer's attention keep-bits (timhip_attn_keep_bits)
 
 
@@ -94,6 +94,19 @@ class TimRecHead(C.Structure):
 
 
 REC_MAX_HEADS = 3   # include/timhip.h: TIMHIP_REC_MAX_HEADS
+
+
+class TimAvga(C.Structure):
+    """one AVGA pooling call (include/timhip.h): inputs, operand copies of the weights, shape"""
+    _fields_ = [(n, vp) for n in ("video", "audio", "w_video", "w_audio", "w_v", "w_g", "w_v_t", "w_g_t", "w_video_s", "w_audio_s", "b_video",
+                                  "b_audio", "w_h")] + [("pitch", C.c_int64)] + \
+               [(n, i32) for n in ("R", "S", "Cv", "Ca", "H", "map_size", "ld_audio", "ld_w_video", "ld_w_audio", "ld_w_v", "ld_w_g",
+                                   "ld_w_v_t", "ld_w_g_t", "ld_w_video_s", "ld_w_audio_s", "reserved")]
+
+
+class TimAvgaGrads(C.Structure):
+    _fields_ = [(n, vp) for n in ("w_video", "b_video", "w_audio", "b_audio", "w_v", "w_g", "w_h")]
+
 
 _SIGS = {
     "timhip_version": (C.c_int, []),
@@ -205,6 +218,9 @@ _SIGS = {
     "timhip_optim_finish": (C.c_int, [vp, i32, vp, i32, f32, vp, vp, vp, i32, vp]),
     "timhip_optim_update": (C.c_int, [i32, vp, i32, vp, C.c_double, C.c_double, C.c_double, C.c_double, vp]),
     "timhip_smooth_one_hot": (C.c_int, [vp, i32, i32, C.c_int64, i32, f32, f32, vp, vp]),
+    "timhip_avga_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i32]),
+    "timhip_avga_fwd": (C.c_int, [i32, C.POINTER(TimAvga), vp, i32, vp, i32, vp, sz, vp]),
+    "timhip_avga_bwd": (C.c_int, [i32, C.POINTER(TimAvga), vp, i32, C.POINTER(TimAvgaGrads), vp, vp, sz, vp]),
 }
 
 _lib = None

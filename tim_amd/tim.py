@@ -10,6 +10,7 @@ their own `forward` is never called on that path.
 """
 import copy
 import math
+import weakref
 
 import torch
 from torch import nn
@@ -149,8 +150,11 @@ class _EncoderStackParams(nn.Module):
 class _AVGAParams(nn.Module):
     """Audio-guided visual attention pooling of the AVE recipe (pool.py:6-43; `pool_features=True`): collapses a [B, T, 7, 7,
     Cv] visual feature map to [B, T, Cv] before the hot path starts.  An input pre-step outside the encoder path (SURVEY 2,
-    row 9): parameter names / shapes / initialisation as the reference's so that checkpoints round-trip; evaluated with stock
-    torch ops (autograd included)."""
+    row 9): parameter names / shapes / initialisation as the reference's so that checkpoints round-trip.  On the GPU, for the
+    shapes `timhip_avga_fwd` covers and inputs that need no gradient, it runs as one fused kernel with a recomputing
+    parameter backward (tim_amd/avga.py; `TIM_AMD_AVGA=0`, read per call, turns that off); everything
+    else - CPU tensors, other shapes, inputs that require gradients, a module outside a `TIM` - runs the stock torch ops
+    below (autograd included)."""
 
     def __init__(self, a_dim, v_dim, hidden_size, map_size=49):
         super().__init__()
@@ -164,7 +168,29 @@ class _AVGAParams(nn.Module):
         nn.init.constant_(self.affine_audio.bias, 0)
         nn.init.constant_(self.affine_video.bias, 0)
 
+    # the model whose Runtime (operand copies) and workspaces the device route uses: a weak reference outside the module
+    # tree and outside pickles / deep copies (TIM binds it at construction and at every encoder forward)
+    def bind(self, model):
+        self.__dict__["_owner_ref"] = weakref.ref(model)
+
+    def owner(self):
+        ref = self.__dict__.get("_owner_ref")
+        return None if ref is None else ref()
+
+    def __getstate__(self):
+        st = self.__dict__.copy()
+        st.pop("_owner_ref", None)
+        return st
+
+    def attention_map(self, audio, video):
+        """alpha [B, T, S]: the weight of every spatial cell, from the device route (GPU tensors of a supported shape)"""
+        from . import avga
+        return avga.attention_map(self, audio, video)
+
     def forward(self, audio, video):
+        from . import avga
+        if avga.route(self, audio, video) == "device":
+            return avga.pool_forward(self, audio, video)
         B, T, C = video.shape[0], video.shape[1], video.shape[-1]
         cells = video.reshape(B * T, -1, C)                                   # [B*T, 49, Cv] spatial cells of one time step
         hv = torch.relu(self.affine_video(cells))
@@ -355,7 +381,8 @@ class TIM(nn.Module):
             self.transformer_encoder = stack
         self._stack_prefix = "backbone" if _variant == "detection" else "transformer_encoder"
         self.drloc_mlp = nn.Sequential(nn.Linear(4 * d, d), nn.ReLU(), nn.Linear(d, d), nn.ReLU(), nn.Linear(d, 1))
-        # AVGA pooling of the AVE recipe: an input pre-step in stock torch, outside the hot path (tim.py:137-144,155-156)
+        # AVGA pooling of the AVE recipe: an input pre-step in front of the encoder path (tim.py:137-144,155-156); its fused
+        # kernels take the operand copies and workspaces of this model (tim_amd/avga.py)
         self.pool = _AVGAParams(audio_input_dim, visual_input_dim, visual_input_dim) if pool_features else None
 
         self.rt = Runtime(precision)
@@ -367,6 +394,8 @@ class TIM(nn.Module):
         self._ws_pinned = False   # set by GraphedStep: workspaces captured in a graph are never freed
         self._ws_retired = []
         self._check_kernel_limits()
+        if self.pool is not None:
+            self.pool.bind(self)
         self._encoder_param_names = [n for n, _ in self.named_parameters()
                                      if not (n.startswith("time_mlp.") or n.startswith("drloc_mlp.") or n.startswith("pool."))]
 
@@ -478,6 +507,7 @@ class TIM(nn.Module):
     # ---- the reference's public interface ------------------------------------------------------------
     def forward_encoder(self, inputs, time_encodings, num_v_queries, num_a_queries):
         if self.pool is not None:
+            self.pool.bind(self)      # (a deep copy or an unpickled model arrives here unbound)
             inputs = [self.pool(inputs[1], inputs[0]), inputs[1]]
         outs = encoder(self, int(num_v_queries or 0), int(num_a_queries or 0), inputs[0], inputs[1], time_encodings)
         o = dict(zip(OUT_SLOTS, outs))
