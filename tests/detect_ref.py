@@ -15,13 +15,18 @@ def sigmoid32(x):
         return (1.0 / (1.0 + np.exp(-x))).astype(np.float32)
 
 
-def decode(reg, window_start, window_size, max_time, num_queries):
-    """-> (seg64 [R, 2] float64 rounded to three decimals, ok [R] bool)"""
+def proposals(reg, window_start, window_size, max_time, num_queries):
+    """-> [R, 2] float64: the decoded proposals, NOT rounded (what the reference saves as v_proposals)"""
     reg = np.asarray(reg, dtype=np.float32)
-    p = np.minimum(np.maximum(reg, np.float32(0.0)), np.float32(max_time))              # fp32 clamp
+    p = np.minimum(np.maximum(reg, np.float32(0.0)), np.float32(max_time))              # fp32 clamp (NaN propagates)
     p = (p * np.float32(window_size)).astype(np.float32)                                # fp32 product, rounded once
     start = np.repeat(np.asarray(window_start, dtype=np.float64), num_queries)
-    p = p.astype(np.float64) + start[:, None]                                           # the sum is float64
+    return p.astype(np.float64) + start[:, None]                                        # the sum is float64
+
+
+def decode(reg, window_start, window_size, max_time, num_queries):
+    """-> (seg64 [R, 2] float64 rounded to three decimals, ok [R] bool)"""
+    p = proposals(reg, window_start, window_size, max_time, num_queries)
     p = np.rint(p * 1000.0) / 1000.0                                                    # numpy.round(p, 3)
     return p, (p[:, 1] - p[:, 0]) > 0.0
 
@@ -42,14 +47,13 @@ def batch_candidates(logits, reg, window_start, window_size, max_time, video_ind
                 row=rows.astype(np.int32), cls=cls.astype(np.int64), video=video, seg32=seg64.astype(np.float32), ok=ok)
 
 
-class Collector:
-    """numpy mirror of tim_amd.DetectionCollector"""
+class CollectorBase:
+    """what the numpy mirrors of the two collectors share: the video index and the per-video NMS loop"""
 
-    def __init__(self, num_classes, score_threshold=0.01):
-        self.C, self.thr = int(num_classes), score_threshold
+    def __init__(self):
         self.video_ids, self._index, self.chunks = [], {}, []
 
-    def update(self, logits, reg, query_times, video_ids, window_start, window_size):
+    def _video_index(self, video_ids):
         idx = []
         for v in video_ids:
             v = str(v)
@@ -57,6 +61,31 @@ class Collector:
                 self._index[v] = len(self.video_ids)
                 self.video_ids.append(v)
             idx.append(self._index[v])
+        return idx
+
+    def _nms_per_video(self, c, labels, iou_threshold, min_score, sigma, method, nms):
+        """candidates `c` with `labels` -> (segs, scores, labels, video) ordered by video, then descending score (stable)"""
+        out = [[], [], [], []]
+        for v in range(len(self.video_ids)):
+            m = c["video"] == v
+            if not m.any():
+                continue
+            s, sc, lb = nms_oracle.batched_nms(c["seg"][m], c["score"][m], labels[m], iou_threshold, min_score, sigma, method, nms)
+            out[0].append(s); out[1].append(sc); out[2].append(lb); out[3].append(np.full(len(sc), v, np.int64))
+        if not out[1]:
+            return np.zeros((0, 2), np.float32), np.zeros(0, np.float32), np.zeros(0, np.int64), np.zeros(0, np.int64)
+        return tuple(np.concatenate(o) for o in out)
+
+
+class Collector(CollectorBase):
+    """numpy mirror of tim_amd.DetectionCollector"""
+
+    def __init__(self, num_classes, score_threshold=0.01):
+        super().__init__()
+        self.C, self.thr = int(num_classes), score_threshold
+
+    def update(self, logits, reg, query_times, video_ids, window_start, window_size):
+        idx = self._video_index(video_ids)
         max_time = np.asarray(query_times, dtype=np.float32).max()
         self.chunks.append(batch_candidates(logits, reg, window_start, window_size, max_time, idx, self.thr))
 
@@ -69,17 +98,7 @@ class Collector:
     def detections(self, sigma=0.1, iou_threshold=0.1, min_score=0.001, method=2, nms="soft"):
         """-> (segs, scores, labels, video) ordered by video, then descending score (stable)"""
         c = self.candidates()
-        out = [[], [], [], []]
-        for v in range(len(self.video_ids)):
-            m = c["video"] == v
-            if not m.any():
-                continue
-            s, sc, lb = nms_oracle.batched_nms(c["seg"][m], c["score"][m], c["cls"][m], iou_threshold, min_score, sigma,
-                                               method, nms)
-            out[0].append(s); out[1].append(sc); out[2].append(lb); out[3].append(np.full(len(sc), v, np.int64))
-        if not out[1]:
-            return np.zeros((0, 2), np.float32), np.zeros(0, np.float32), np.zeros(0, np.int64), np.zeros(0, np.int64)
-        return tuple(np.concatenate(o) for o in out)
+        return self._nms_per_video(c, c["cls"], iou_threshold, min_score, sigma, method, nms)
 
     def results(self, **nms_args):
         s, sc, lb, vd = self.detections(**nms_args)

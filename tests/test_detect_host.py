@@ -2,8 +2,6 @@
 without a GPU, and the two library entry points are declared in the header, bound, and exported under the unchanged ABI
 number."""
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -11,11 +9,8 @@ import torch
 
 import tim_amd
 from tests import helpers as H
+from tests.candidate_helpers import check_entry_points
 from tim_amd import _lib
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = {"timhip_det_candidates_count", "timhip_det_candidates_emit"}
-
 
 def test_collector_is_a_lazy_export():
     assert "DetectionCollector" not in vars(tim_amd)
@@ -46,17 +41,7 @@ def test_cpu_tensors_fail_loudly():
 
 
 def test_entry_points_are_declared_bound_and_exported():
-    hdr = open(os.path.join(ROOT, "include", "timhip.h")).read()
-    declared = {n for n in re.findall(r"\b(timhip_[a-z0-9_]+)\s*\(", hdr) if n.startswith("timhip_det_candidates")}
-    assert declared == NAMES
-    assert NAMES <= set(_lib.exported_symbols())
-    assert len(_lib._SIGS["timhip_det_candidates_count"][1]) == 14 and len(_lib._SIGS["timhip_det_candidates_emit"][1]) == 16
-    assert re.search(r"#define\s+TIMHIP_VERSION\s+6\b", hdr) and _lib.ABI_VERSION == 6
-    so = _lib.LIB_PATH
-    if os.path.exists(so):
-        syms = subprocess.run(["nm", "-D", "--defined-only", so], capture_output=True, text=True, check=True).stdout
-        for n in NAMES:
-            assert re.search(r"\bT %s\b" % n, syms), n
+    check_entry_points("timhip_det_candidates", {"timhip_det_candidates_count": 14, "timhip_det_candidates_emit": 16}, "detect.hip")
 
 
 def test_restatement_and_host_agree_on_the_class_key():

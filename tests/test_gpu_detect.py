@@ -16,15 +16,10 @@ pytestmark = pytest.mark.gpu
 
 from tests import detect_ref as D  # noqa: E402
 from tests import helpers as H  # noqa: E402
+from tests.candidate_helpers import DEV, dv, logit, ulp_apart  # noqa: E402
+from tests.candidate_helpers import meta as _meta  # noqa: E402
 from tim_amd import _lib as L  # noqa: E402
 from tim_amd import detect as hd  # noqa: E402
-
-DEV = "cuda"
-
-
-def _logit(t):
-    return np.log(t / (1.0 - t)) if 0.0 < t < 1.0 else -9.0
-
 
 def make_batch(seed, B, nq, ncls, thr, start0=0.0, invalid="some"):
     """one batch of synthetic head outputs; no score within 1 ulp of the threshold"""
@@ -40,10 +35,10 @@ def make_batch(seed, B, nq, ncls, thr, start0=0.0, invalid="some"):
         reg[2] = (0.33, 0.33)                                     # zero width
         reg[3] = (-0.4, 1.7)                                      # both clamps
         reg[4:7] = ((0.2, 0.6), (0.1, 0.5), (0.3, 0.9))           # the rows with crafted logits below are valid
-    logits = rng.normal(_logit(thr) - 2.4, 1.5, size=(R, ncls)).astype(np.float32)
+    logits = rng.normal(logit(thr, -9.0) - 2.4, 1.5, size=(R, ncls)).astype(np.float32)
     if R >= 8:
-        logits[4] = _logit(thr) + 2.0 + rng.uniform(0, 1, size=ncls)      # every class passes
-        logits[5] = (_logit(thr) - 3.0 - rng.uniform(0, 1, size=ncls)) if thr > 0 else -150.0      # none does
+        logits[4] = logit(thr, -9.0) + 2.0 + rng.uniform(0, 1, size=ncls)      # every class passes
+        logits[5] = (logit(thr, -9.0) - 3.0 - rng.uniform(0, 1, size=ncls)) if thr > 0 else -150.0      # none does
         logits[6, ::3] = (-110.0, -30.0, 40.0, 95.0)[seed % 4]            # far tails
     s = D.sigmoid32(logits)
     t32 = np.float32(thr)
@@ -56,7 +51,6 @@ def make_batch(seed, B, nq, ncls, thr, start0=0.0, invalid="some"):
 
 
 def run_kernels(b, nq, thr, window_size, logits_dev=None):
-    dv = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
     lg = dv(b["logits"]) if logits_dev is None else logits_dev
     mt = dv(b["queries"]).max()
     out = hd.candidates(lg, dv(b["reg"]), dv(b["starts"]), window_size, mt, dv(b["vidx"]), nq, thr)
@@ -64,17 +58,15 @@ def run_kernels(b, nq, thr, window_size, logits_dev=None):
     return [t.cpu().numpy() for t in out]
 
 
-def ulp_apart(a, b):
-    return np.abs(a.view(np.int32).astype(np.int64) - b.view(np.int32).astype(np.int64))
-
-
-def check_against_ref(got, b, thr, window_size):
+def check_against_ref(got, b, thr, window_size, first=None):
+    """`first`: `got` is the first that many candidates of the list (an emit into a smaller capacity)"""
     seg, score, key, row = got
     ref = D.batch_candidates(b["logits"], b["reg"], b["starts"], window_size, b["queries"].max(), b["vidx"], thr)
-    assert row.shape == ref["row"].shape, (row.shape, ref["row"].shape)
-    assert np.array_equal(row, ref["row"]) and np.array_equal(key, ref["key"])       # membership and order
-    assert seg.dtype == np.float32 and np.array_equal(seg.view(np.int32), ref["seg"].view(np.int32))
-    d = ulp_apart(score, ref["score"])
+    want = {k: ref[k][:first] for k in ("row", "key", "seg", "score")}
+    assert row.shape == want["row"].shape, (row.shape, want["row"].shape)
+    assert np.array_equal(row, want["row"]) and np.array_equal(key, want["key"])     # membership and order
+    assert seg.dtype == np.float32 and np.array_equal(seg.view(np.int32), want["seg"].view(np.int32))
+    d = ulp_apart(score, want["score"])
     assert d.max(initial=0) <= 1
     assert int((d != 0).sum()) <= max(1, len(score) // 1000000)
     return ref
@@ -90,6 +82,33 @@ def test_kernels_match_the_restatement(ncls, B, nq, thr):
     if B * nq >= 8:
         assert len(ref["row"]) > 0 and (ref["row"] == 4).sum() == ncls and not (ref["row"] == 5).any()
         assert not ref["ok"][1] and not ref["ok"][2]
+
+
+def test_grid_stride_past_one_pass_of_the_grid():
+    """R = 8,200 proposal rows: past the 2,048 blocks * 4 waves = 8,192 rows one pass of the grid covers"""
+    B, nq, ncls, thr, ws = 2, 4100, 3, 0.01, 30.000000000000004
+    b = make_batch(43, B, nq, ncls, thr)
+    ref = check_against_ref(run_kernels(b, nq, thr, ws), b, thr, ws)
+    assert len(ref["row"]) > 50 and ref["row"].max() >= 8192          # candidates from the rows of the second pass
+
+
+def test_a_capacity_below_the_count_clips_the_output():
+    """emit with capacity = n // 2 into buffers one guard element longer: the first n // 2 candidates of the full list, and
+    everything from the capacity onward keeps its sentinel"""
+    B, nq, ncls, thr, ws = 2, 9, 23, 0.01, 10.24
+    b = make_batch(29, B, nq, ncls, thr)
+    n = len(check_against_ref(run_kernels(b, nq, thr, ws), b, thr, ws)["row"])
+    cap = n // 2
+    assert n >= 4
+    bufs = (torch.full((cap + 1, 2), -7.0, device=DEV), torch.full((cap + 1,), -7.0, device=DEV),
+            torch.full((cap + 1,), -7, dtype=torch.int64, device=DEV), torch.full((cap + 1,), -7, dtype=torch.int32, device=DEV))
+    res = hd.candidates(dv(b["logits"]), dv(b["reg"]), dv(b["starts"]), ws, dv(b["queries"]).max(), dv(b["vidx"]), nq, thr,
+                        out=tuple(t[:cap] for t in bufs))
+    torch.cuda.synchronize()
+    assert int(res[4].item()) == n                                   # the count is the whole list's
+    check_against_ref([t[:cap].cpu().numpy() for t in bufs], b, thr, ws, first=cap)
+    for t in bufs:
+        assert bool((t[cap:] == -7).all())
 
 
 def test_window_start_beyond_fp32_resolution():
@@ -135,11 +154,6 @@ def test_library_refuses_bad_shapes():
 
 
 # ---- the collector ------------------------------------------------------------------------------------------------------------
-def _meta(video_ids, starts, window_size):
-    return {"video_id": list(video_ids), "window_start": torch.tensor(np.asarray(starts), dtype=torch.float64),
-            "window_size": torch.tensor([window_size] * len(video_ids), dtype=torch.float64)}
-
-
 def _same_detections(got, want):
     gs, gc, gl, gv = [t.cpu().numpy() for t in got]
     ws, wc, wl, wv = want
@@ -266,7 +280,6 @@ def test_both_calls_replay_in_a_graph_on_new_logits():
     nq, ncls, thr, ws, B = 21, 65, 0.03, 30.0, 4
     R = B * nq
     b1, b2 = make_batch(31, B, nq, ncls, thr), make_batch(32, B, nq, ncls, thr)
-    dv = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
     logits, reg, starts, vidx = dv(b1["logits"]), dv(b1["reg"]), dv(b1["starts"]), dv(b1["vidx"])
     mt = dv(b1["queries"]).max().reshape(1)
     cap = R * ncls

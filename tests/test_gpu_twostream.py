@@ -19,20 +19,10 @@ pytestmark = pytest.mark.gpu
 
 from tests import helpers as H  # noqa: E402
 from tests import twostream_ref as T  # noqa: E402
+from tests.candidate_helpers import DEV, dv, logit, ulp_apart  # noqa: E402
+from tests.candidate_helpers import meta as _meta  # noqa: E402
 from tim_amd import _lib as L  # noqa: E402
 from tim_amd import twostream as ts  # noqa: E402
-
-DEV = "cuda"
-
-
-def _logit(t):
-    return np.log(t / (1.0 - t)) if 0.0 < t < 1.0 else -3.0
-
-
-def ulp_apart(a, b):
-    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
-    return np.abs(a.view(np.int32).astype(np.int64) - b.view(np.int32).astype(np.int64))
-
 
 def _near(x, thr):
     """within 4 ulp of the threshold (NaN: no)"""
@@ -72,8 +62,8 @@ def make_batch(seed, B, nq, Cv, Cn, thr, invalid="some", start0=0.0):
         vr[3], nr[3] = (-0.4, 1.7), (0.05, 1.3)                   # clamps
     # the best of C normal draws sits near the threshold's logit: rows where the verb, the noun, both or neither pass
     lift = lambda C: 0.0 if C < 2 else 1.5 * np.sqrt(2 * np.log(C))
-    vl = rng.normal(_logit(thr) - lift(Cv) + 1.0, 1.5, size=(R, Cv)).astype(np.float32)
-    nl = rng.normal(_logit(thr) - lift(Cn) + 1.0, 1.5, size=(R, Cn)).astype(np.float32)
+    vl = rng.normal(logit(thr, -3.0) - lift(Cv) + 1.0, 1.5, size=(R, Cv)).astype(np.float32)
+    nl = rng.normal(logit(thr, -3.0) - lift(Cn) + 1.0, 1.5, size=(R, Cn)).astype(np.float32)
     if R >= 5:
         vl[4] += 6.0                                              # many classes of both streams pass in a valid row
         nl[4] += 6.0
@@ -85,7 +75,6 @@ def make_batch(seed, B, nq, Cv, Cn, thr, invalid="some", start0=0.0):
 
 
 def run_kernels(b, nq, thr, alpha, k, ws, vl_dev=None, nl_dev=None):
-    dv = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
     out = ts.candidates(dv(b["vl"]) if vl_dev is None else vl_dev, dv(b["nl"]) if nl_dev is None else nl_dev, dv(b["vr"]),
                         dv(b["nr"]), dv(b["starts"]), ws, dv(b["queries"]).max(), dv(b["vidx"]), nq, thr, alpha, k, records=True)
     torch.cuda.synchronize()
@@ -266,7 +255,6 @@ def test_a_capacity_below_the_count_clips_the_output():
     n = len(ref["row"])
     cap, G = n - 17, 64
     assert cap > 20
-    dv = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
     big = (torch.full((cap + 2 * G, 2), -7.0, device=DEV), torch.full((cap + 2 * G,), -7.0, device=DEV),
            torch.full((cap + 2 * G,), -7, dtype=torch.int64, device=DEV), torch.full((cap + 2 * G,), -7, dtype=torch.int32, device=DEV))
     out = tuple(t[G:G + cap] for t in big)
@@ -318,11 +306,6 @@ def test_library_argument_checks():
 # ---- the collector ------------------------------------------------------------------------------------------------------------
 def _fixture():
     return np.load(os.path.join(H.GOLDEN, "twostream_small.npz"))
-
-
-def _meta(video_ids, starts, window_size):
-    return {"video_id": list(video_ids), "window_start": torch.tensor(np.asarray(starts), dtype=torch.float64),
-            "window_size": torch.tensor([window_size] * len(video_ids), dtype=torch.float64)}
 
 
 def _collect(g, tag, sizes=(2, 2, 2), **kw):
@@ -422,7 +405,6 @@ def test_one_model_with_verb_and_noun_heads_passed_twice():
     two = _collect(g, "k3")
     one = TwoStreamCollector(11, 23, float(g["threshold"]), 0.65, 3, verb_head="verb", noun_head="noun")
     for b in range(3):
-        dv = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
         output = ((dv(g["verb_logits"][b]), dv(g["noun_logits"][b]), None, None), (dv(g["verb_reg"][b]), None))
         qt = torch.from_numpy(np.tile(g["queries"][None], (2, 1, 1))).to(DEV)
         one.update(output, output, (qt, None), _meta(g["video_ids"][b], g["window_start"][b], float(g["window_size"])))
@@ -464,7 +446,6 @@ def test_both_calls_replay_in_a_graph_on_new_inputs():
     R = B * nq
     b1, b2 = make_batch(31, B, nq, Cv, Cn, thr), make_batch(32, B, nq, Cv, Cn, thr)
     refs = {id(b): settle(b, thr, alpha, k, ws) for b in (b1, b2)}
-    dv = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
     vl, nl, vr, nr, starts, vidx = dv(b1["vl"]), dv(b1["nl"]), dv(b1["vr"]), dv(b1["nr"]), dv(b1["starts"]), dv(b1["vidx"])
     mt = dv(b1["queries"]).max().reshape(1)
     cap = R * k * k

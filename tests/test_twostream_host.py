@@ -3,7 +3,6 @@ without a GPU, the two library entry points are declared in the header, bound, a
 and the kernels are in the spill gate's table."""
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -11,11 +10,8 @@ import pytest
 import torch
 
 import tim_amd
+from tests.candidate_helpers import ROOT, check_entry_points
 from tim_amd import _lib
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = {"timhip_ts_candidates_count", "timhip_ts_candidates_emit"}
-
 
 def test_collector_is_a_lazy_export():
     assert "TwoStreamCollector" not in vars(tim_amd)
@@ -56,17 +52,7 @@ def test_exponents_match_the_restatement():
 
 
 def test_entry_points_are_declared_bound_and_exported():
-    hdr = open(os.path.join(ROOT, "include", "timhip.h")).read()
-    declared = {n for n in re.findall(r"\b(timhip_[a-z0-9_]+)\s*\(", hdr) if n.startswith("timhip_ts_")}
-    assert declared == NAMES
-    assert NAMES <= set(_lib.exported_symbols())
-    assert len(_lib._SIGS["timhip_ts_candidates_count"][1]) == 24 and len(_lib._SIGS["timhip_ts_candidates_emit"][1]) == 17
-    assert re.search(r"#define\s+TIMHIP_VERSION\s+6\b", hdr) and _lib.ABI_VERSION == 6      # additive: the version stays
-    so = _lib.LIB_PATH
-    if os.path.exists(so):
-        syms = subprocess.run(["nm", "-D", "--defined-only", so], capture_output=True, text=True, check=True).stdout
-        for n in NAMES:
-            assert re.search(r"\bT %s\b" % n, syms), n
+    check_entry_points("timhip_ts_", {"timhip_ts_candidates_count": 24, "timhip_ts_candidates_emit": 17}, "twostream.hip")
 
 
 def test_kernels_are_in_the_spill_table_and_the_unit_in_the_makefile():
@@ -79,6 +65,3 @@ def test_kernels_are_in_the_spill_table_and_the_unit_in_the_makefile():
     assert pats["ts_select_kernel"] == 0 and pats["ts_emit_kernel"] == 0
     mk = open(os.path.join(ROOT, "tim_amd", "csrc", "Makefile")).read()
     assert re.search(r"^SRCS\s*=.*\btwostream\.hip\b", mk, re.M)
-    src = open(os.path.join(ROOT, "tim_amd", "csrc", "twostream.hip")).read()
-    assert "#pragma clang fp contract(off)" in src and '#include "row_scan.h"' in src
-    assert '#include "row_scan.h"' in open(os.path.join(ROOT, "tim_amd", "csrc", "detect.hip")).read()

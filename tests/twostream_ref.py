@@ -1,21 +1,11 @@
 """TEST INFRASTRUCTURE ONLY: numpy restatement of the two-stream detection fusion - what the reference's
 eval_detection/format_two_stream_predictions_epic.py computes between the saved outputs of a verb model and a noun model and
 its submission, written from its contract.  tests/test_twostream_ref.py pins it to a fixture recorded from the reference
-itself; tests/test_gpu_twostream.py then checks the HIP kernels and tim_amd.TwoStreamCollector against it.  The sigmoid is
-tests/detect_ref.py's, the NMS goes through oracle.nms_oracle.  Never imported by tim_amd."""
+itself; tests/test_gpu_twostream.py then checks the HIP kernels and tim_amd.TwoStreamCollector against it.  The sigmoid and
+the decode of a stream's proposals are tests/detect_ref.py's, the NMS goes through oracle.nms_oracle.  Never imported by tim_amd."""
 import numpy as np
 
-from oracle import nms_oracle
-from tests.detect_ref import sigmoid32
-
-
-def proposals(reg, window_start, window_size, max_time, num_queries):
-    """-> [R, 2] float64: the decoded proposal of one stream, NOT rounded (the reference's saved v_proposals)"""
-    reg = np.asarray(reg, dtype=np.float32)
-    p = np.minimum(np.maximum(reg, np.float32(0.0)), np.float32(max_time))              # fp32 clamp (NaN propagates)
-    p = (p * np.float32(window_size)).astype(np.float32)                                # fp32 product, rounded once
-    start = np.repeat(np.asarray(window_start, dtype=np.float64), num_queries)
-    return p.astype(np.float64) + start[:, None]
+from tests.detect_ref import CollectorBase, proposals, sigmoid32  # noqa: F401 (proposals: the shared decode, per stream)
 
 
 def select_top_k(score, k):
@@ -74,21 +64,15 @@ def batch_candidates(verb_logits, noun_logits, verb_reg, noun_reg, window_start,
                 key=video * (Cv * Cn) + verb * Cn + noun, row=rows.astype(np.int32), verb=verb, noun=noun, video=video)
 
 
-class Collector:
+class Collector(CollectorBase):
     """numpy mirror of tim_amd.TwoStreamCollector"""
 
     def __init__(self, num_verbs, num_nouns, score_threshold=0.03, verb_alpha=0.65, top_k=1):
+        super().__init__()
         self.V, self.N, self.thr, self.alpha, self.k = int(num_verbs), int(num_nouns), score_threshold, verb_alpha, int(top_k)
-        self.video_ids, self._index, self.chunks = [], {}, []
 
     def update(self, verb_logits, noun_logits, verb_reg, noun_reg, query_times, video_ids, window_start, window_size):
-        idx = []
-        for v in video_ids:
-            v = str(v)
-            if v not in self._index:
-                self._index[v] = len(self.video_ids)
-                self.video_ids.append(v)
-            idx.append(self._index[v])
+        idx = self._video_index(video_ids)
         max_time = np.asarray(query_times, dtype=np.float32).max()
         self.chunks.append(batch_candidates(verb_logits, noun_logits, verb_reg, noun_reg, window_start, window_size, max_time,
                                             idx, self.thr, self.alpha, self.k))
@@ -103,17 +87,7 @@ class Collector:
     def detections(self, sigma=0.25, iou_threshold=0.1, min_score=0.001, method=2, nms="soft", task="action"):
         """-> (segs, scores, labels, video) ordered by video, then descending score (stable)"""
         c = self.candidates()
-        out = [[], [], [], []]
-        for v in range(len(self.video_ids)):
-            m = c["video"] == v
-            if not m.any():
-                continue
-            s, sc, lb = nms_oracle.batched_nms(c["seg"][m], c["score"][m], c["verb"][m] * self.N + c["noun"][m], iou_threshold,
-                                               min_score, sigma, method, nms)
-            out[0].append(s); out[1].append(sc); out[2].append(lb); out[3].append(np.full(len(sc), v, np.int64))
-        if not out[1]:
-            return np.zeros((0, 2), np.float32), np.zeros(0, np.float32), np.zeros(0, np.int64), np.zeros(0, np.int64)
-        s, sc, lb, vd = (np.concatenate(o) for o in out)
+        s, sc, lb, vd = self._nms_per_video(c, c["verb"] * self.N + c["noun"], iou_threshold, min_score, sigma, method, nms)
         lb = lb.astype(np.int64)
         return s, sc, {"action": lb, "verb": lb // self.N, "noun": lb % self.N}[task], vd
 

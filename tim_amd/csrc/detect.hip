@@ -8,7 +8,7 @@
 // reference's order - proposal by proposal, ascending class inside a proposal - by count + scan + emit:
 //   det_count_kernel   one wavefront per proposal row: decode + round the segment (fp32 / fp64 split below), count the
 //                      classes over the threshold -> row_offsets[r + 1]
-//   det_scan_kernel    (row_scan.h) one block: in-place inclusive scan -> row_offsets[r] = first output slot of row r, [R] = total
+//   det_scan_kernel    (candidates.h) one block: in-place inclusive scan -> row_offsets[r] = first output slot of row r, [R] = total
 //   det_emit_kernel    the same walk; candidate k of row r lands at row_offsets[r] + k (__ballot + popcount of the lower
 //                      lanes inside a 64-class chunk, a running base across chunks)
 // No atomics and no look-back between workgroups: nothing depends on dispatch order.
@@ -40,28 +40,11 @@
 #include <math.h>
 
 #include "common.h"
-#include "row_scan.h"
 
-#pragma clang fp contract(off)
+#pragma clang fp contract(off)   // ahead of candidates.h: its arithmetic is compiled under it as well
+#include "candidates.h"
 
 namespace {
-
-constexpr int kWavesPerBlock = 4;
-constexpr int kMaxBlocks = 2048;   // memory-bound grid: cap the grid and stride over the rows
-
-__device__ __forceinline__ float det_score(float x) {
-  return (float)__ddiv_rn(1.0, __dadd_rn(1.0, exp(-(double)x)));
-}
-
-// numpy.round(v, 3) on float64
-__device__ __forceinline__ double det_round3(double v) { return __ddiv_rn(rint(__dmul_rn(v, 1000.0)), 1000.0); }
-
-__device__ __forceinline__ float det_clamp(float v, float hi) {
-  if (v != v) return v;                       // torch.clamp propagates NaN (such a proposal fails the width test below)
-  return fminf(fmaxf(v, 0.0f), hi);
-}
-
-__device__ __forceinline__ unsigned long long lanes_below(int lane) { return (1ull << lane) - 1ull; }
 
 __global__ __launch_bounds__(64 * kWavesPerBlock) void det_count_kernel(
     const float* __restrict__ logits, long long ld, const float* __restrict__ reg, const double* __restrict__ window_start,
@@ -73,10 +56,9 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void det_count_kernel(
   const float tmax = max_time[0];
   for (int r = wave; r < R; r += nwaves) {
     // ---- the proposal (every lane computes the same two numbers; lane 0 stores them)
-    const float c0 = det_clamp(reg[2 * (size_t)r], tmax), c1 = det_clamp(reg[2 * (size_t)r + 1], tmax);
-    const float m0 = __fmul_rn(c0, window_size), m1 = __fmul_rn(c1, window_size);
     const double ws = window_start[r / Nq];
-    const double p0 = det_round3(__dadd_rn((double)m0, ws)), p1 = det_round3(__dadd_rn((double)m1, ws));
+    const double p0 = cand_round3(cand_decode(reg[2 * (size_t)r], tmax, window_size, ws));
+    const double p1 = cand_round3(cand_decode(reg[2 * (size_t)r + 1], tmax, window_size, ws));
     const bool ok = __dsub_rn(p1, p0) > 0.0;
     int n = 0;
     if (ok) {
@@ -91,7 +73,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void det_count_kernel(
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           bool pass = x[k] > hi;
-          if (!pass && !(x[k] < lo) && cb + 64 * k + lane < C) pass = det_score(x[k]) > thr;
+          if (!pass && !(x[k] < lo) && cb + 64 * k + lane < C) pass = cand_sigmoid(x[k]) > thr;
           n += __popcll(__ballot(pass));
         }
       }
@@ -116,9 +98,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void det_emit_kernel(
   for (int r = wave; r < R; r += nwaves) {
     if (!seg_ok[r]) continue;                                  // its logits are not read at all
     long long base = row_offsets[r];
-    // never past this row's slots nor past the buffers: a count taken on other logits cannot make this kernel write
-    // out of bounds, it can only cut the row short
-    const long long end = min((long long)row_offsets[r + 1], capacity);
+    const long long end = cand_row_end(row_offsets, r, capacity);
     if (base >= end) continue;
     const float s0 = seg32[2 * (size_t)r], s1 = seg32[2 * (size_t)r + 1];
     const long long key0 = (long long)video_index[r / Nq] * (long long)C;
@@ -135,7 +115,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void det_emit_kernel(
         const int c = cb + 64 * k + lane;
         float s = 0.f;
         bool pass = false;
-        if (!(x[k] < lo) && c < C) { s = det_score(x[k]); pass = s > thr; }
+        if (!(x[k] < lo) && c < C) { s = cand_sigmoid(x[k]); pass = s > thr; }
         const unsigned long long m = __ballot(pass);
         const long long pos = base + __popcll(m & lanes_below(lane));
         if (pass && pos < end) {
@@ -176,11 +156,6 @@ void det_bounds(float thr, float* lo, float* hi) {
   }
 }
 
-int det_grid(int R) {
-  const int blocks = (R + kWavesPerBlock - 1) / kWavesPerBlock;
-  return blocks < 1 ? 1 : (blocks > kMaxBlocks ? kMaxBlocks : blocks);
-}
-
 int det_check_shape(int R, int C, long long ld, int Nq) {
   if (R < 0 || C < 1 || Nq < 1 || ld < C || R % Nq != 0) return TIMHIP_EINVAL;
   if ((long long)R * (long long)C > 0x7fffffffLL) return TIMHIP_EUNSUPPORTED;   // the offsets are int32
@@ -202,14 +177,12 @@ int timhip_det_candidates_count(const float* logits, int64_t ld_logits, const fl
   float lo, hi;
   det_bounds(score_threshold, &lo, &hi);
   if (R > 0) {
-    hipLaunchKernelGGL(det_count_kernel, dim3(det_grid(R)), dim3(64 * kWavesPerBlock), 0, s, logits, (long long)ld_logits,
+    hipLaunchKernelGGL(det_count_kernel, dim3(cand_grid(R)), dim3(64 * kWavesPerBlock), 0, s, logits, (long long)ld_logits,
                        reg, window_start, window_size, max_time, R, C, Nq, score_threshold, lo, hi, seg32, seg_ok,
                        row_offsets);
     TIM_CHECK_LAUNCH();
   }
-  hipLaunchKernelGGL(det_scan_kernel, dim3(1), dim3(1024), 0, s, row_offsets, R);
-  TIM_CHECK_LAUNCH();
-  return TIMHIP_OK;
+  return cand_scan(row_offsets, R, s);
 }
 
 int timhip_det_candidates_emit(const float* logits, int64_t ld_logits, const float* seg32, const uint8_t* seg_ok,
@@ -223,7 +196,7 @@ int timhip_det_candidates_emit(const float* logits, int64_t ld_logits, const flo
   if (!logits || !seg32 || !seg_ok || !row_offsets || !video_index || !seg || !score || !key || !row) return TIMHIP_EINVAL;
   float lo, hi;
   det_bounds(score_threshold, &lo, &hi);
-  hipLaunchKernelGGL(det_emit_kernel, dim3(det_grid(R)), dim3(64 * kWavesPerBlock), 0, (hipStream_t)stream, logits,
+  hipLaunchKernelGGL(det_emit_kernel, dim3(cand_grid(R)), dim3(64 * kWavesPerBlock), 0, (hipStream_t)stream, logits,
                      (long long)ld_logits, seg32, seg_ok, row_offsets, video_index, R, C, Nq, score_threshold, lo,
                      (long long)capacity, seg, score, (long long*)key, row);
   TIM_CHECK_LAUNCH();

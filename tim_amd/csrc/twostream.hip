@@ -8,18 +8,18 @@
 // score inside a verb - by select + scan + emit:
 //   ts_select_kernel   one wavefront per proposal row: both rows of logits -> fp32 scores, the top k of each stream, the
 //                      k * k pairs (one lane each) -> a small record per row and row_offsets[r + 1] = the survivors
-//   det_scan_kernel    row_scan.h, shared with detect.hip: in-place inclusive scan
+//   det_scan_kernel    candidates.h, shared with detect.hip: in-place inclusive scan
 //   ts_emit_kernel     reads only the records; survivor j of row r lands at row_offsets[r] + j
 // No atomics and no look-back between workgroups: nothing depends on dispatch order.
 //
 // Arithmetic, operation by operation as the reference's arrays carry it (NumPy 2: an fp32 scalar combined with a Python
 // float stays fp32):
-//   vs, ns   = (float)(1.0 / (1.0 + exp(-(double)x)))     det_score of detect.hip: the float64 sigmoid rounded once
+//   vs, ns   = (float)(1.0 / (1.0 + exp(-(double)x)))     cand_sigmoid of candidates.h: the float64 sigmoid, one rounding
 //   prop     = (double)(clamp(reg, 0, max_time) * window_size) + window_start     fp32 clamp and product, fp64 sum, per
 //                                                          stream, NOT rounded (the saved v_proposals are float64)
 //   pass     = vs > thr  &&  ns > thr  &&  score > thr     fp32 compares (a NaN fails them)
 //   score    = (float)pow(vs, a32) * (float)pow(ns, b32)   each power the float64 pow rounded once to fp32 (reproducible on
-//                                                          a CPU, as det_score is), the product fp32 with one rounding
+//                                                          a CPU, as cand_sigmoid is), the product fp32 with one rounding
 //   w        = vs / (vs + ns),  w1 = 1 - w                 fp32
 //   seg      = (double)w * prop_v + (double)w1 * prop_n    two fp64 products, one fp64 add (contraction off)
 //   seg      = rint(seg * 1000.0) / 1000.0                 numpy.round(seg, 3)
@@ -36,27 +36,14 @@
 #include <math.h>
 
 #include "common.h"
-#include "row_scan.h"
 
-#pragma clang fp contract(off)
+#pragma clang fp contract(off)   // ahead of candidates.h: its arithmetic is compiled under it as well
+#include "candidates.h"
 
 namespace {
 
-constexpr int kWavesPerBlock = 4;
-constexpr int kMaxBlocks = 2048;      // memory-bound grid: cap the grid and stride over the rows
 constexpr int kMaxTopK = 8;           // k * k pairs, one lane each
 constexpr int kMaxClasses = 4096;     // Cv + Cn: 4 waves * 4096 words = the 64 KiB of LDS a block may ask for
-
-__device__ __forceinline__ float ts_sigmoid(float x) {
-  return (float)__ddiv_rn(1.0, __dadd_rn(1.0, exp(-(double)x)));
-}
-
-__device__ __forceinline__ double ts_round3(double v) { return __ddiv_rn(rint(__dmul_rn(v, 1000.0)), 1000.0); }
-
-__device__ __forceinline__ float ts_clamp(float v, float hi) {
-  if (v != v) return v;                       // torch.clamp propagates NaN (such a pair fails the width test)
-  return fminf(fmaxf(v, 0.0f), hi);
-}
 
 __device__ __forceinline__ unsigned ts_key(float s) { return s != s ? 0xffffffffu : __float_as_uint(s) + 1u; }
 __device__ __forceinline__ float ts_unkey(unsigned k) {
@@ -76,7 +63,7 @@ __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
 // scores of one row into this lane's words of `keys`, then k rounds of maximum; lane j < k returns winner j
 __device__ __forceinline__ void ts_top_k(const float* __restrict__ row, int C, int k, int lane, unsigned* keys, unsigned* my_key,
                                          int* my_idx) {
-  for (int c = lane; c < C; c += 64) keys[c] = ts_key(ts_sigmoid(row[c]));
+  for (int c = lane; c < C; c += 64) keys[c] = ts_key(cand_sigmoid(row[c]));
   *my_key = 0u;
   *my_idx = 0;
   for (int j = 0; j < k; ++j) {
@@ -127,10 +114,9 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void ts_select_kernel(
     double s[2];
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
-      const float mv = __fmul_rn(ts_clamp(verb_reg[2 * (size_t)r + e], tmax), window_size);
-      const float mn = __fmul_rn(ts_clamp(noun_reg[2 * (size_t)r + e], tmax), window_size);
-      const double pv = __dadd_rn((double)mv, ws), pn = __dadd_rn((double)mn, ws);
-      s[e] = ts_round3(__dadd_rn(__dmul_rn((double)w, pv), __dmul_rn((double)w1, pn)));
+      const double pv = cand_decode(verb_reg[2 * (size_t)r + e], tmax, window_size, ws);
+      const double pn = cand_decode(noun_reg[2 * (size_t)r + e], tmax, window_size, ws);
+      s[e] = cand_round3(__dadd_rn(__dmul_rn((double)w, pv), __dmul_rn((double)w1, pn)));
     }
     const bool pass = lane < kk && vs > thr && ns > thr && score > thr && __dsub_rn(s[1], s[0]) > 0.0;
     const unsigned long long m = __ballot(pass);
@@ -159,10 +145,8 @@ __global__ __launch_bounds__(256) void ts_emit_kernel(
     const int r = (int)(t / kk), p = (int)(t - (long long)r * kk);
     const unsigned long long m = pair_mask[r];
     if (!((m >> p) & 1ull)) continue;
-    // never past this row's slots nor past the buffers: a count taken on other inputs cannot make this kernel write out of
-    // bounds, it can only cut the row short
-    const long long end = min((long long)row_offsets[r + 1], capacity);
-    const long long pos = (long long)row_offsets[r] + __popcll(m & ((1ull << p) - 1ull));
+    const long long end = cand_row_end(row_offsets, r, capacity);
+    const long long pos = (long long)row_offsets[r] + __popcll(m & lanes_below(p));
     if (pos < 0 || pos >= end) continue;
     const int verb = sel_idx[(size_t)r * (size_t)(2 * k) + p / k], noun = sel_idx[(size_t)r * (size_t)(2 * k) + k + p % k];
     seg[2 * pos] = pair_seg[2 * t];
@@ -171,11 +155,6 @@ __global__ __launch_bounds__(256) void ts_emit_kernel(
     key[pos] = (long long)video_index[r / Nq] * ((long long)Cv * (long long)Cn) + (long long)verb * Cn + noun;
     rowid[pos] = r;
   }
-}
-
-int ts_grid(int R) {
-  const int blocks = (R + kWavesPerBlock - 1) / kWavesPerBlock;
-  return blocks < 1 ? 1 : (blocks > kMaxBlocks ? kMaxBlocks : blocks);
 }
 
 int ts_check_shape(int R, int Cv, int Cn, int Nq, int k) {
@@ -204,15 +183,13 @@ int timhip_ts_candidates_count(const float* verb_logits, int64_t ld_v, const flo
   hipStream_t s = (hipStream_t)stream;
   if (R > 0) {
     const size_t lds = (size_t)kWavesPerBlock * (size_t)(Cv + Cn) * sizeof(unsigned);
-    hipLaunchKernelGGL(ts_select_kernel, dim3(ts_grid(R)), dim3(64 * kWavesPerBlock), lds, s, verb_logits, (long long)ld_v,
+    hipLaunchKernelGGL(ts_select_kernel, dim3(cand_grid(R)), dim3(64 * kWavesPerBlock), lds, s, verb_logits, (long long)ld_v,
                        noun_logits, (long long)ld_n, verb_reg, noun_reg, window_start, window_size, max_time, R, Cv, Cn, Nq,
                        top_k, score_threshold, alpha32, beta32, sel_idx, sel_score, pair_score, pair_seg,
                        (unsigned long long*)pair_mask, row_offsets);
     TIM_CHECK_LAUNCH();
   }
-  hipLaunchKernelGGL(det_scan_kernel, dim3(1), dim3(1024), 0, s, row_offsets, R);
-  TIM_CHECK_LAUNCH();
-  return TIMHIP_OK;
+  return cand_scan(row_offsets, R, s);
 }
 
 int timhip_ts_candidates_emit(const int32_t* sel_idx, const float* pair_score, const float* pair_seg, const uint64_t* pair_mask,

@@ -11,9 +11,9 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from ._collect import CandidateCollector, candidate_buffers, fp32_rows, require_gpu
 from ._lib import call, ptr
 from .functional import _stream
-from .nms import grouped_nms
 
 # head -> (slot of the classification outputs, slot of the regressions / query times)
 HEADS = {"verb": (0, 0), "noun": (1, 0), "action": (2, 0), "audio": (3, 1)}
@@ -33,10 +33,7 @@ def head_classes(num_class, head):
     return int(vis)
 
 
-def _on_gpu(t, what):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise L.TimHipError("DetectionCollector.update: %s must be a device tensor; the detection tail runs on the "
-                            "MI355X HIP kernels only (there is no CPU fallback)" % what)
+_WHO = ("DetectionCollector.update", "the detection tail runs")
 
 
 def candidates(logits, reg, window_start, window_size, max_time, video_index, num_queries, score_threshold, out=None):
@@ -46,9 +43,8 @@ def candidates(logits, reg, window_start, window_size, max_time, video_index, nu
     `out` = (seg, score, key, row) buffers to fill instead (their length is the capacity; nothing is read back and the
     returned tensors are the buffers, valid up to row_offsets[R] which is returned as a fifth, device, value)."""
     L.load()
+    logits = fp32_rows(logits)
     R, C = logits.shape
-    if logits.dtype != torch.float32 or logits.stride(1) != 1 or logits.stride(0) < C:
-        logits = logits.to(torch.float32).contiguous()
     reg = reg.to(torch.float32).contiguous()
     dev = logits.device
     seg32 = torch.empty((R, 2), dtype=torch.float32, device=dev)
@@ -58,15 +54,7 @@ def candidates(logits, reg, window_start, window_size, max_time, video_index, nu
     st = _stream()
     call("timhip_det_candidates_count", ptr(logits), logits.stride(0), ptr(reg), ptr(window_start),
          float(np.float32(window_size)), ptr(max_time), R, C, int(num_queries), thr, ptr(seg32), ptr(ok), ptr(off), st)
-    if out is None:
-        n = int(off[R].item())                              # the one device-to-host read of a batch: 4 bytes
-        seg = torch.empty((n, 2), dtype=torch.float32, device=dev)
-        score = torch.empty((n,), dtype=torch.float32, device=dev)
-        key = torch.empty((n,), dtype=torch.int64, device=dev)
-        row = torch.empty((n,), dtype=torch.int32, device=dev)
-    else:
-        seg, score, key, row = out
-        n = score.shape[0]
+    (seg, score, key, row), n = candidate_buffers(off, R, out)
     call("timhip_det_candidates_emit", ptr(logits), logits.stride(0), ptr(seg32), ptr(ok), ptr(off), ptr(video_index),
          R, C, int(num_queries), thr, n, ptr(seg), ptr(score), ptr(key), ptr(row), st)
     if out is None:
@@ -74,7 +62,7 @@ def candidates(logits, reg, window_start, window_size, max_time, video_index, nu
     return seg, score, key, row, off[R]
 
 
-class DetectionCollector:
+class DetectionCollector(CandidateCollector):
     """Collects the detection candidates of one head over an evaluation and turns them into detections.
 
         col = DetectionCollector(num_class, head="action", score_threshold=0.01)
@@ -91,17 +79,12 @@ class DetectionCollector:
         self.score_threshold = float(score_threshold)
         self.reset()
 
-    def reset(self):
-        self.video_ids = []          # dense index -> video id, in first-seen order
-        self._index = {}
-        self._chunks = []            # per batch (seg, score, key) on the device
-
     def update(self, features, regressions, query_times, metadata):
         cls_slot, reg_slot = HEADS[self.head]
         logits, reg, qt = features[cls_slot], regressions[reg_slot], query_times[reg_slot]
-        _on_gpu(logits, "features[%d]" % cls_slot)
-        _on_gpu(reg, "regressions[%d]" % reg_slot)
-        _on_gpu(qt, "query_times[%d]" % reg_slot)
+        require_gpu(logits, _WHO, "features[%d]" % cls_slot)
+        require_gpu(reg, _WHO, "regressions[%d]" % reg_slot)
+        require_gpu(qt, _WHO, "query_times[%d]" % reg_slot)
         if logits.dim() != 2 or logits.shape[1] != self.num_classes:
             raise ValueError("the %s head has %d classes, got logits of shape %s"
                              % (self.head, self.num_classes, tuple(logits.shape)))
@@ -109,47 +92,17 @@ class DetectionCollector:
         B, R = len(vids), logits.shape[0]
         if B == 0 or R % B != 0 or reg.shape[0] != R:
             raise ValueError("%d proposal rows do not divide into %d windows" % (R, B))
-        idx = np.empty(B, dtype=np.int32)
-        for i, v in enumerate(vids):
-            v = str(v)
-            j = self._index.get(v)
-            if j is None:
-                j = self._index[v] = len(self.video_ids)
-                self.video_ids.append(v)
-            idx[i] = j
-        starts = torch.as_tensor(metadata["window_start"]).detach().to(torch.float64).reshape(-1)
-        if starts.numel() != B:
-            raise ValueError("metadata['window_start'] holds %d values for %d windows" % (starts.numel(), B))
-        window_size = float(torch.as_tensor(metadata["window_size"]).reshape(-1)[0])
+        idx = self._video_index(vids)
+        starts, window_size = self._windows(metadata, B)
         dev = logits.device
-        max_time = qt.detach().to(torch.float32).max()       # stays on the device
-        seg, score, key, _ = candidates(logits.detach(), reg.detach(), starts.to(dev), window_size, max_time,
+        seg, score, key, _ = candidates(logits.detach(), reg.detach(), starts.to(dev), window_size, self._max_time(qt),
                                         torch.from_numpy(idx).to(dev), R // B, self.score_threshold)
-        if score.shape[0]:
-            self._chunks.append((seg, score, key))
-
-    def candidates(self):
-        """everything collected so far: (seg [N, 2], score [N], key [N]) in collection order"""
-        if not self._chunks:
-            if not torch.cuda.is_available():
-                raise L.TimHipError("DetectionCollector runs on the MI355X HIP kernels only (no CPU fallback)")
-            dev = torch.device("cuda")
-            return (torch.zeros((0, 2), dtype=torch.float32, device=dev), torch.zeros((0,), dtype=torch.float32, device=dev),
-                    torch.zeros((0,), dtype=torch.int64, device=dev))
-        if len(self._chunks) > 1:                            # concatenate once, and keep the result as the one chunk
-            self._chunks = [tuple(torch.cat([c[i] for c in self._chunks]) for i in range(3))]
-        return self._chunks[0]
+        self._keep(seg, score, key)
 
     def detections(self, sigma=0.1, iou_threshold=0.1, min_score=0.001, method=2, nms="soft"):
         """-> (segs [M, 2] fp32, scores [M] fp32, labels [M] int64, video [M] int64 index into `video_ids`), ordered by
         video and, inside a video, by descending score (stable: equal scores keep class, then selection order)"""
-        seg, score, key = self.candidates()
-        s, c, k = grouped_nms(seg, score, key, iou_threshold, min_score, sigma, method, nms)
-        video = torch.div(k, self.num_classes, rounding_mode="floor")
-        labels = k - video * self.num_classes
-        o = torch.argsort(-c, stable=True)
-        o = o[torch.argsort(video[o], stable=True)]
-        return s[o], c[o], labels[o], video[o]
+        return self._detections(iou_threshold, min_score, sigma, method, nms)
 
     def results(self, **nms_args):
         """the `results` dict of the reference's submission (format_predictions.py): every video seen, its detections by

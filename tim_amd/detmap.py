@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from ._collect import require_gpu
 from ._lib import call, ptr
 from .functional import _stream
 
@@ -33,10 +34,7 @@ def timestamp_to_seconds(timestamp):
     return h * 3600 + m * 60 + s
 
 
-def _on_gpu(t, what):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise L.TimHipError("DetectionScorer.evaluate: %s must be a device tensor; detection scoring runs on the MI355X HIP "
-                            "kernels only (there is no CPU fallback)" % what)
+_WHO = ("DetectionScorer.evaluate", "detection scoring runs")
 
 
 class DetectionScorer:
@@ -85,7 +83,7 @@ class DetectionScorer:
         at the end, all 0), `order` [M] (position -> input row) and `lock` [T, G] (ground-truth input row -> the rank inside
         its class of the prediction that took it, -1: none) on the device."""
         for t, what in ((segs, "segs"), (scores, "scores"), (labels, "labels"), (video, "video")):
-            _on_gpu(t, what)
+            require_gpu(t, _WHO, what)
         M = scores.shape[0]
         if scores.dim() != 1 or tuple(segs.shape) != (M, 2) or tuple(labels.shape) != (M,) or tuple(video.shape) != (M,):
             raise ValueError("segs %s, scores %s, labels %s, video %s do not describe one list of detections"

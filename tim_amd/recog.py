@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from ._collect import require_gpu
 from ._lib import call, ptr
 from .detect import HEADS, head_classes
 from .functional import _stream
@@ -22,10 +23,7 @@ VISUAL_HEADS = ("verb", "noun", "action")
 NO_RANK = 0x7fffffff            # rank of an action without a usable label (csrc/recog.hip)
 
 
-def _on_gpu(t, what):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise L.TimHipError("RecognitionCollector.update: %s must be a device tensor; the recognition tail runs on the "
-                            "MI355X HIP kernels only (there is no CPU fallback)" % what)
+_WHO = ("RecognitionCollector.update", "the recognition tail runs")
 
 
 def accuracy_floats(count1, count5, size):
@@ -111,11 +109,11 @@ class RecognitionCollector:
             labels = [labels[k] for k in (VISUAL_HEADS if g.n_labels == 3 else ("class_id",))]
         if isinstance(labels, (list, tuple)):
             for t in labels:
-                _on_gpu(t, what)
+                require_gpu(t, _WHO, what)
             if len(labels) != g.n_labels:
                 raise ValueError("%s: %d label vectors for %d label columns" % (what, len(labels), g.n_labels))
             labels = torch.stack([t.reshape(-1) for t in labels], dim=1) if g.n_labels > 1 else labels[0]
-        _on_gpu(labels, what)
+        require_gpu(labels, _WHO, what)
         if labels.dtype != torch.int64:
             labels = labels.to(torch.int64)
         if labels.numel() != R * g.n_labels:
@@ -132,7 +130,7 @@ class RecognitionCollector:
         for i, h in enumerate(g.heads):
             slot = HEADS[h][0]
             x = features[slot]
-            _on_gpu(x, "features[%d]" % slot)
+            require_gpu(x, _WHO, "features[%d]" % slot)
             if x.dim() != 2 or x.shape[1] != g.classes[i]:
                 raise ValueError("the %s head has %d classes, got logits of shape %s" % (h, g.classes[i], tuple(x.shape)))
             x = x.detach()
@@ -145,7 +143,7 @@ class RecognitionCollector:
             keep.append(x)
             table[i].logits, table[i].sum, table[i].ld = ptr(x), ptr(g.sum[i]), max(int(x.stride(0)), g.classes[i])
             table[i].C, table[i].pitch = g.classes[i], g.pitch[i]
-        _on_gpu(ids, "%s_action_ids" % name[0])
+        require_gpu(ids, _WHO, "%s_action_ids" % name[0])
         ids = ids.detach().reshape(-1)
         if ids.dtype != torch.int64 or ids.stride(0) != 1:
             ids = ids.to(torch.int64).contiguous()
@@ -155,7 +153,7 @@ class RecognitionCollector:
         if labels is not None:
             labels, ld_labels = self._labels(g, labels, R, "%s_labels" % name[0])
         if valid is not None:
-            _on_gpu(valid, "%s_valid" % name[0])
+            require_gpu(valid, _WHO, "%s_valid" % name[0])
             valid = valid.detach().reshape(-1)
             if valid.numel() != R:
                 raise ValueError("%s_valid holds %d values for %d rows" % (name[0], valid.numel(), R))

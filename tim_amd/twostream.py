@@ -13,30 +13,21 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from ._collect import CandidateCollector, candidate_buffers, fp32_rows, require_gpu
 from ._lib import call, ptr
 from .detect import HEADS
 from .functional import _stream
-from .nms import grouped_nms
 
 MAX_TOP_K = 8         # csrc/twostream.hip: k * k pairs, one lane each
 TASKS = ("action", "verb", "noun")
 
 
-def _on_gpu(t, what):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise L.TimHipError("TwoStreamCollector.update: %s must be a device tensor; the two-stream fusion runs on the "
-                            "MI355X HIP kernels only (there is no CPU fallback)" % what)
+_WHO = ("TwoStreamCollector.update", "the two-stream fusion runs")
 
 
 def exponents(verb_alpha):
     """(alpha32, beta32) as the library takes them: the subtraction in double, each rounded to fp32"""
     return float(np.float32(verb_alpha)), float(np.float32(1.0 - float(verb_alpha)))
-
-
-def _rows(t):
-    if t.dtype != torch.float32 or t.stride(1) != 1 or t.stride(0) < t.shape[1]:
-        t = t.to(torch.float32).contiguous()
-    return t
 
 
 def candidates(verb_logits, noun_logits, verb_reg, noun_reg, window_start, window_size, max_time, video_index, num_queries,
@@ -50,7 +41,7 @@ def candidates(verb_logits, noun_logits, verb_reg, noun_reg, window_start, windo
     `records=True` appends the per-row records (sel_idx [R, 2, k], sel_score [R, 2, k], pair_score [R, k * k],
     pair_seg [R, k * k, 2], pair_mask [R] int64, row_offsets [R + 1])."""
     L.load()
-    verb_logits, noun_logits = _rows(verb_logits), _rows(noun_logits)
+    verb_logits, noun_logits = fp32_rows(verb_logits), fp32_rows(noun_logits)
     R, Cv = verb_logits.shape
     Cn = noun_logits.shape[1]
     k = int(top_k)
@@ -69,15 +60,7 @@ def candidates(verb_logits, noun_logits, verb_reg, noun_reg, window_start, windo
          ptr(verb_reg), ptr(noun_reg), ptr(window_start), float(np.float32(window_size)), ptr(max_time), R, Cv, Cn,
          int(num_queries), k, float(np.float32(score_threshold)), a32, b32, ptr(sel_idx), ptr(sel_score), ptr(pair_score),
          ptr(pair_seg), ptr(pair_mask), ptr(off), st)
-    if out is None:
-        n = int(off[R].item())                              # the one device-to-host read of a batch: 4 bytes
-        seg = torch.empty((n, 2), dtype=torch.float32, device=dev)
-        score = torch.empty((n,), dtype=torch.float32, device=dev)
-        key = torch.empty((n,), dtype=torch.int64, device=dev)
-        row = torch.empty((n,), dtype=torch.int32, device=dev)
-    else:
-        seg, score, key, row = out
-        n = score.shape[0]
+    (seg, score, key, row), n = candidate_buffers(off, R, out)
     call("timhip_ts_candidates_emit", ptr(sel_idx), ptr(pair_score), ptr(pair_seg), ptr(pair_mask), ptr(off), ptr(video_index),
          R, Cv, Cn, int(num_queries), k, n, ptr(seg), ptr(score), ptr(key), ptr(row), st)
     res = (seg, score, key, row) if out is None else (seg, score, key, row, off[R])
@@ -86,7 +69,7 @@ def candidates(verb_logits, noun_logits, verb_reg, noun_reg, window_start, windo
     return res
 
 
-class TwoStreamCollector:
+class TwoStreamCollector(CandidateCollector):
     """Collects the fused (verb, noun) detection candidates of two streams over an evaluation and turns them into detections.
 
         col = TwoStreamCollector(num_verbs=97, num_nouns=300, score_threshold=0.03, verb_alpha=0.65, top_k=1)
@@ -114,19 +97,14 @@ class TwoStreamCollector:
         self.num_classes = self.num_verbs * self.num_nouns          # of the fused label verb * num_nouns + noun
         self.reset()
 
-    def reset(self):
-        self.video_ids = []          # dense index -> video id, in first-seen order
-        self._index = {}
-        self._chunks = []            # per batch (seg, score, key) on the device
-
     def update(self, verb_output, noun_output, query_times, metadata):
         streams = []
         for name, output, head, ncls in (("verb", verb_output, self.verb_head, self.num_verbs),
                                          ("noun", noun_output, self.noun_head, self.num_nouns)):
             cls_slot, reg_slot = HEADS[head]
             logits, reg = output[0][cls_slot], output[1][reg_slot]
-            _on_gpu(logits, "%s_output[0][%d]" % (name, cls_slot))
-            _on_gpu(reg, "%s_output[1][%d]" % (name, reg_slot))
+            require_gpu(logits, _WHO, "%s_output[0][%d]" % (name, cls_slot))
+            require_gpu(reg, _WHO, "%s_output[1][%d]" % (name, reg_slot))
             if logits.dim() != 2 or logits.shape[1] != ncls:
                 raise ValueError("the %s stream has %d classes, got logits of shape %s" % (name, ncls, tuple(logits.shape)))
             streams.append((logits, reg, reg_slot))
@@ -134,43 +112,20 @@ class TwoStreamCollector:
         if slot_v != slot_n:
             raise ValueError("the %s and %s heads regress different queries" % (self.verb_head, self.noun_head))
         qt = query_times[slot_v]
-        _on_gpu(qt, "query_times[%d]" % slot_v)
+        require_gpu(qt, _WHO, "query_times[%d]" % slot_v)
         vids = list(metadata["video_id"])
         B, R = len(vids), vl.shape[0]
         if nl.shape[0] != R:
             raise ValueError("the verb stream has %d proposal rows, the noun stream %d" % (R, nl.shape[0]))
         if B == 0 or R % B != 0 or vr.shape[0] != R or nr.shape[0] != R:
             raise ValueError("%d proposal rows do not divide into %d windows" % (R, B))
-        idx = np.empty(B, dtype=np.int32)
-        for i, v in enumerate(vids):
-            v = str(v)
-            j = self._index.get(v)
-            if j is None:
-                j = self._index[v] = len(self.video_ids)
-                self.video_ids.append(v)
-            idx[i] = j
-        starts = torch.as_tensor(metadata["window_start"]).detach().to(torch.float64).reshape(-1)
-        if starts.numel() != B:
-            raise ValueError("metadata['window_start'] holds %d values for %d windows" % (starts.numel(), B))
-        window_size = float(torch.as_tensor(metadata["window_size"]).reshape(-1)[0])
+        idx = self._video_index(vids)
+        starts, window_size = self._windows(metadata, B)
         dev = vl.device
-        max_time = qt.detach().to(torch.float32).max()       # stays on the device
-        seg, score, key, _ = candidates(vl.detach(), nl.detach(), vr.detach(), nr.detach(), starts.to(dev), window_size, max_time,
-                                        torch.from_numpy(idx).to(dev), R // B, self.score_threshold, self.verb_alpha, self.top_k)
-        if score.shape[0]:
-            self._chunks.append((seg, score, key))
-
-    def candidates(self):
-        """everything collected so far: (seg [N, 2], score [N], key [N]) in collection order"""
-        if not self._chunks:
-            if not torch.cuda.is_available():
-                raise L.TimHipError("TwoStreamCollector runs on the MI355X HIP kernels only (no CPU fallback)")
-            dev = torch.device("cuda")
-            return (torch.zeros((0, 2), dtype=torch.float32, device=dev), torch.zeros((0,), dtype=torch.float32, device=dev),
-                    torch.zeros((0,), dtype=torch.int64, device=dev))
-        if len(self._chunks) > 1:                            # concatenate once, and keep the result as the one chunk
-            self._chunks = [tuple(torch.cat([c[i] for c in self._chunks]) for i in range(3))]
-        return self._chunks[0]
+        seg, score, key, _ = candidates(vl.detach(), nl.detach(), vr.detach(), nr.detach(), starts.to(dev), window_size,
+                                        self._max_time(qt), torch.from_numpy(idx).to(dev), R // B, self.score_threshold,
+                                        self.verb_alpha, self.top_k)
+        self._keep(seg, score, key)
 
     def detections(self, sigma=0.25, iou_threshold=0.1, min_score=0.001, method=2, nms="soft", task="action"):
         """-> (segs [M, 2] fp32, scores [M] fp32, labels [M] int64, video [M] int64 index into `video_ids`), ordered by
@@ -178,17 +133,12 @@ class TwoStreamCollector:
         is verb * num_nouns + noun for task "action", the verb for "verb", the noun for "noun" (the same detections)."""
         if task not in TASKS:
             raise ValueError("task must be one of %s" % (TASKS,))
-        seg, score, key = self.candidates()
-        s, c, k = grouped_nms(seg, score, key, iou_threshold, min_score, sigma, method, nms)
-        video = torch.div(k, self.num_classes, rounding_mode="floor")
-        labels = k - video * self.num_classes
+        s, c, labels, video = self._detections(iou_threshold, min_score, sigma, method, nms)
         if task == "verb":
             labels = torch.div(labels, self.num_nouns, rounding_mode="floor")
         elif task == "noun":
             labels = labels % self.num_nouns
-        o = torch.argsort(-c, stable=True)
-        o = o[torch.argsort(video[o], stable=True)]
-        return s[o], c[o], labels[o], video[o]
+        return s, c, labels, video
 
     def results(self, **nms_args):
         """the `results` dict of the reference's submission (format_two_stream_predictions_epic.py): the videos that had at

@@ -22,7 +22,6 @@ valid rows once and writes 13 bytes per row; emit reads them again and writes 24
 """
 import argparse
 import os
-import statistics
 import sys
 import time
 
@@ -32,6 +31,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tim_amd import DetectionCollector  # noqa: E402
 from tim_amd import detect as hd  # noqa: E402
+from tools._timing import host_timed, synthetic_windows, timed  # noqa: E402
 
 B, NQ = 16, 399
 R = B * NQ
@@ -41,30 +41,8 @@ WS, THR = 30.0, 0.01
 def make(C, seed, dev):
     g = torch.Generator(device="cpu").manual_seed(seed)
     logits = torch.randn(R, C, generator=g) * 1.5 - 7.0                 # ~ 5 % of the scores above 0.01
-    centre, half = torch.rand(NQ, generator=g) * 0.85 + 0.05, torch.rand(NQ, generator=g) * 0.07 + 0.01
-    q = torch.stack([centre - half, centre + half], 1).clamp(0, 0.98)
-    reg = q.repeat(B, 1) + 0.01 * torch.randn(R, 2, generator=g)
-    starts = torch.arange(B, dtype=torch.float64) * 7.5 + 0.000123
-    return dict(logits=logits.to(dev), reg=reg.to(dev), q=q.to(dev), starts=starts.to(dev),
-                vidx=(torch.arange(B, dtype=torch.int32) // 4).to(dev))
-
-
-def timed(fn, reps, inner, rotate=1):
-    """median / min / max microseconds per call over `reps` windows of `inner` calls (device events)"""
-    for i in range(3):
-        fn(i % rotate)
-    torch.cuda.synchronize()
-    out, k = [], 0
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(inner):
-            fn(k % rotate)
-            k += 1
-        e1.record()
-        e1.synchronize()
-        out.append(e0.elapsed_time(e1) * 1e3 / inner)
-    return statistics.median(out), min(out), max(out)
+    q, (reg,), starts, vidx = synthetic_windows(g, B, NQ)
+    return dict(logits=logits.to(dev), reg=reg.to(dev), q=q.to(dev), starts=starts.to(dev), vidx=vidx.to(dev))
 
 
 def torch_form(d, mt, C):
@@ -124,7 +102,7 @@ def main(argv=None):
         print("  bytes a call must move: count %.1f MB read + %.2f MB written; emit %.1f MB read + %.2f MB written"
               % (logit_bytes / 1e6, R * 13 / 1e6, logit_bytes / 1e6, n * 24 / 1e6))
 
-        def hip_pair(i):
+        def hip_pair(i=0):
             s = sets[i]
             hd.candidates(s["logits"], s["reg"], s["starts"], WS, mt, s["vidx"], NQ, THR, out=out)
 
@@ -132,14 +110,14 @@ def main(argv=None):
         meta = {"video_id": ["v%d" % (i // 4) for i in range(B)], "window_start": d["starts"].cpu(),
                 "window_size": torch.tensor([WS] * B, dtype=torch.float64)}
 
-        def hip_update(i):
+        def hip_update(i=0):
             s = sets[i]
             col.reset()
             col.update((None, None, s["logits"], None), (s["reg"], None), (s["q"], None), meta)
 
         rows = [("hip  count + emit (3 launches), warm", hip_pair, 1), ("hip  count + emit (3 launches), cold", hip_pair, nbuf),
                 ("hip  DetectionCollector.update, warm", hip_update, 1),
-                ("torch ops on the device, warm", lambda i: torch_form(sets[i], mt, C), 1),
+                ("torch ops on the device, warm", lambda i=0: torch_form(sets[i], mt, C), 1),
                 ("torch ops on the device, cold", lambda i: torch_form(sets[i], mt, C), nbuf)]
         for name, fn, rot in rows:
             med, lo, hi = timed(fn, args.reps, args.inner, rot)
@@ -150,14 +128,10 @@ def main(argv=None):
                                                               ", still cache-resident" if rot * logit_bytes < (256 << 20) else "") if rot > 1 else ""
             print("  %-40s %10.1f (%.1f - %.1f)%s%s" % (name, med, lo, hi, extra, note))
         hr = min(args.host_rows, R)
-        ts = []
-        for _ in range(3):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            e = host_form(d, mt, hr)
-            ts.append((time.perf_counter() - t0) * 1e6)
+        entries = []
+        med, lo, hi = host_timed(lambda: entries.append(len(host_form(d, mt, hr))), runs=3)
         print("  %-40s %10.1f (%.1f - %.1f)   host clock, %d of %d proposals, %d entries, 3 runs"
-              % ("host form (dense copy + Python loop)", statistics.median(ts), min(ts), max(ts), hr, R, len(e)))
+              % ("host form (dense copy + Python loop)", med, lo, hi, hr, R, entries[-1]))
         del sets, out
         torch.cuda.empty_cache()
 
@@ -175,17 +149,12 @@ def main(argv=None):
     torch.cuda.synchronize()
     t1 = time.perf_counter()
     ncand = int(col.candidates()[1].numel())
-    ts = []
-    for _ in range(3):
-        torch.cuda.synchronize()
-        t2 = time.perf_counter()
-        dets = col.detections(sigma=0.1)
-        torch.cuda.synchronize()
-        ts.append((time.perf_counter() - t2) * 1e3)
+    dets = []
+    med, lo, hi = (t / 1e3 for t in host_timed(lambda: dets.append(col.detections(sigma=0.1)), runs=3))
     print("\nstream of %d batches (C = %d, %d videos): update %.1f us per batch (host clock, synchronised at the end); %d candidates; "
           "detections() %.1f ms (min %.1f, max %.1f; host clock, 3 runs, the first includes the one concatenation) -> %d detections"
-          % (args.stream, C, len(col.video_ids), (t1 - t0) * 1e6 / args.stream, ncand, statistics.median(ts), min(ts), max(ts),
-             int(dets[1].numel())))
+          % (args.stream, C, len(col.video_ids), (t1 - t0) * 1e6 / args.stream, ncand, med, lo, hi,
+             int(dets[-1][1].numel())))
 
 
 if __name__ == "__main__":

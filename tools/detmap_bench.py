@@ -15,7 +15,6 @@ it is printed as what it is.
 """
 import argparse
 import os
-import statistics
 import sys
 import time
 
@@ -26,6 +25,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tests import detmap_ref as R  # noqa: E402
 from tim_amd import DetectionScorer  # noqa: E402
 from tim_amd import _lib as L  # noqa: E402
+from tools._timing import timed  # noqa: E402
 
 CLASSES, VIDEOS = 3806, 138
 
@@ -51,18 +51,6 @@ def make_problem(n_gt, n_det, seed=0):
     return ([names[v] for v in g_video], g_seg, g_label), (seg.astype(np.float32), score, label.astype(np.int64), video.astype(np.int64)), names
 
 
-def timed(fn, reps):
-    ms = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return statistics.median(ms), min(ms), max(ms)
-
-
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
@@ -76,7 +64,8 @@ def main(argv=None):
     d = [torch.from_numpy(x).to(dev) for x in (seg, score, label, video)]
     mAP, avg = sc.evaluate(*d, names)                                     # warm-up (library load, allocator, sort temporaries)
     sc.evaluate(*d, names)
-    med, lo, hi = timed(lambda: sc.evaluate(*d, names), args.reps)
+    ms = lambda fn: tuple(t / 1e3 for t in timed(fn, args.reps, 1))       # one call per window, milliseconds
+    med, lo, hi = ms(lambda: sc.evaluate(*d, names))
     groups = sc._host["gt_off"].shape[0] - 1
     print("%d detections, %d ground-truth segments in %d (class, video) groups of up to %d, %d classes; mAP %s avg %.4f"
           % (args.detections, args.segments, groups, int(np.diff(sc._host["gt_off"]).max()), sc.classes.shape[0],
@@ -114,8 +103,8 @@ def main(argv=None):
     match()
     avp()
     assert torch.equal(apd, sc.ap)
-    print("hip   timhip_det_match (+ the two fills): median %.3f ms (%.3f - %.3f)" % timed(match, args.reps))
-    print("hip   timhip_det_ap: median %.3f ms (%.3f - %.3f)" % timed(avp, args.reps))
+    print("hip   timhip_det_match (+ the two fills): median %.3f ms (%.3f - %.3f)" % ms(match))
+    print("hip   timhip_det_ap: median %.3f ms (%.3f - %.3f)" % ms(avp))
 
     if not args.no_host:
         sub = np.arange(0, args.detections, 100)

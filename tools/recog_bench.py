@@ -21,15 +21,14 @@ once, the accumulator chunk of every distinct id read once and written once.
 """
 import argparse
 import os
-import statistics
 import sys
-import time
 
 import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tim_amd import RecognitionCollector  # noqa: E402
+from tools._timing import captured, host_timed, timed  # noqa: E402
 
 CLASSES = {"verb": 97, "noun": 300, "action": 3806, "audio": 44}
 NUM_CLASS = [[97, 300, 3806], 44]
@@ -54,47 +53,6 @@ def make_batch(windows, n_act, seed, dev):
     g = torch.Generator(device="cpu").manual_seed(seed)
     out["logits"] = tuple((torch.randn(windows * (NV if h != "audio" else NA), CLASSES[h], generator=g) * 3.0).to(dev) for h in HEADS)
     return out
-
-
-def timed(fn, reps, inner):
-    """median / min / max microseconds per call over `reps` windows of `inner` calls (device events)"""
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(inner):
-            fn()
-        e1.record()
-        e1.synchronize()
-        out.append(e0.elapsed_time(e1) * 1e3 / inner)
-    return statistics.median(out), min(out), max(out)
-
-
-def host_timed(fn, runs=5):
-    ts = []
-    for _ in range(runs):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        ts.append((time.perf_counter() - t0) * 1e6)
-    return statistics.median(ts), min(ts), max(ts)
-
-
-def captured(fn):
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        fn()
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        fn()
-    return graph
 
 
 class TorchState:

@@ -20,7 +20,6 @@ Method: every timed callable is warmed up, then timed --reps times with device e
 """
 import argparse
 import os
-import statistics
 import sys
 import time
 
@@ -30,6 +29,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tim_amd import TwoStreamCollector  # noqa: E402
 from tim_amd import twostream as ts  # noqa: E402
+from tools._timing import captured, host_timed, synthetic_windows, timed  # noqa: E402
 
 B, NQ, CV, CN = 16, 399, 97, 300
 R = B * NQ
@@ -40,30 +40,8 @@ def make(seed, dev):
     g = torch.Generator(device="cpu").manual_seed(seed)
     vl = torch.randn(R, CV, generator=g) * 1.5 - 7.0                    # the best verb of a row passes 0.03 about half the time
     nl = torch.randn(R, CN, generator=g) * 1.5 - 7.6
-    centre, half = torch.rand(NQ, generator=g) * 0.85 + 0.05, torch.rand(NQ, generator=g) * 0.07 + 0.01
-    q = torch.stack([centre - half, centre + half], 1).clamp(0, 0.98)
-    vr = q.repeat(B, 1) + 0.01 * torch.randn(R, 2, generator=g)
-    nr = q.repeat(B, 1) + 0.01 * torch.randn(R, 2, generator=g)
-    starts = torch.arange(B, dtype=torch.float64) * 7.5 + 0.000123
-    return dict(vl=vl.to(dev), nl=nl.to(dev), vr=vr.to(dev), nr=nr.to(dev), q=q.to(dev), starts=starts.to(dev),
-                vidx=(torch.arange(B, dtype=torch.int32) // 4).to(dev))
-
-
-def timed(fn, reps, inner):
-    """median / min / max microseconds per call over `reps` windows of `inner` calls (device events)"""
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(inner):
-            fn()
-        e1.record()
-        e1.synchronize()
-        out.append(e0.elapsed_time(e1) * 1e3 / inner)
-    return statistics.median(out), min(out), max(out)
+    q, (vr, nr), starts, vidx = synthetic_windows(g, B, NQ, streams=2)
+    return dict(vl=vl.to(dev), nl=nl.to(dev), vr=vr.to(dev), nr=nr.to(dev), q=q.to(dev), starts=starts.to(dev), vidx=vidx.to(dev))
 
 
 def torch_form(d, mt, k):
@@ -138,15 +116,7 @@ def main(argv=None):
         def hip_pair():
             ts.candidates(d["vl"], d["nl"], d["vr"], d["nr"], d["starts"], WS, mt, d["vidx"], NQ, THR, ALPHA, k, out=out)
 
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            hip_pair()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            hip_pair()
+        graph = captured(hip_pair)
 
         col = TwoStreamCollector(CV, CN, THR, ALPHA, k)
         meta = {"video_id": ["v%d" % (i // 4) for i in range(B)], "window_start": d["starts"].cpu(),
@@ -164,14 +134,10 @@ def main(argv=None):
             extra = "   %.0f GB/s of the %.1f MB read once" % (logit_bytes / med / 1e3, logit_bytes / 1e6) if "graph" in name else ""
             print("  %-42s %10.1f (%.1f - %.1f)%s" % (name, med, lo, hi, extra))
         hr = min(args.host_rows, R)
-        tt = []
-        for _ in range(3):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            e = host_form(d, mt, k, hr)
-            tt.append((time.perf_counter() - t0) * 1e6)
+        entries = []
+        med, lo, hi = host_timed(lambda: entries.append(len(host_form(d, mt, k, hr))), runs=3)
         print("  %-42s %10.1f (%.1f - %.1f)   host clock, %d of %d proposals, %d entries, 3 runs"
-              % ("host form (dense copies + Python loop)", statistics.median(tt), min(tt), max(tt), hr, R, len(e)))
+              % ("host form (dense copies + Python loop)", med, lo, hi, hr, R, entries[-1]))
         del graph, out
 
     # ---- a stream of batches, then detections()
@@ -187,18 +153,13 @@ def main(argv=None):
     torch.cuda.synchronize()
     t1 = time.perf_counter()
     ncand = int(col.candidates()[1].numel())
-    tt = []
-    for _ in range(3):
-        torch.cuda.synchronize()
-        t2 = time.perf_counter()
-        dets = col.detections(sigma=0.25)
-        torch.cuda.synchronize()
-        tt.append((time.perf_counter() - t2) * 1e3)
+    dets = []
+    med, lo, hi = (t / 1e3 for t in host_timed(lambda: dets.append(col.detections(sigma=0.25)), runs=3))
     print("\nstream of %d batches (top_k 1, %d videos): update %.1f us per batch = %.0f windows/s (host clock, synchronised at the "
           "end); %d candidates; detections() %.1f ms (min %.1f, max %.1f; host clock, 3 runs, the first includes the one "
           "concatenation) -> %d detections"
           % (args.stream, len(col.video_ids), (t1 - t0) * 1e6 / args.stream, B * args.stream / (t1 - t0), ncand,
-             statistics.median(tt), min(tt), max(tt), int(dets[1].numel())))
+             med, lo, hi, int(dets[-1][1].numel())))
 
 
 if __name__ == "__main__":
