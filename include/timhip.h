@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define TIMHIP_VERSION 6   /* 6, additive (no layout or signature change, so no new number): timhip_rec_{accumulate,finalize,counts}, timhip_det_candidates_{count,emit}, timhip_stack_infer, timhip_stack_infer_workspace_bytes, timhip_attention_fwd_rows, TIMHIP_EPI_GELU_T, lse = NULL in timhip_attention_fwd; 6 (round 6): timhip_timing_stop_families; 5 (round 5): timhip_assemble_{fwd,bwd}_p (token / modality vectors by pointer), timhip_dx_init_slabs, timhip_det_side_loss_{fwd,bwd}, timhip_sigmoid_bwd_rows, timhip_time_l1_fwd_split3, timhip_gather_split3_ranges, TIMHIP_EPI_RELU_SPLIT3_T, timhip_layernorm_{fwd,bwd}2, timhip_cast_rows_pair; 4 (round 4): 8-word timhip_grad_scale block + non-finite flag, TIMHIP_DESC_STREAM16*, timhip_dx_init, timhip_reload_env */
+#define TIMHIP_VERSION 6   /* 6, additive (no layout or signature change, so no new number): timhip_attention_weights, timhip_stack_infer_maps, timhip_stack_infer_maps_workspace_bytes, timhip_rec_{accumulate,finalize,counts}, timhip_det_candidates_{count,emit}, timhip_stack_infer, timhip_stack_infer_workspace_bytes, timhip_attention_fwd_rows, TIMHIP_EPI_GELU_T, lse = NULL in timhip_attention_fwd; 6 (round 6): timhip_timing_stop_families; 5 (round 5): timhip_assemble_{fwd,bwd}_p (token / modality vectors by pointer), timhip_dx_init_slabs, timhip_det_side_loss_{fwd,bwd}, timhip_sigmoid_bwd_rows, timhip_time_l1_fwd_split3, timhip_gather_split3_ranges, TIMHIP_EPI_RELU_SPLIT3_T, timhip_layernorm_{fwd,bwd}2, timhip_cast_rows_pair; 4 (round 4): 8-word timhip_grad_scale block + non-finite flag, TIMHIP_DESC_STREAM16*, timhip_dx_init, timhip_reload_env */
 
 enum {
   TIMHIP_OK = 0,
@@ -382,6 +382,19 @@ int timhip_attention_fwd(const TimDesc* d, const void* qkv, void* o, float* lse,
  * bit for bit; 32-row blocks that lie wholly below s0 are not run.  With s0 = F: the query rows, all the last layer of an
  * evaluation forward needs once nobody reads `feats` (timhip_stack_infer, tail_only). */
 int timhip_attention_fwd_rows(const TimDesc* d, const void* qkv, int s0, void* o_rows, void* stream);
+/* The attention WEIGHTS of those rows - what the reference's TransformerEncoder.forward returns beside its output (transformers.py:
+ * 45-48: nn.MultiheadAttention's head-averaged softmax weights) and the kernels above keep in registers.  A token attends to the F
+ * feature tokens and to itself, so a row has F + 1 entries: w[b * (S - s0) + (s - s0), j] (fp32, row pitch ld >= F + 1 floats;
+ * columns past F are not written) = the mean over the heads, in ascending head order, of softmax_j(scale q[b,h,s] . k[b,h,key(j)]),
+ * key(j) = j for j < F; column F = the token's own key for query rows (s >= F) and exact 0.0f for feature rows, whose own key is
+ * one of the F.  per_head != 0: no mean, w is [B, H, S - s0, ld].  Keys come from the full qkv (the matrix timhip_attention_fwd
+ * reads); the softmax is computed here, no lse is read.  No dropout: d->p_drop must be 0 (the reference's weights under dropout
+ * are a mask, not a map).  A row's arithmetic depends on neither B nor s0: the same window gives the same bits alone or in any
+ * batch, on every run (no atomics).  16-bit precisions run Q K^T on the matrix cores for the shapes timhip_attention_fwd does;
+ * every other shape, the fp32-storage modes and TIMHIP_DESC_ATTN_FP32 run one fp32-arithmetic kernel (F <= 192, else
+ * TIMHIP_EUNSUPPORTED).  Checked before any launch: NULL d / qkv / w, a bad descriptor, p_drop != 0, s0 outside [0, S),
+ * ld < F + 1 - TIMHIP_EINVAL; w not float-aligned (qkv not element-aligned) - TIMHIP_EALIGN. */
+int timhip_attention_weights(const TimDesc* d, const void* qkv, int s0, int per_head, float* w, int ld, void* stream);
 /* ABI 6: keep-bits of the attention dropout of `nlayers` encoder layers in ONE launch, written into the layers' saved blocks
  * (saved[l] = the block timhip_layer_fwd of layer l will fill; field TIMHIP_SAVED_ATTN_KEEP_BITS: per (window, head, token row)
  * two 64-bit words, word g bit 4 c + t = key 8 c + 4 g + t kept, keys 0 .. 127 - the order in which the MFMA attention
@@ -487,6 +500,18 @@ int timhip_layer_fwd_chained(const TimDesc* d, const TimLayerParams* w, const Ti
 size_t timhip_stack_infer_workspace_bytes(const TimDesc* d, int nlayers, int tail_only);
 int timhip_stack_infer(const TimDesc* d, int nlayers, const TimLayerParams* layers, const float* x_in, const void* x_in_T,
                        float* x_out, void* x_out_T, int tail_only, void* workspace, size_t workspace_bytes, void* stream);
+/* timhip_stack_infer that also writes attention maps: behind layer l's launches, while that layer's qkv is live in the arena,
+ * timhip_attention_weights (mean over heads, rows maps_s0 .. S - 1, row pitch ld) into maps[l].  maps: a HOST array of nlayers
+ * device pointers, read during the call only; NULL entries are skipped.  With tail_only = 1 the last layer still computes qkv on
+ * all rows, so maps_s0 = F (the query rows) and maps_s0 = 0 both work there.  The arena is timhip_stack_infer's, whatever
+ * the number of maps: the maps are the caller's buffers.  x_out / x_out_T are timhip_stack_infer's bit for bit (the same launches
+ * in the same order; the weights kernels only read).  Launches only, one stream, no events, no host reads of device memory:
+ * capturable as a linear graph.  maps == NULL, maps_s0 outside [0, S), ld < F + 1: TIMHIP_EINVAL; a map that is not float-aligned:
+ * TIMHIP_EALIGN - all before the first launch. */
+size_t timhip_stack_infer_maps_workspace_bytes(const TimDesc* d, int nlayers, int tail_only);
+int timhip_stack_infer_maps(const TimDesc* d, int nlayers, const TimLayerParams* layers, const float* x_in, const void* x_in_T,
+                            float* x_out, void* x_out_T, int tail_only, float* const* maps, int maps_s0, int ld,
+                            void* workspace, size_t workspace_bytes, void* stream);
 /* dx_out: gradient w.r.t. the layer output (fp32 [M,E]).  dx_in: gradient w.r.t. the
  * layer input (fp32 [M,E]).  Parameter gradients are accumulated (+=) into *g.
  * This is timhip_layer_bwd_split (below: the form tim_amd calls) with dx_out_add = dx_in_add = NULL. */

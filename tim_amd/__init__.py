@@ -31,6 +31,9 @@ def __getattr__(name):  # lazy: importing the package must not require torch on 
     if name == "RecognitionCollector":
         from .recog import RecognitionCollector
         return RecognitionCollector
+    if name == "AttentionMaps":
+        from .attn_maps import AttentionMaps
+        return AttentionMaps
     if name == "optim":
         import importlib
         return importlib.import_module(".optim", __name__)

@@ -132,6 +132,7 @@ _SIGS = {
                                        f32, u64, u32, vp, vp, vp, vp]),
     "timhip_attention_fwd": (C.c_int, [C.POINTER(TimDesc), vp, vp, vp, vp]),
     "timhip_attention_fwd_rows": (C.c_int, [C.POINTER(TimDesc), vp, i32, vp, vp]),
+    "timhip_attention_weights": (C.c_int, [C.POINTER(TimDesc), vp, i32, i32, vp, i32, vp]),
     "timhip_attention_bwd": (C.c_int, [C.POINTER(TimDesc), vp, vp, vp, vp, vp, vp, sz, vp]),
     "timhip_attention_bwd_workspace_bytes": (sz, [C.POINTER(TimDesc)]),
     "timhip_time_l1_fwd": (C.c_int, [i32, vp, i32, i32, vp, vp, vp, i32, vp]),
@@ -144,6 +145,9 @@ _SIGS = {
                                            vp, vp, vp]),
     "timhip_stack_infer_workspace_bytes": (sz, [C.POINTER(TimDesc), i32, i32]),
     "timhip_stack_infer": (C.c_int, [C.POINTER(TimDesc), i32, C.POINTER(TimLayerParams), vp, vp, vp, vp, i32, vp, sz, vp]),
+    "timhip_stack_infer_maps_workspace_bytes": (sz, [C.POINTER(TimDesc), i32, i32]),
+    "timhip_stack_infer_maps": (C.c_int, [C.POINTER(TimDesc), i32, C.POINTER(TimLayerParams), vp, vp, vp, vp, i32, C.POINTER(vp), i32,
+                                          i32, vp, sz, vp]),
     "timhip_layer_bwd": (C.c_int, [C.POINTER(TimDesc), C.POINTER(TimLayerParams), vp, vp, vp, vp,
                                    C.POINTER(TimLayerGrads), vp, sz, vp]),
     "timhip_layer_bwd_split": (C.c_int, [C.POINTER(TimDesc), C.POINTER(TimLayerParams), vp, vp, vp, vp, vp, vp,

@@ -485,13 +485,22 @@ size_t timhip_stack_infer_workspace_bytes(const TimDesc* d, int nlayers, int tai
   return (d && check_layer_desc(*d) == TIMHIP_OK) ? infer_layout(*d, tail_only).total : 0;
 }
 
-int timhip_stack_infer(const TimDesc* dp, int nlayers, const TimLayerParams* layers, const float* x_in, const void* x_in_T,
-                       float* x_out, void* x_out_T, int tail_only, void* workspace, size_t workspace_bytes, void* stream) {
+// The one body of timhip_stack_infer and timhip_stack_infer_maps.  maps (HOST array of nlayers device pointers, or NULL): behind
+// layer l's launches - its qkv is live in the arena until layer l + 1's in-projection - the weights kernel writes maps[l].
+static int stack_infer_body(const TimDesc* dp, int nlayers, const TimLayerParams* layers, const float* x_in, const void* x_in_T,
+                            float* x_out, void* x_out_T, int tail_only, float* const* maps, int maps_s0, int ld,
+                            void* workspace, size_t workspace_bytes, void* stream) {
   if (!dp || !layers || nlayers <= 0 || !x_in || !x_in_T || !x_out_T || !workspace) return TIMHIP_EINVAL;
   TimDesc d = *dp;
   int rc = check_layer_desc(d);
   if (rc) return rc;
   if (d.p_drop != 0.f || (tail_only && d.S == d.F)) return TIMHIP_EINVAL;
+  if (maps) {   // refused before the first launch, like everything above
+    if (maps_s0 < 0 || maps_s0 >= d.S || ld < d.F + 1) return TIMHIP_EINVAL;
+    if (d.F > 192) return TIMHIP_EUNSUPPORTED;
+    for (int l = 0; l < nlayers; ++l)
+      if (((uintptr_t)maps[l] & 3) != 0) return TIMHIP_EALIGN;
+  }
   const InferLayout L = infer_layout(d, tail_only);
   if (workspace_bytes < L.total) return TIMHIP_EWORKSPACE;
   hipStream_t s = (hipStream_t)stream;
@@ -516,8 +525,28 @@ int timhip_stack_infer(const TimDesc* dp, int nlayers, const TimLayerParams* lay
     const void* in_T = l == 0 ? x_in_T : (const void*)L.xt.at(ws);
     if ((rc = layer_fwd_body(d, &layers[l], res, pre, pst, l ? layers[l - 1].n2_w : nullptr, l ? layers[l - 1].n2_b : nullptr, in_T,
                              last ? x_out : nullptr, last ? x_out_T : (void*)L.xt.at(ws), bufs, s0, s))) return rc;
+    if (maps && maps[l] && (rc = tim_attention_weights(d, bufs.qkv, maps_s0, 0, maps[l], ld, s))) return rc;
   }
   return TIMHIP_OK;
+}
+
+int timhip_stack_infer(const TimDesc* dp, int nlayers, const TimLayerParams* layers, const float* x_in, const void* x_in_T,
+                       float* x_out, void* x_out_T, int tail_only, void* workspace, size_t workspace_bytes, void* stream) {
+  return stack_infer_body(dp, nlayers, layers, x_in, x_in_T, x_out, x_out_T, tail_only, nullptr, 0, 0, workspace, workspace_bytes,
+                          stream);
+}
+
+// (the maps are the caller's buffers: the arena is timhip_stack_infer's)
+size_t timhip_stack_infer_maps_workspace_bytes(const TimDesc* d, int nlayers, int tail_only) {
+  return timhip_stack_infer_workspace_bytes(d, nlayers, tail_only);
+}
+
+int timhip_stack_infer_maps(const TimDesc* dp, int nlayers, const TimLayerParams* layers, const float* x_in, const void* x_in_T,
+                            float* x_out, void* x_out_T, int tail_only, float* const* maps, int maps_s0, int ld,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+  if (!maps) return TIMHIP_EINVAL;
+  return stack_infer_body(dp, nlayers, layers, x_in, x_in_T, x_out, x_out_T, tail_only, maps, maps_s0, ld, workspace,
+                          workspace_bytes, stream);
 }
 
 size_t timhip_layer_ln_partial_bytes(const TimDesc* d) { return d ? 2 * tim_layernorm_bwd_ws(d->B * d->S, d->E) : 0; }

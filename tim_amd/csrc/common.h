@@ -496,6 +496,8 @@ int tim_attention_bwd(const TimDesc& d, const void* qkv, const void* o, const fl
 // attention_mfma.hip: keep-bits of layers first .. first + n - 1 (n <= 8) into out[i]: [B * H * S][2] 64-bit words
 int tim_attn_keep_bits(const TimDesc& d, int first_layer, int n, unsigned long long* const* out, hipStream_t s);
 size_t tim_attention_bwd_ws(const TimDesc& d);
+// attn_maps.hip: the head-averaged (per_head: per-head) softmax weights of the rows s0 .. S - 1, [.., S - s0, ld] fp32
+int tim_attention_weights(const TimDesc& d, const void* qkv, int s0, int per_head, float* w, int ld, hipStream_t s);
 
 // operand storage: bf16 for TIMHIP_PREC_BF16, fp16 for TIMHIP_PREC_F16, fp32 for TIMHIP_PREC_FP32 and TIMHIP_PREC_BF16X3
 static inline bool h16_storage(int precision) { return precision == TIMHIP_PREC_BF16 || precision == TIMHIP_PREC_F16; }

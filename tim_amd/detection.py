@@ -106,7 +106,7 @@ class TIM(_TIMBase):
         return query_targets, self.assign_positive_labels(modality, query_labels), query_ious
 
     # ---- tim.py:272-400
-    def _run(self, inputs, feature_times, target, train, label_queries):
+    def _run(self, inputs, feature_times, target, train, label_queries, maps=None):
         v_offsets = a_offsets = torch.empty(0, 2)
         v_labels = a_labels = torch.empty(0, 4)
         num_v = num_a = 0
@@ -150,7 +150,7 @@ class TIM(_TIMBase):
             a_queries = torch.flatten(a_queries, 0, 1)
 
         time_encodings = self._time_mlp(all_times)
-        outs = encoder(self, num_v, num_a, inputs[0], inputs[1], time_encodings)
+        outs = encoder(self, num_v, num_a, inputs[0], inputs[1], time_encodings, maps)
         o = dict(zip(OUT_SLOTS, outs))
         cls_scores = (o["verb"], o["noun"], o["action"], o["audio"])
         reg_scores = (o["reg_visual"], o["reg_audio"])
@@ -162,6 +162,18 @@ class TIM(_TIMBase):
 
     def forward_inference(self, inputs, feature_times, target, label_queries=False):
         return self._run(inputs, feature_times, target, False, label_queries)
+
+    def attention_maps(self, inputs, feature_times, target=None, label_queries=False, layers="last", rows="queries", out=None):
+        """-> (outputs, maps): `outputs` is what `self(inputs, "encoder", feature_times, target, label_queries)` returns under
+        `eval()` / `no_grad()` (forward_inference, its own query pyramid), bit for bit; `maps` the attention weights of the
+        layers asked for, [B, S - s0, F + 1] - with rows="queries" one row per query of the pyramid (visual queries first,
+        then audio).  Arguments and conditions as the recognition model's `attention_maps`."""
+        from .attn_maps import MapRequest
+        req = MapRequest(self, layers, rows, out)
+        _require_gpu(feature_times, "attention_maps")
+        with torch.no_grad():
+            outputs = self._run(inputs, feature_times, target, False, label_queries, maps=req)
+        return outputs, req.result
 
     def forward_encoder(self, inputs, feature_times, target, label_queries=False):
         if self.training:

@@ -1294,12 +1294,14 @@ class EncoderFn(torch.autograd.Function):
 # ==================================================================================================
 # evaluation forward: the same stages, no backward to prepare for
 # ==================================================================================================
-def _infer_forward(model, nv, na, visual, audio, te):
+def _infer_forward(model, nv, na, visual, audio, te, maps=None):
     """The encoder under `model.eval()` and no-grad (validation, feature extraction): the stages of `EncoderFn.forward` with the
     layer stack as ONE library call out of one arena (timhip_stack_infer) - no saved blocks, no per-layer row buffers, no
     stores only a backward reads, no autograd node; a single-stream chain of launches (capturable as a linear graph).
     `model.eval_feats` (default True): every output is the training route's evaluation output bit for bit.  False: `feats`
-    is None and the last layer runs behind its in-projection on the query rows alone (tail_only); the heads read compact rows."""
+    is None and the last layer runs behind its in-projection on the query rows alone (tail_only); the heads read compact rows.
+    `maps` (an attn_maps.MapRequest: `model.attention_maps`): the same stack walk through timhip_stack_infer_maps, which also
+    writes the attention weights of the layers asked for; every output keeps its bits."""
     rt, cfg = model.rt, model.cfg
     _require_gpu(te, "encoder")
     B, T, d = te.shape
@@ -1320,17 +1322,23 @@ def _infer_forward(model, nv, na, visual, audio, te):
     xL_t = torch.empty((rows, q.E), dtype=rt.op_dtype, device=q.dev)
     ws_bytes = L.load().timhip_stack_infer_workspace_bytes(C.byref(desc), Lyr, int(tail))
     ws = model._workspace(ws_bytes, q.dev, slot="infer")
-    call("timhip_stack_infer", C.byref(desc), Lyr, layers, ptr(x0_f), ptr(x0_t), ptr(xL_f), ptr(xL_t), int(tail), ptr(ws), ws_bytes, q.st)
+    if maps is not None:
+        maps.run(model, q, desc, Lyr, layers, x0_f, x0_t, xL_f, xL_t, tail, ws, ws_bytes)
+    else:
+        call("timhip_stack_infer", C.byref(desc), Lyr, layers, ptr(x0_f), ptr(x0_t), ptr(xL_f), ptr(xL_t), int(tail), ptr(ws), ws_bytes, q.st)
     outs = {"feats": None if not model.eval_feats else xL_f.view(B, q.S, q.E)[:, :q.F]}
     _heads_fwd(q, P, xL_f, xL_t, outs, row0)
     _reg_heads_fwd(q, P, xL_t, outs, row0)
     return tuple(outs.get(k) for k in OUT_SLOTS)
 
 
-def encoder(model, nv, na, visual, audio, te):
+def encoder(model, nv, na, visual, audio, te, maps=None):
     """The encoder of one call -> the 7 outputs (OUT_SLOTS; None if absent).  `model.eval()` with gradients off takes the
     evaluation route (`_infer_forward`); everything else - training, or an evaluation somebody differentiates - the autograd
-    Function.  TIM_AMD_INFER=0: the Function everywhere (A/B switch)."""
+    Function.  TIM_AMD_INFER=0: the Function everywhere (A/B switch).  `maps` (`model.attention_maps`): the evaluation route,
+    whatever the switch says - only it computes them."""
+    if maps is not None:
+        return _infer_forward(model, nv, na, visual, audio, te, maps)
     if not model.training and not torch.is_grad_enabled() and os.environ.get("TIM_AMD_INFER", "1") != "0":
         return _infer_forward(model, nv, na, visual, audio, te)
     return EncoderFn.apply(model, nv, na, visual, audio, te, *model._encoder_param_list())

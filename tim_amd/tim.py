@@ -505,13 +505,32 @@ class TIM(nn.Module):
         return _GradBuckets(self.rt, names, params, dev, self._bucket_of, layer_overwrite, extra_zero, layout=lay)
 
     # ---- the reference's public interface ------------------------------------------------------------
-    def forward_encoder(self, inputs, time_encodings, num_v_queries, num_a_queries):
+    def forward_encoder(self, inputs, time_encodings, num_v_queries, num_a_queries, _maps=None):
         if self.pool is not None:
             self.pool.bind(self)      # (a deep copy or an unpickled model arrives here unbound)
             inputs = [self.pool(inputs[1], inputs[0]), inputs[1]]
-        outs = encoder(self, int(num_v_queries or 0), int(num_a_queries or 0), inputs[0], inputs[1], time_encodings)
+        outs = encoder(self, int(num_v_queries or 0), int(num_a_queries or 0), inputs[0], inputs[1], time_encodings, _maps)
         o = dict(zip(OUT_SLOTS, outs))
         return (o["verb"], o["noun"], o["action"], o["audio"]), o["feats"]
+
+    def attention_maps(self, inputs, time_encodings, num_v_queries=None, num_a_queries=None, layers="last", rows="queries",
+                       out=None):
+        """-> (outputs, maps): `outputs` is what `self(inputs, "encoder", time_encodings, num_v_queries, num_a_queries)` returns
+        under `eval()` / `no_grad()`, bit for bit (the same stack walk, `eval_feats` honoured); `maps` an
+        `attn_maps.AttentionMaps` with the attention weights [B, S - s0, F + 1] of the layers asked for - what the reference's
+        `TransformerEncoder.forward` returns as `attn_weights`, in the F + 1 columns TIM's mask leaves non-zero.
+        layers: "last", "all" or a list of layer indices (negative: from the end); rows: "queries" (the query tokens, s0 = F)
+        or "all".  Needs `eval()` (ValueError under `.train()`: the reference's weights are dropped-out there); runs under
+        no-grad on the evaluation route whatever TIM_AMD_INFER says.  out: an `AttentionMaps` of an earlier call with the same
+        arguments and batch (or its list of buffers) to write into - a call captured under `torch.cuda.graph` then keeps its
+        map buffers outside the graph's pool."""
+        from .attn_maps import MapRequest
+        from .functional import _require_gpu
+        req = MapRequest(self, layers, rows, out)
+        _require_gpu(time_encodings, "attention_maps")
+        with torch.no_grad():
+            outputs = self.forward_encoder(inputs, time_encodings, num_v_queries, num_a_queries, _maps=req)
+        return outputs, req.result
 
     def _time_mlp(self, times):
         m = self.time_mlp

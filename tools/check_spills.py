@@ -36,6 +36,9 @@ BUDGET = {
     "wgrad_pp.hip": [(r"wgrad_ld_kernel", 0), (r"wgrad_pp_kernel", 0), (r"wgrad_p8_kernel", 0)],
     "wgrad.hip": [(r"wgrad_group_kernel", 0), (r"wgrad_tn_kernel", 0)],
     "attention_mfma.hip": [(r"attn_fwd_mfma", 0)],
+    # the attention-weights kernels: the scores of a head and the running head mean both live in registers (202 VGPRs at head width
+    # 128, F = 100; 229 at five key blocks) - scratch traffic would sit inside the loop over the heads
+    "attn_maps.hip": [(r"attn_w_mfma", 0), (r"attn_w_generic", 0)],
     # the fp16 fused backward (C2a / C3 / C4), with the kernel's own draws and with the keep-bits of round 6
     "attention_bwd2.hip": [(r"attn_bwd_rowsIDF16_Li128ELi4ELb1E", 0), (r"attn_bwd_rowsIDF16[_b]Li128ELi4ELb1ELb1ELb1E", 0)],
     "rowops.hip": [(r"ln_fwd8", 0), (r"ln_bwd_kernel", 0)],
