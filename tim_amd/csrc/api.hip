@@ -3,6 +3,7 @@
 // allocation, no synchronisation, no retained state.
 #include <atomic>
 #include "common.h"
+#include "gemm_plan.h"
 
 namespace {
 
@@ -208,24 +209,24 @@ TimKnobs g_knobs;
 std::atomic<int> g_knobs_state{0};   // 0: not read, 1: valid
 int env_int(const char* name, int dflt) { const char* v = getenv(name); return (v && v[0]) ? atoi(v) : dflt; }
 void read_knobs(TimKnobs& k) {
-  k.gemm_pp = env_int("TIMHIP_GEMM_PP", 1); k.gemm_ld = env_int("TIMHIP_GEMM_LD", 1); k.gemm_pf = env_int("TIMHIP_GEMM_PF", 4);
-  k.gemm_pf_mode = env_int("TIMHIP_GEMM_PF_MODE", 1); k.gemm_pf_mr = env_int("TIMHIP_GEMM_PF_MR", 0);
-  k.gemm_ldp = env_int("TIMHIP_GEMM_LDP", 1); k.gemm_ld1 = env_int("TIMHIP_GEMM_LD1", 0); k.gemm_pt = env_int("TIMHIP_GEMM_PT", 0);
-  k.gemm_dg = env_int("TIMHIP_GEMM_DG", 0); k.gemm_dg_offset = env_int("TIMHIP_GEMM_DG_OFFSET", 9);
-  k.fuse_ln = env_int("TIMHIP_FUSE_LN", 0); k.fuse_ln_spin = env_int("TIMHIP_FUSE_LN_SPIN", 100000);
-  k.wgrad_pp = env_int("TIMHIP_WGRAD_PP", 1); k.wgrad_ld = env_int("TIMHIP_WGRAD_LD", 1); k.wgrad_pf = env_int("TIMHIP_WGRAD_PF", 4);
-  k.wgrad_p8 = env_int("TIMHIP_WGRAD_P8", 1); k.wgrad_p8_ph = env_int("TIMHIP_WGRAD_P8_PH", 2);
-  k.attn_waves = env_int("TIMHIP_ATTN_WAVES", 0); k.attn_fused = env_int("TIMHIP_ATTN_FUSED", 1);
-  k.ln_rpb = env_int("TIMHIP_LN_RPB", 0);
-  k.gemm_tmw = env_int("TIMHIP_GEMM_TMW", 0);
-  k.ln_rpb_small = env_int("TIMHIP_LN_RPB_SMALL", 0); k.ln_fwd_rpb = env_int("TIMHIP_LN_FWD_RPB", 0);
-  k.gemm_small_nst = env_int("TIMHIP_GEMM_SMALL_NST", 0); k.gemm_small_w8 = env_int("TIMHIP_GEMM_SMALL_W8", 1); k.gemm_p8_ph = env_int("TIMHIP_GEMM_P8_PH", 2);
-  k.gemm_pp_min = env_int("TIMHIP_GEMM_PP_MIN_TILES", 192);
-  k.attn_ks = env_int("TIMHIP_ATTN_KS", 1);
-  k.gemm_p8 = env_int("TIMHIP_GEMM_P8", 1);
-  k.ln_pair = env_int("TIMHIP_LN_PAIR", 1);
-  k.epi_pair = env_int("TIMHIP_EPI_PAIR", 1);
-  k.attn_split_min = env_int("TIMHIP_ATTN_SPLIT_MIN", 4);
+  k.gemm_pp = env_int("TIMHIP_GEMM_PP", k.gemm_pp); k.gemm_ld = env_int("TIMHIP_GEMM_LD", k.gemm_ld); k.gemm_pf = env_int("TIMHIP_GEMM_PF", k.gemm_pf);
+  k.gemm_pf_mode = env_int("TIMHIP_GEMM_PF_MODE", k.gemm_pf_mode); k.gemm_pf_mr = env_int("TIMHIP_GEMM_PF_MR", k.gemm_pf_mr);
+  k.gemm_ldp = env_int("TIMHIP_GEMM_LDP", k.gemm_ldp); k.gemm_ld1 = env_int("TIMHIP_GEMM_LD1", k.gemm_ld1); k.gemm_pt = env_int("TIMHIP_GEMM_PT", k.gemm_pt);
+  k.gemm_dg = env_int("TIMHIP_GEMM_DG", k.gemm_dg); k.gemm_dg_offset = env_int("TIMHIP_GEMM_DG_OFFSET", k.gemm_dg_offset);
+  k.fuse_ln = env_int("TIMHIP_FUSE_LN", k.fuse_ln); k.fuse_ln_spin = env_int("TIMHIP_FUSE_LN_SPIN", k.fuse_ln_spin);
+  k.wgrad_pp = env_int("TIMHIP_WGRAD_PP", k.wgrad_pp); k.wgrad_ld = env_int("TIMHIP_WGRAD_LD", k.wgrad_ld); k.wgrad_pf = env_int("TIMHIP_WGRAD_PF", k.wgrad_pf);
+  k.wgrad_p8 = env_int("TIMHIP_WGRAD_P8", k.wgrad_p8); k.wgrad_p8_ph = env_int("TIMHIP_WGRAD_P8_PH", k.wgrad_p8_ph);
+  k.attn_waves = env_int("TIMHIP_ATTN_WAVES", k.attn_waves); k.attn_fused = env_int("TIMHIP_ATTN_FUSED", k.attn_fused);
+  k.ln_rpb = env_int("TIMHIP_LN_RPB", k.ln_rpb);
+  k.gemm_tmw = env_int("TIMHIP_GEMM_TMW", k.gemm_tmw);
+  k.ln_rpb_small = env_int("TIMHIP_LN_RPB_SMALL", k.ln_rpb_small); k.ln_fwd_rpb = env_int("TIMHIP_LN_FWD_RPB", k.ln_fwd_rpb);
+  k.gemm_small_nst = env_int("TIMHIP_GEMM_SMALL_NST", k.gemm_small_nst); k.gemm_small_w8 = env_int("TIMHIP_GEMM_SMALL_W8", k.gemm_small_w8); k.gemm_p8_ph = env_int("TIMHIP_GEMM_P8_PH", k.gemm_p8_ph);
+  k.gemm_pp_min = env_int("TIMHIP_GEMM_PP_MIN_TILES", k.gemm_pp_min);
+  k.attn_ks = env_int("TIMHIP_ATTN_KS", k.attn_ks);
+  k.gemm_p8 = env_int("TIMHIP_GEMM_P8", k.gemm_p8);
+  k.ln_pair = env_int("TIMHIP_LN_PAIR", k.ln_pair);
+  k.epi_pair = env_int("TIMHIP_EPI_PAIR", k.epi_pair);
+  k.attn_split_min = env_int("TIMHIP_ATTN_SPLIT_MIN", k.attn_split_min);
   if (k.attn_split_min < 1) k.attn_split_min = 1;
 }
 }  // namespace
@@ -243,7 +244,7 @@ extern "C" {
 
 int timhip_version(void) { return TIMHIP_VERSION; }
 void timhip_reload_env(void) { g_knobs_state.store(0, std::memory_order_release); (void)tim_knobs(); }
-int timhip_gemm_p8_choice(int epi, int M, int N, int K) { return tim_gemm_p8_choice(epi, M, N, K); }
+int timhip_gemm_p8_choice(int epi, int M, int N, int K) { return gemm_p8_tm(tim_knobs(), epi, M, N, K, 0); }
 int timhip_build_flags(void) {
 #ifdef TIMHIP_TUNING
   return 1;

@@ -282,44 +282,7 @@ __device__ __forceinline__ void gelu_both_f(float x, float& gl, float& dg) {
   dg = fmaf(x * kInvSqrt2Pi, e, ph);
 }
 
-// A/B knobs of the launchers, read from the environment ONCE (first launch) instead of per launch - the step issues 144
-// launches and the host is within 36 % of being the bottleneck.  timhip_reload_env() (test hook, include/timhip.h) re-reads
-// them; the knobs marked (T) select kernels that exist only in a TUNING=1 build of the library and are ignored otherwise.
-struct TimKnobs {
-  int gemm_pp;        // TIMHIP_GEMM_PP      0: no one-block-per-CU NT kernels at all (the two-blocks-per-CU kernels of gemm.hip)
-  int gemm_ld;        // TIMHIP_GEMM_LD      0: the 8-wave ping-pong kernel instead of loader waves + L2 prefetch
-  int gemm_pf;        // TIMHIP_GEMM_PF      L2 prefetch distance in stages (default 4, 0: off)
-  int gemm_pf_mode;   // TIMHIP_GEMM_PF_MODE 1: a tile touches its share of the XCD's lines, 2: all its lines
-  int gemm_pf_mr;     // TIMHIP_GEMM_PF_MR   prefetch distance of multi-round shapes run one tile per block (default 0)
-  int gemm_ldp;       // TIMHIP_GEMM_LDP     0: one tile per block where the default walks 2-4
-  int gemm_ld1;       // TIMHIP_GEMM_LD1 (T) 1: one barrier per contraction step
-  int gemm_pt;        // TIMHIP_GEMM_PT  (T) 1: 8-wave persistent-tile kernel
-  int gemm_dg;        // TIMHIP_GEMM_DG  (T) 1: dual-group persistent kernel;  gemm_dg_offset: TIMHIP_GEMM_DG_OFFSET
-  int gemm_dg_offset;
-  int fuse_ln;        // TIMHIP_FUSE_LN  (T) 1: residual + LayerNorm inside the out-projection / linear2 epilogue
-  int fuse_ln_spin;   // TIMHIP_FUSE_LN_SPIN
-  int wgrad_pp;       // TIMHIP_WGRAD_PP     0: no one-block-per-CU weight-gradient grid
-  int wgrad_ld;       // TIMHIP_WGRAD_LD     0: its 8-wave merged-phase form
-  int wgrad_pf;       // TIMHIP_WGRAD_PF     its L2 prefetch distance (default 4)
-  int wgrad_p8_ph;    // TIMHIP_WGRAD_P8_PH  phases per contraction step of the eight-phase weight-gradient kernel: 2 (32 MFMAs each, default) or 4 (16 each, as first written)
-  int wgrad_p8;       // TIMHIP_WGRAD_P8     0: no eight-phase 256 x 256 weight-gradient grid (two layers per launch)
-  int attn_waves;     // TIMHIP_ATTN_WAVES   waves per attention block (0: by shape)
-  int attn_fused;     // TIMHIP_ATTN_FUSED   0: two-kernel attention backward
-  int ln_rpb;         // TIMHIP_LN_RPB       rows per LayerNorm-backward block (0: by shape)
-  int gemm_p8_ph;     // TIMHIP_GEMM_P8_PH   phases per contraction step of the eight-phase NT kernel: 2 (4 TM MFMAs each, default) or 4 (2 TM each, as first written)
-  int gemm_small_w8;  // TIMHIP_GEMM_SMALL_W8   0: four waves instead of eight (2 x 4 of 32 x 32) on the small-problem GEMM's 64 x 128 tile where four stages are taken
-  int gemm_small_nst; // TIMHIP_GEMM_SMALL_NST  LDS stages of the small-problem GEMM instances (0: by the block count; 1 / 2: two, as before round 6)
-  int ln_fwd_rpb;     // TIMHIP_LN_FWD_RPB   rows per block of the 8-columns-per-lane LayerNorm forward (0: by the row count)
-  int ln_rpb_small;   // TIMHIP_LN_RPB_SMALL rows per block of the LayerNorm-backward launches that end in atomics (0: as TIMHIP_LN_RPB)
-  int gemm_tmw;       // TIMHIP_GEMM_TMW     5 / 4: force the 160- / 128-row tile of the loader-wave NT kernels (0: by shape)
-  int attn_ks;        // TIMHIP_ATTN_KS      0: fused attention backward with the one-wave-per-row-block phase 1 (default 1: key-split)
-  int gemm_pp_min;    // TIMHIP_GEMM_PP_MIN_TILES  fewest 160 x 256 tiles the one-block-per-CU NT kernels are used for (default 192)
-  int attn_split_min; // TIMHIP_ATTN_SPLIT_MIN  attention forward, B * H < 128: fewest row blocks per workgroup when a (window, head) is split (default 4)
-  int epi_pair;       // TIMHIP_EPI_PAIR     dropout + residual NT epilogue: lane pairs share the Philox calls of their keep factors (default 1)
-  int ln_pair;        // TIMHIP_LN_PAIR      LayerNorm backward: lane pairs share the Philox calls of their dropout keep factors (default 1)
-  int gemm_p8;        // TIMHIP_GEMM_P8      eight-phase 256 / 320 x 256 tiles for the multi-round NT shapes: 0 off, 1 by shape (default), 2 + the mulaux epilogue, 8 / 10 forced
-};
-const TimKnobs& tim_knobs();
+#include "tim_knobs.h"   // TimKnobs, tim_knobs(): the launchers' A/B knobs
 
 // Non-finite watch of the fp16 gradient path.  `out_scale` (where a kernel takes one) points at word 1 of the block
 // timhip_grad_scale writes: {S, 1/S, scratch, scratch, FLAG, 0, 0, 0}.  Every kernel that writes FINAL fp32 gradients
@@ -435,9 +398,6 @@ struct TimGemmScope {
 int tim_gemm_nt(int precision, int epi, const void* A, int lda, const void* B, int ldb, int M, int N,
                 int K, const TimEpi& e, int splitk, hipStream_t s);
 int tim_gemm_nt_group(int precision, int epi, const TimGemmItem* items, int n, hipStream_t s);
-// gemm_pp.hip: the one-block-per-CU ping-pong kernel for the encoder-layer shapes (epi_dev: the caller's EpiDev)
-bool tim_gemm_pp_wins(int M, int N, int K, int splitk);
-int tim_gemm_p8_choice(int epi, int M, int N, int K);   // gemm_pp.hip: 8 / 10 = the eight-phase kernel's row tile for this launch, 0 = not taken
 // gemm_pp.hip: out-projection / linear2 with the LayerNorm that follows fused into the epilogue (gemm_nt_ldln_kernel)
 struct TimLnFuse {
   void* xt; int ldt; float* xf; int ldx; float* stats; const float* g; const float* b;            // LayerNorm outputs / parameters
@@ -447,8 +407,11 @@ int tim_gemm_nt_pp_ln(int precision, const void* A, int lda, const void* B, int 
                       const TimLnFuse& lf, const uint32_t** fail, hipStream_t s);
 int tim_gemm_nt_fuse_ln(int precision, const void* A, int lda, const void* B, int ldb, int M, int N, int K, const TimEpi& te,
                         const TimLnFuse& lf, const uint32_t** fail, hipStream_t s);
-int tim_gemm_nt_pp(int precision, int epi, const void* A, int lda, const void* B, int ldb, int M, int N, int K, const void* epi_dev,
-                   hipStream_t s);
+// gemm_pp.hip: the one-block-per-CU kernels for the encoder-layer shapes, launched as gemm_plan.h's plan says (a plan of one of
+// their families; epi_dev: the caller's EpiDev)
+struct GemmPlan;
+int tim_gemm_nt_pp(const GemmPlan& p, int precision, int epi, const void* A, int lda, const void* B, int ldb, int M, int N, int K,
+                   const void* epi_dev, hipStream_t s);
 int tim_transpose(int precision, const void* src, int rows, int cols, int lds, void* dst, int ld,
                   float* colsum, hipStream_t s);
 int tim_slab_reduce(const float* slab, long long n, int nslab, float* dW, hipStream_t s);

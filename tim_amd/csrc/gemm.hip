@@ -19,6 +19,7 @@
 #include <stdlib.h>
 
 #include "gemm_epi.h"
+#include "gemm_plan.h"
 
 namespace {
 
@@ -613,136 +614,113 @@ __global__ __launch_bounds__(256) void gemm_nt_x3_kernel(const float* __restrict
   }
 }
 
+// ---------------------------------------------------------------------------
+// launchers: which kernel and what geometry is gemm_plan.h's decision; these turn a plan into the launch
+// ---------------------------------------------------------------------------
 template <typename HT, int EPI, int BM, int BN, int WM, int WN, int BKT, int NST, int GM, int ABL = 0>
-void launch_h16(const void* A, int lda, const void* B, int ldb, int M, int N, int K, const EpiDev& e, int splitk,
-                 hipStream_t s) {
-  const int nk = K / BK;
-  const int per = (nk + splitk - 1) / splitk;
-  dim3 grid(((M + BM - 1) / BM) * ((N + BN - 1) / BN), 1, splitk);
-  const size_t shmem = (size_t)NST * (BM + BN) * BKT * 2;
+void launch_h16(const GemmPlan& p, const void* A, int lda, const void* B, int ldb, int M, int N, int K, const EpiDev& e, hipStream_t s) {
   static PerDeviceOnce attr_set;  // idempotent; a benign race sets it twice at worst
-  if (shmem > 64 * 1024 && attr_set.first()) {
+  if (p.lds_bytes > 64 * 1024 && attr_set.first()) {
     (void)hipFuncSetAttribute((const void*)gemm_nt_h16_kernel<HT, EPI, BM, BN, WM, WN, BKT, NST, GM, ABL>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
   }
-  hipLaunchKernelGGL((gemm_nt_h16_kernel<HT, EPI, BM, BN, WM, WN, BKT, NST, GM, ABL>), grid, dim3(WM * WN * 64), shmem, s,
-                     (const HT*)A, lda, (const HT*)B, ldb, M, N, K, per, e);
+  hipLaunchKernelGGL((gemm_nt_h16_kernel<HT, EPI, BM, BN, WM, WN, BKT, NST, GM, ABL>), dim3(p.grid_x, 1, p.grid_z), dim3(p.block),
+                     p.lds_bytes, s, (const HT*)A, lda, (const HT*)B, ldb, M, N, K, p.ksteps, e);
 }
 
-// Tile height.  Two tiles are built: 128 x 128 (2 x 2 waves of 64 x 64) and 160 x 128 (1 x 4 waves of 160 x 32).
-// The taller tile stages 71 instead of 64 FLOP per LDS-DMA byte (the kernel is staging-bound) and quantises the
-// encoder's M = 64 windows x 155 tokens = 9920 = 62 x 160 rows exactly: N = 1024 -> 496 tiles = ONE round of the
-// 512 block slots (2 per CU) instead of 624 = 1.2 rounds.  Measured on M = 9920 (tools/gemm_tune.py, variant 14):
-// +8...+35 % on every shape of the layer.  Cost model: rounds of 512 slots x tile height; the tall tile also wins ties.
-static inline bool tall_tile_wins(int M, int N, int splitk) {
-  if (M <= 128) return false;
-  const long long tn = (N + 127) / 128;
-  const long long t128 = (long long)((M + 127) / 128) * tn * splitk, t160 = (long long)((M + 159) / 160) * tn * splitk;
-  const long long c128 = ((t128 + 511) / 512) * 128, c160 = ((t160 + 511) / 512) * 160;
-  if (c160 != c128) return c160 < c128;
-  return (long long)((M + 159) / 160) * 160 <= (long long)((M + 127) / 128) * 128 + 32;
+template <int EPI>
+int launch(const GemmPlan& p, int precision, const void* A, int lda, const void* B, int ldb, int M, int N, int K, const EpiDev& e,
+           hipStream_t s) {
+  if (p.family == GEMM_X3) {
+    hipLaunchKernelGGL(gemm_nt_x3_kernel<EPI>, dim3(p.grid_x, 1, p.grid_z), dim3(p.block), 0, s, (const float*)A, lda, (const float*)B,
+                       ldb, M, N, K, p.ksteps, e);
+  } else if (p.family == GEMM_F32) {
+    hipLaunchKernelGGL(gemm_nt_f32_kernel<EPI>, dim3(p.grid_x, 1, p.grid_z), dim3(p.block), 0, s, (const float*)A, lda, (const float*)B,
+                       ldb, M, N, K, p.ksteps, e);
+  } else {
+#define H16(BM, BN, WM, WN, NST) launch_h16<HT, EPI, BM, BN, WM, WN, 64, NST, 1>(p, A, lda, B, ldb, M, N, K, e, s)
+    DISPATCH_H16(precision,
+      if (p.bm == 64 && p.wm == 2) H16(64, 128, 2, 4, 4);
+      else if (p.bm == 64 && p.nst == 4) H16(64, 128, 1, 4, 4);
+      else if (p.bm == 64 && p.nst == 3) H16(64, 128, 1, 4, 3);
+      else if (p.bm == 64) H16(64, 128, 1, 4, 2);
+      else if (p.bm == 160) H16(160, 128, 1, 4, 2);
+      else H16(128, 128, 2, 2, 2));
+#undef H16
+  }
+  return hipGetLastError() == hipSuccess ? TIMHIP_OK : TIMHIP_ELAUNCH;
 }
 
-// LDS stages of the small-problem (64 x 128) instances: TIMHIP_GEMM_SMALL_NST = 2 / 3 / 4 forces; 0 (default) = by the block
-// count - as many stages as leave every block of the launch resident at once (24 KiB per stage, 160 KiB per CU)
-static inline int small_nst(long long blocks) {
-  const int k = tim_knobs().gemm_small_nst;
-  if (k >= 2 && k <= 4) return k;
-  if (k == 1) return 2;
-  return blocks <= 256 ? 4 : (blocks <= 512 ? 3 : 2);
-}
-
-// tile variants (bf16): 0 = default, others for tuning on selected epilogues
+#ifdef TIMHIP_TUNING
+// Experiment arms of a TUNING=1 build (tools/gemm_tune.py, tools/gemm_abl.py), in FRONT of the plan: TIMHIP_GEMM_VARIANT picks a
+// bf16 tile variant for selected epilogues (0 = the production plan), TIMHIP_GEMM_ALIAS makes every operand row alias row 0
+// (cache-resident).  true: the variant was launched.
+#define TILE(BM, BN, WM, WN, BKT, NST, ...) \
+  launch_h16<bf16_t, EPI, BM, BN, WM, WN, BKT, NST, __VA_ARGS__>(gemm_h16_tile(BM, BN, WM, WN, NST, M, N, K, splitk, BKT), A, lda, B, ldb, M, N, K, e, s)
 template <int EPI>
 constexpr bool tunable() {
   return EPI == TIMHIP_EPI_STORE_T || EPI == TIMHIP_EPI_ADD_F32 || EPI == TIMHIP_EPI_DROP_RES_F32;
 }
-
 template <int EPI>
-int launch(int precision, int variant, const void* A, int lda, const void* B, int ldb, int M, int N, int K,
-           const EpiDev& e, int splitk, hipStream_t s) {
-  if (precision == TIMHIP_PREC_BF16X3) {
-    const int nk = K / BK;
-    const int per = (nk + splitk - 1) / splitk;
-    dim3 grid(((M + 127) / 128) * ((N + 127) / 128), 1, splitk);
-    hipLaunchKernelGGL(gemm_nt_x3_kernel<EPI>, grid, dim3(256), 0, s, (const float*)A, lda, (const float*)B, ldb, M,
-                       N, K, per, e);
-  } else if (precision == TIMHIP_PREC_FP32) {
-    const int nk = K / FBK;
-    const int per = (nk + splitk - 1) / splitk;
-    dim3 grid(((M + 127) / 128) * ((N + 127) / 128), 1, splitk);
-    hipLaunchKernelGGL(gemm_nt_f32_kernel<EPI>, grid, dim3(256), 0, s, (const float*)A, lda,
-                       (const float*)B, ldb, M, N, K, per, e);
-  } else {
-#ifdef TIMHIP_TUNING
-    if constexpr (EPI == TIMHIP_EPI_STORE_T) {  // ablation builds (tools/gemm_abl.py): variant = 100*ABL + tile
-#define ABLV(T, ...) case T: launch_h16<bf16_t, EPI, __VA_ARGS__>(A, lda, B, ldb, M, N, K, e, splitk, s); return hipGetLastError() == hipSuccess ? TIMHIP_OK : TIMHIP_ELAUNCH;
-      switch (variant) {
-        ABLV(100, 128, 128, 2, 2, 64, 2, 1, 1) ABLV(200, 128, 128, 2, 2, 64, 2, 1, 2) ABLV(300, 128, 128, 2, 2, 64, 2, 1, 3)
-        ABLV(700, 128, 128, 2, 2, 64, 2, 1, 7) ABLV(800, 128, 128, 2, 2, 64, 2, 1, 8)
-        ABLV(1600, 128, 128, 2, 2, 64, 2, 1, 16) ABLV(1614, 160, 128, 1, 4, 64, 2, 1, 16)
-        ABLV(814, 160, 128, 1, 4, 64, 2, 1, 8) ABLV(114, 160, 128, 1, 4, 64, 2, 1, 1) ABLV(214, 160, 128, 1, 4, 64, 2, 1, 2)
-        ABLV(314, 160, 128, 1, 4, 64, 2, 1, 3)
-        ABLV(207, 128, 128, 2, 2, 64, 4, 8, 2) ABLV(208, 256, 256, 2, 4, 64, 2, 4, 2) ABLV(205, 256, 256, 4, 2, 32, 4, 4, 2)
-        ABLV(203, 256, 128, 4, 2, 64, 3, 8, 2) ABLV(202, 128, 128, 2, 2, 32, 4, 8, 2)
-
-        default: break;
-      }
+bool launch_variant(int variant, const void* A, int lda, const void* B, int ldb, int M, int N, int K, const EpiDev& e, int splitk,
+                    hipStream_t s) {
+  if constexpr (EPI == TIMHIP_EPI_STORE_T) {  // ablation builds (tools/gemm_abl.py): variant = 100*ABL + tile
+#define ABLV(T, ...) case T: TILE(__VA_ARGS__); return true;
+    switch (variant) {
+      ABLV(100, 128, 128, 2, 2, 64, 2, 1, 1) ABLV(200, 128, 128, 2, 2, 64, 2, 1, 2) ABLV(300, 128, 128, 2, 2, 64, 2, 1, 3)
+      ABLV(700, 128, 128, 2, 2, 64, 2, 1, 7) ABLV(800, 128, 128, 2, 2, 64, 2, 1, 8)
+      ABLV(1600, 128, 128, 2, 2, 64, 2, 1, 16) ABLV(1614, 160, 128, 1, 4, 64, 2, 1, 16)
+      ABLV(814, 160, 128, 1, 4, 64, 2, 1, 8) ABLV(114, 160, 128, 1, 4, 64, 2, 1, 1) ABLV(214, 160, 128, 1, 4, 64, 2, 1, 2)
+      ABLV(314, 160, 128, 1, 4, 64, 2, 1, 3)
+      ABLV(207, 128, 128, 2, 2, 64, 4, 8, 2) ABLV(208, 256, 256, 2, 4, 64, 2, 4, 2) ABLV(205, 256, 256, 4, 2, 32, 4, 4, 2)
+      ABLV(203, 256, 128, 4, 2, 64, 3, 8, 2) ABLV(202, 128, 128, 2, 2, 32, 4, 8, 2)
+      default: break;
+    }
 #undef ABLV
-    }
-    if (tunable<EPI>() && variant != 0) {   // (bf16 tile variants of tools/gemm_tune.py; variant 0 = the production dispatch below)
-      switch (variant) {
-        case 1: launch_h16<bf16_t, EPI, 128, 128, 2, 2, 64, 2, 8>(A, lda, B, ldb, M, N, K, e, splitk, s); break;
-        case 2: launch_h16<bf16_t, EPI, 128, 128, 2, 2, 32, 4, 8>(A, lda, B, ldb, M, N, K, e, splitk, s); break;
-        case 3: launch_h16<bf16_t, EPI, 256, 128, 4, 2, 64, 3, 8>(A, lda, B, ldb, M, N, K, e, splitk, s); break;
-        case 4: launch_h16<bf16_t, EPI, 256, 256, 2, 4, 32, 4, 4>(A, lda, B, ldb, M, N, K, e, splitk, s); break;
-        case 5: launch_h16<bf16_t, EPI, 256, 256, 4, 2, 32, 4, 4>(A, lda, B, ldb, M, N, K, e, splitk, s); break;
-        case 6: launch_h16<bf16_t, EPI, 256, 128, 4, 2, 32, 4, 8>(A, lda, B, ldb, M, N, K, e, splitk, s); break;
-        case 7: launch_h16<bf16_t, EPI, 128, 128, 2, 2, 64, 4, 8>(A, lda, B, ldb, M, N, K, e, splitk, s); break;
-        case 8: launch_h16<bf16_t, EPI, 256, 256, 2, 4, 64, 2, 4>(A, lda, B, ldb, M, N, K, e, splitk, s); break;
-        case 9: launch_h16<bf16_t, EPI, 128, 128, 2, 2, 32, 3, 1>(A, lda, B, ldb, M, N, K, e, splitk, s); break;
-        case 11: launch_h16<bf16_t, EPI, 128, 128, 2, 2, 64, 2, 4>(A, lda, B, ldb, M, N, K, e, splitk, s); break;
-        case 12: launch_h16<bf16_t, EPI, 128, 128, 2, 2, 64, 2, 16>(A, lda, B, ldb, M, N, K, e, splitk, s); break;
-        case 13: launch_h16<bf16_t, EPI, 128, 128, 2, 2, 64, 2, 39>(A, lda, B, ldb, M, N, K, e, splitk, s); break;
-        case 10: launch_h16<bf16_t, EPI, 128, 128, 2, 2, 32, 3, 8>(A, lda, B, ldb, M, N, K, e, splitk, s); break;
-        case 14: launch_h16<bf16_t, EPI, 160, 128, 1, 4, 64, 2, 1>(A, lda, B, ldb, M, N, K, e, splitk, s); break;
-        case 19: launch_h16<bf16_t, EPI, 192, 128, 2, 2, 64, 2, 1>(A, lda, B, ldb, M, N, K, e, splitk, s); break;
-        case 22: launch_h16<bf16_t, EPI, 320, 128, 2, 4, 64, 2, 1>(A, lda, B, ldb, M, N, K, e, splitk, s); break;
-        case 24: launch_h16<bf16_t, EPI, 160, 128, 1, 4, 64, 3, 1>(A, lda, B, ldb, M, N, K, e, splitk, s); break;
-        case 25: launch_h16<bf16_t, EPI, 192, 128, 1, 4, 64, 2, 1>(A, lda, B, ldb, M, N, K, e, splitk, s); break;
-        default: launch_h16<bf16_t, EPI, 128, 128, 2, 2, 64, 2, 1>(A, lda, B, ldb, M, N, K, e, splitk, s); break;
-      }
-    } else
-#endif
-    {
-      (void)variant;
-      // small problems (front end, heads: a few hundred to a few thousand rows): when 128-row tiles would fill at most
-      // half of the 512 block slots, 64 x 128 tiles (1 x 4 waves of 64 x 32, 48 KB of LDS: three blocks per CU) double
-      // the number of blocks - these launches are occupancy-bound, not staging-bound
-      const long long t128 = (long long)((M + 127) / 128) * ((N + 127) / 128) * splitk;
-      DISPATCH_H16(precision,
-        if (t128 <= 256 && M > 64) {
-          // (a block of such a launch is a CHAIN of K / 64 stage latencies: with two LDS stages one load is in flight while the
-          //  previous stage is multiplied - 0.1 us of MFMAs - so a step lasts a memory latency; deeper rings divide that.
-          //  TIMHIP_GEMM_SMALL_NST = 2 / 3 / 4 stages of 24 KiB: 3 / 2 / 1 blocks per CU)
-          const int nst = small_nst((long long)((M + 63) / 64) * ((N + 127) / 128) * splitk);
-          // With the latency chain shortened, a step costs a wave its six LDS-DMA issue stalls and eight MFMAs: the launches of at
-          // most 256 blocks (one per CU: three SIMD slots of four idle) run the tile on EIGHT waves, 2 x 4 of 32 x 32 - half of both
-          // per wave: C2a at 8 windows per GPU 1.843 -> 1.790 ms, C1 0.832 -> 0.826 (profiles/r06_aa_small_gemm_w8_ab.txt; the
-          // two-blocks-per-CU launches gain nothing from it: r06_ab).  TIMHIP_GEMM_SMALL_W8=0: four waves.
-          if (nst >= 4 && tim_knobs().gemm_small_w8 != 0) launch_h16<HT, EPI, 64, 128, 2, 4, 64, 4, 1>(A, lda, B, ldb, M, N, K, e, splitk, s);
-          else if (nst >= 4) launch_h16<HT, EPI, 64, 128, 1, 4, 64, 4, 1>(A, lda, B, ldb, M, N, K, e, splitk, s);
-          else if (nst == 3) launch_h16<HT, EPI, 64, 128, 1, 4, 64, 3, 1>(A, lda, B, ldb, M, N, K, e, splitk, s);
-          else launch_h16<HT, EPI, 64, 128, 1, 4, 64, 2, 1>(A, lda, B, ldb, M, N, K, e, splitk, s);
-        } else if (tall_tile_wins(M, N, splitk))
-          launch_h16<HT, EPI, 160, 128, 1, 4, 64, 2, 1>(A, lda, B, ldb, M, N, K, e, splitk, s);
-        else
-          launch_h16<HT, EPI, 128, 128, 2, 2, 64, 2, 1>(A, lda, B, ldb, M, N, K, e, splitk, s));
-    }
   }
-  if (hipGetLastError() != hipSuccess) return TIMHIP_ELAUNCH;
-  return TIMHIP_OK;
+  if (!tunable<EPI>()) return false;   // (a run-time test, as it always was: the variant tiles stay instantiated for every epilogue)
+  switch (variant) {   // (bf16 tile variants of tools/gemm_tune.py)
+    case 1: TILE(128, 128, 2, 2, 64, 2, 8); break;
+    case 2: TILE(128, 128, 2, 2, 32, 4, 8); break;
+    case 3: TILE(256, 128, 4, 2, 64, 3, 8); break;
+    case 4: TILE(256, 256, 2, 4, 32, 4, 4); break;
+    case 5: TILE(256, 256, 4, 2, 32, 4, 4); break;
+    case 6: TILE(256, 128, 4, 2, 32, 4, 8); break;
+    case 7: TILE(128, 128, 2, 2, 64, 4, 8); break;
+    case 8: TILE(256, 256, 2, 4, 64, 2, 4); break;
+    case 9: TILE(128, 128, 2, 2, 32, 3, 1); break;
+    case 11: TILE(128, 128, 2, 2, 64, 2, 4); break;
+    case 12: TILE(128, 128, 2, 2, 64, 2, 16); break;
+    case 13: TILE(128, 128, 2, 2, 64, 2, 39); break;
+    case 10: TILE(128, 128, 2, 2, 32, 3, 8); break;
+    case 14: TILE(160, 128, 1, 4, 64, 2, 1); break;
+    case 19: TILE(192, 128, 2, 2, 64, 2, 1); break;
+    case 22: TILE(320, 128, 2, 4, 64, 2, 1); break;
+    case 24: TILE(160, 128, 1, 4, 64, 3, 1); break;
+    case 25: TILE(192, 128, 1, 4, 64, 2, 1); break;
+    default: TILE(128, 128, 2, 2, 64, 2, 1); break;
+  }
+  return true;
 }
+#undef TILE
+bool gemm_tuning_launch(int precision, int epi, const void* A, int& lda, const void* B, int& ldb, int M, int N, int K, const EpiDev& e,
+                        int splitk, hipStream_t s) {
+  if (getenv("TIMHIP_GEMM_ALIAS")) { lda = 0; ldb = 0; }
+  const char* v = getenv("TIMHIP_GEMM_VARIANT");
+  const int variant = v ? atoi(v) : 0;
+  if (variant == 0 || !h16_storage(precision)) return false;
+  switch (epi) {
+#define CASE(X) case X: return launch_variant<X>(variant, A, lda, B, ldb, M, N, K, e, splitk, s);
+    CASE(TIMHIP_EPI_STORE_T) CASE(TIMHIP_EPI_RELU_T) CASE(TIMHIP_EPI_STORE_F32) CASE(TIMHIP_EPI_GELU_DROP_T2) CASE(TIMHIP_EPI_DROP_RES_F32)
+    CASE(TIMHIP_EPI_ADD_F32) CASE(TIMHIP_EPI_DGELU_T) CASE(TIMHIP_EPI_DRELU_T) CASE(TIMHIP_EPI_ATOMIC_F32) CASE(TIMHIP_EPI_SIGMOID_F32)
+    CASE(TIMHIP_EPI_DRELU_F32IN_T) CASE(TIMHIP_EPI_GELU_DROP_G2) CASE(TIMHIP_EPI_MULAUX_T) CASE(TIMHIP_EPI_RELU_SPLIT3_T) CASE(TIMHIP_EPI_GELU_T)
+#undef CASE
+    default: return false;
+  }
+}
+#else
+inline bool gemm_tuning_launch(int, int, const void*, int&, const void*, int&, int, int, int, const EpiDev&, int, hipStream_t) { return false; }
+#endif
 
 }  // namespace
 
@@ -790,7 +768,7 @@ static int prepare_gemm(int precision, int epi, const void* A, int lda, const vo
   return TIMHIP_OK;
 }
 
-// n <= 6 independent bf16 problems with the same epilogue as one grid of 64 x 128 tiles (small problems: the heads)
+// n <= 6 independent bf16 problems with the same epilogue as one grid of 64-row tiles (small problems: the heads)
 int tim_gemm_nt_group(int precision, int epi, const TimGemmItem* items, int n, hipStream_t s) {
   if (!h16_storage(precision)) return TIMHIP_EUNSUPPORTED;
   if (!items || n < 1 || n > GG_MAX) return TIMHIP_EINVAL;
@@ -798,47 +776,36 @@ int tim_gemm_nt_group(int precision, int epi, const TimGemmItem* items, int n, h
     return TIMHIP_EUNSUPPORTED;
   GemmGroupDev g;
   g.n = n;
-  g.tile0[0] = 0;
   double flops = 0.0;
-  for (int i = 0; i < GG_MAX; ++i) {
-    if (i >= n) {
-      g.A[i] = g.B[i] = nullptr; g.lda[i] = g.ldb[i] = g.M[i] = g.N[i] = g.K[i] = 0; g.tile0[i + 1] = g.tile0[i];
-      g.e[i] = g.e[0];
-      continue;
-    }
+  for (int i = 0; i < n; ++i) {
     const TimGemmItem& t = items[i];
     const int rc = prepare_gemm(precision, epi, t.A, t.lda, t.B, t.ldb, t.M, t.N, t.K, t.e, 1, g.e[i]);
     if (rc) return rc;
     g.A[i] = t.A; g.B[i] = t.B; g.lda[i] = t.lda; g.ldb[i] = t.ldb;
     g.M[i] = t.M; g.N[i] = t.N; g.K[i] = round_up(t.K, 64);
-    g.tile0[i + 1] = g.tile0[i] + ((t.M + 63) / 64) * ((t.N + 127) / 128);
     flops += 2.0 * t.M * t.N * t.K / (t.reserved > 1 ? t.reserved : 1);   // reserved: operand replication of a split GEMM
   }
+  const GemmGroupPlan p = gemm_group_plan(tim_knobs(), epi, items, n);
+  g.tile0[0] = 0;
+  for (int i = 0; i < GG_MAX; ++i) {   // the items' tile lists, concatenated; the unused slots are empty
+    if (i < n) { g.tile0[i + 1] = g.tile0[i] + ((g.M[i] + 63) / 64) * ((g.N[i] + p.bn - 1) / p.bn); continue; }
+    g.A[i] = g.B[i] = nullptr; g.lda[i] = g.ldb[i] = g.M[i] = g.N[i] = g.K[i] = 0; g.tile0[i + 1] = g.tile0[i];
+    g.e[i] = g.e[0];
+  }
   TimGemmScope timing(flops, s);
-  if (g.tile0[n] <= 512 && epi == TIMHIP_EPI_ADD_F32) {
-    // still under-filled with 64 x 128 tiles (the heads' input gradients: one long-K item dominates): 64 x 64 tiles double
-    // the blocks again
-    for (int i = 0; i < n; ++i) g.tile0[i + 1] = g.tile0[i] + ((items[i].M + 63) / 64) * ((items[i].N + 63) / 64);
-    for (int i = n; i < GG_MAX; ++i) g.tile0[i + 1] = g.tile0[n];
-    DISPATCH_H16(precision, hipLaunchKernelGGL((gemm_nt_group_kernel<HT, TIMHIP_EPI_ADD_F32, 64, 64, 2, 2, 64, 2>),
-                                               dim3((unsigned)g.tile0[n]), dim3(256), (size_t)2 * (64 + 64) * 64 * 2, s, g));
-    return hipGetLastError() == hipSuccess ? TIMHIP_OK : TIMHIP_ELAUNCH;
+#define GROUP(X, BN, WM, WN, NS) do { \
+    if (BN == 128) DISPATCH_H16(precision, (void)hipFuncSetAttribute((const void*)gemm_nt_group_kernel<HT, X, 64, BN, WM, WN, 64, NS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes)); \
+    DISPATCH_H16(precision, hipLaunchKernelGGL((gemm_nt_group_kernel<HT, X, 64, BN, WM, WN, 64, NS>), dim3(p.tiles), dim3(p.block), p.lds_bytes, s, g)); } while (0)
+#define CASE(X) case X: if (p.nst >= 4) GROUP(X, 128, 1, 4, 4); else if (p.nst == 3) GROUP(X, 128, 1, 4, 3); else GROUP(X, 128, 1, 4, 2); break;
+  if (p.bn == 64) GROUP(TIMHIP_EPI_ADD_F32, 64, 2, 2, 2);
+  else switch (epi) {
+    CASE(TIMHIP_EPI_STORE_F32)
+    CASE(TIMHIP_EPI_ADD_F32)
+    CASE(TIMHIP_EPI_STORE_T)
+    CASE(TIMHIP_EPI_RELU_T)
   }
-  const dim3 grid((unsigned)g.tile0[n]);
-  const int nst = small_nst(g.tile0[n]);
-  const size_t shmem = (size_t)nst * (64 + 128) * 64 * 2;
-#define GROUP_N(X, NS) do { DISPATCH_H16(precision, (void)hipFuncSetAttribute((const void*)gemm_nt_group_kernel<HT, X, 64, 128, 1, 4, 64, NS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem)); \
-    DISPATCH_H16(precision, hipLaunchKernelGGL((gemm_nt_group_kernel<HT, X, 64, 128, 1, 4, 64, NS>), grid, dim3(256), shmem, s, g)); } while (0)
-#define GROUP(X) case X: if (nst >= 4) GROUP_N(X, 4); else if (nst == 3) GROUP_N(X, 3); else GROUP_N(X, 2); break;
-  switch (epi) {
-    GROUP(TIMHIP_EPI_STORE_F32)
-    GROUP(TIMHIP_EPI_ADD_F32)
-    GROUP(TIMHIP_EPI_STORE_T)
-    GROUP(TIMHIP_EPI_RELU_T)
-    default: return TIMHIP_EUNSUPPORTED;
-  }
+#undef CASE
 #undef GROUP
-#undef GROUP_N
   return hipGetLastError() == hipSuccess ? TIMHIP_OK : TIMHIP_ELAUNCH;
 }
 
@@ -860,18 +827,12 @@ int tim_gemm_nt(int precision, int epi, const void* A, int lda, const void* B, i
   if (rc0) return rc0;
   const int Kp = round_up(K, 64);
   TimGemmScope timing(2.0 * M * N * K / (te.reserved > 1 ? te.reserved : 1), s);   // te.reserved: operand replication (split GEMM)
-  // production-batch layer shapes: the one-block-per-CU ping-pong kernel (TIMHIP_GEMM_PP=0 turns it off: A/B switch)
-  if (tim_knobs().gemm_pp != 0 && h16_storage(precision) && tim_gemm_pp_wins(M, N, Kp, splitk)) {
-    const int rc = tim_gemm_nt_pp(precision, epi, A, lda, B, ldb, M, N, Kp, &e, s);
-    if (rc != TIMHIP_EUNSUPPORTED) return rc;
-  }
-  int variant = 0;
-#ifdef TIMHIP_TUNING  // tools/gemm_tune.py, tools/gemm_abl.py: make -C tim_amd/csrc TUNING=1
-  if (const char* v = getenv("TIMHIP_GEMM_VARIANT")) variant = atoi(v);
-  if (getenv("TIMHIP_GEMM_ALIAS")) { lda = 0; ldb = 0; }  // every operand row aliases row 0 (cache-resident)
-#endif
+  const GemmPlan p = gemm_nt_plan(tim_knobs(), precision, epi, M, N, Kp, splitk, e.a_wrap);
+  if (p.family >= GEMM_PP8W) return tim_gemm_nt_pp(p, precision, epi, A, lda, B, ldb, M, N, Kp, &e, s);
+  if (gemm_tuning_launch(precision, epi, A, lda, B, ldb, M, N, Kp, e, splitk, s))
+    return hipGetLastError() == hipSuccess ? TIMHIP_OK : TIMHIP_ELAUNCH;
   switch (epi) {
-#define CASE(X) case X: return launch<X>(precision, variant, A, lda, B, ldb, M, N, Kp, e, splitk, s);
+#define CASE(X) case X: return launch<X>(p, precision, A, lda, B, ldb, M, N, Kp, e, s);
     CASE(TIMHIP_EPI_STORE_T)
     CASE(TIMHIP_EPI_RELU_T)
     CASE(TIMHIP_EPI_STORE_F32)

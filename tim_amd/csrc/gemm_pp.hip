@@ -29,10 +29,11 @@
 #include <mutex>
 
 #include "gemm_epi.h"
+#include "gemm_plan.h"
 
 namespace {
 
-constexpr int PP_BN = 256, PP_ROWB = 128, PP_NST = 3, PP_TNW = 4;
+constexpr int PP_TNW = 4;   // (PP_BN, PP_ROWB, PP_NST: gemm_plan.h)
 
 __device__ __forceinline__ void pp_barrier() {
   __builtin_amdgcn_sched_barrier(0);
@@ -1032,14 +1033,16 @@ __global__ __launch_bounds__(512) void gemm_nt_p8_kernel(const HT* __restrict__ 
   pp_epilogue<HT, EPI, TM, 2, PpNoSync, 2>(e, acc, m0 + wr * 16 * TM, n0 + wc * 64, M, N, ep, lane);
 }
 
+// the eight-phase kernel, launched as the plan says (gemm_plan.h: GEMM_P8)
 template <typename HT, int EPI, int TM>
-void launch_p8(const void* A, int lda, const void* B, int ldb, int M, int N, int K, const EpiDev& e, hipStream_t s) {
-  constexpr int BM = 32 * TM;
-  const size_t shmem = (size_t)2 * (BM + PP_BN) * PP_ROWB;
+void launch_p8(const GemmPlan& p, const void* A, int lda, const void* B, int ldb, int M, int N, int K, const EpiDev& e, hipStream_t s) {
+  const size_t shmem = p.lds_bytes;
+  const dim3 grid(p.grid_x);
   static PerDeviceOnce attr_set;
-  if (attr_set.first())
+  if (attr_set.first()) {
     (void)hipFuncSetAttribute((const void*)gemm_nt_p8_kernel<HT, EPI, TM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-  const dim3 grid(((M + BM - 1) / BM) * ((N + PP_BN - 1) / PP_BN));
+    (void)hipFuncSetAttribute((const void*)gemm_nt_p8_kernel<HT, EPI, TM, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+  }
 #ifdef TIMHIP_P8_VARIANTS   // experiment arms (tools/p8_ab.py with TIMHIP_GEMM_P8_VAR): plain-store fp16 instances only
   if constexpr (EPI == TIMHIP_EPI_STORE_T && sizeof(HT) == 2 && __is_same(HT, f16_t)) {
     static const int var = getenv("TIMHIP_GEMM_P8_VAR") ? atoi(getenv("TIMHIP_GEMM_P8_VAR")) : 0;
@@ -1050,38 +1053,10 @@ void launch_p8(const void* A, int lda, const void* B, int ldb, int M, int N, int
 #undef P8V
   }
 #endif
-  if (tim_knobs().gemm_p8_ph != 4) {   // two phases per step: the default (in-projection forward 60.0 -> 56.8 us, linear1 forward 54.5 -> 51.9: profiles/r06_af_*)
-    static PerDeviceOnce attr2;
-    if (attr2.first())
-      (void)hipFuncSetAttribute((const void*)gemm_nt_p8_kernel<HT, EPI, TM, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-    hipLaunchKernelGGL((gemm_nt_p8_kernel<HT, EPI, TM, 4>), grid, dim3(512), shmem, s, (const HT*)A, lda, (const HT*)B, ldb, M, N, K, e);
-    return;
-  }
-  hipLaunchKernelGGL((gemm_nt_p8_kernel<HT, EPI, TM>), grid, dim3(512), shmem, s, (const HT*)A, lda, (const HT*)B, ldb, M, N, K, e);
-}
-
-// Which shapes: the ones that run MORE than one round of 160 x 256 tiles, when one of the two big tiles fills its rounds to at
-// least 85 % (useful tile area / (rounds x 256 CUs)).  C2a, M = 9920: N = 3072 -> 256 rows (0.91), N = 2048 -> 320 rows (0.97),
-// N = 1024 stays on the one-round 160-row kernel.  TIMHIP_GEMM_P8 = 0: off; 1 (default): by shape, the 16-bit store and the GELU
-// epilogue; 2: by shape, also the multiply-by-saved-factor epilogue (linear2's input gradient: measured 40.2 against 46.8 us
-// with a plain store but 53.3 against 52.6 with its epilogue - 80 MB of aux rows and results leave through 8 waves instead of
-// 12 - profiles/r06_b_p8_ab.txt); 8 / 10: that tile for every legal shape and all three epilogues (tests)
-static int p8_choice(int epi, int M, int N, int K, const EpiDev& e) {
-  const int kn = tim_knobs().gemm_p8;
-  if (kn == 0 || e.a_wrap != 0 || K % 64 || K < 128 || N % PP_BN || M < 1) return 0;
-  if (epi != TIMHIP_EPI_STORE_T && epi != TIMHIP_EPI_GELU_DROP_G2 && epi != TIMHIP_EPI_GELU_T && epi != TIMHIP_EPI_MULAUX_T) return 0;
-  if (kn == 8 || kn == 10) return kn;
-  if (epi == TIMHIP_EPI_MULAUX_T && kn != 2) return 0;
-  const long long t160 = (long long)((M + 159) / 160) * (N / PP_BN);
-  if (t160 <= 256) return 0;
-  auto fill = [&](int bm) {
-    const long long tiles = (long long)((M + bm - 1) / bm) * (N / PP_BN), rounds = (tiles + 255) / 256;
-    return (double)M * N / ((double)bm * PP_BN) / (double)(rounds * 256);
-  };
-  const double f8 = fill(256), f10 = fill(320);
-  if (f10 >= f8 && f10 >= 0.85) return 10;
-  if (f8 >= 0.85) return 8;
-  return 0;
+  if (p.phases == 2)
+    hipLaunchKernelGGL((gemm_nt_p8_kernel<HT, EPI, TM, 4>), grid, dim3(p.block), shmem, s, (const HT*)A, lda, (const HT*)B, ldb, M, N, K, e);
+  else
+    hipLaunchKernelGGL((gemm_nt_p8_kernel<HT, EPI, TM>), grid, dim3(p.block), shmem, s, (const HT*)A, lda, (const HT*)B, ldb, M, N, K, e);
 }
 
 // ---- residual + LayerNorm fused into the epilogue (gemm_nt_ldln_kernel, round 3) ---------------------------
@@ -1446,7 +1421,35 @@ __global__ __launch_bounds__(512) void gemm_nt_dg_kernel(const HT* __restrict__ 
   }
 }
 
-#ifdef TIMHIP_TUNING   // (measured 13 % slower than one tile per block, DESIGN.md section 5c: tuning builds only)
+// the 8-wave, loader-wave and walking kernels, launched as the plan says (gemm_plan.h: GEMM_PP8W / GEMM_LD / GEMM_LDP); the
+// 128-row tile (TMW = 4) exists for the loader-wave kernels only
+template <typename HT, int EPI, int TMW>
+void launch_pp(const GemmPlan& p, const void* A, int lda, const void* B, int ldb, int M, int N, int K, const EpiDev& e, hipStream_t s) {
+  static PerDeviceOnce attr_set;   // idempotent; a benign race sets it twice at worst
+  if (attr_set.first()) {
+    if constexpr (TMW == 5)
+      (void)hipFuncSetAttribute((const void*)gemm_nt_pp_kernel<HT, EPI, TMW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
+    (void)hipFuncSetAttribute((const void*)gemm_nt_ld_kernel<HT, EPI, TMW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
+    (void)hipFuncSetAttribute((const void*)gemm_nt_ldp_kernel<HT, EPI, TMW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
+  }
+  const dim3 grid(p.grid_x), block(p.block);
+  if (p.family == GEMM_LDP)
+    hipLaunchKernelGGL((gemm_nt_ldp_kernel<HT, EPI, TMW>), grid, block, p.lds_bytes, s, (const HT*)A, lda, (const HT*)B, ldb, M, N, K, e,
+                       p.pf_dist, p.pf_mode, p.tpb);
+  else if (p.family == GEMM_LD)
+    hipLaunchKernelGGL((gemm_nt_ld_kernel<HT, EPI, TMW>), grid, block, p.lds_bytes, s, (const HT*)A, lda, (const HT*)B, ldb, M, N, K, e,
+                       p.pf_dist, p.pf_mode);
+  else if constexpr (TMW == 5)
+    hipLaunchKernelGGL((gemm_nt_pp_kernel<HT, EPI, TMW>), grid, block, p.lds_bytes, s, (const HT*)A, lda, (const HT*)B, ldb, M, N, K, e);
+}
+
+}  // namespace
+
+#ifdef TIMHIP_TUNING
+// ---- experiment arms of a TUNING=1 build, in FRONT of the plan (a product build's plan can never name them) --------------------
+namespace {
+
+// (measured 13 % slower than one tile per block)
 template <typename HT, int EPI>
 void launch_dg(const void* A, int lda, const void* B, int ldb, int M, int N, int K, const EpiDev& e, int offset_phases, hipStream_t s) {
   const size_t shmem = 2 * (size_t)DG_RING;
@@ -1458,129 +1461,82 @@ void launch_dg(const void* A, int lda, const void* B, int ldb, int M, int N, int
   hipLaunchKernelGGL((gemm_nt_dg_kernel<HT, EPI>), dim3(npairs / ppb), dim3(512), shmem, s, (const HT*)A, lda, (const HT*)B, ldb, M, N,
                      K, e, ppb, offset_phases);
 }
+// Shapes for the dual-group persistent kernel: whole 160 x 256 tile pairs, at least two contraction steps, an even spread of the
+// pairs over the blocks, vectorised epilogue operands.
+bool tim_gemm_dg_ok(int M, int N, int K, const EpiDev& e) {
+  if (M % DG_BM || N % (2 * DG_BN) || K % 64 || K < 128 || !e.vec || !e.vec8) return false;
+  const int npairs = (M / DG_BM) * (N / (2 * DG_BN));
+  const int ppb = (npairs + 255) / 256;
+  return npairs >= 192 && npairs % ppb == 0;
+}
+constexpr bool dg_carries(int epi) {
+  return epi == TIMHIP_EPI_STORE_T || epi == TIMHIP_EPI_DROP_RES_F32 || epi == TIMHIP_EPI_ADD_F32 || epi == TIMHIP_EPI_GELU_DROP_G2 ||
+         epi == TIMHIP_EPI_MULAUX_T;
+}
 
-#endif
-
-template <typename HT, int EPI, int TMW = 5>
-void launch_pp(const void* A, int lda, const void* B, int ldb, int M, int N, int K, const EpiDev& e, hipStream_t s) {
-  constexpr int BM = 32 * TMW;
-  const size_t shmem = (size_t)PP_NST * (BM + PP_BN) * PP_ROWB;
-  if constexpr (TMW != 5) {   // the 128-row tile exists for the loader-wave kernels only
-    if (tim_knobs().gemm_ld == 0 || e.a_wrap != 0) return launch_pp<HT, EPI, 5>(A, lda, B, ldb, M, N, K, e, s);
-  }
-#ifdef TIMHIP_TUNING   // per-phase cycle counters (tools/pp_phase.py)
-  if constexpr (EPI == TIMHIP_EPI_STORE_T && TMW == 5) {
-    if (getenv("TIMHIP_PP_PROF")) {
-      const char* ab = getenv("TIMHIP_PP_ABL");   // 1 no DMA, 2 no MFMAs, 3 DMA only, L the late wait (two-barrier loop)
-      const dim3 g_(((M + BM - 1) / BM) * ((N + PP_BN - 1) / PP_BN));
-#define PP_ABL_LAUNCH(ABLV, LATEV) do { \
-        (void)hipFuncSetAttribute((const void*)gemm_nt_pp_kernel<HT, EPI, TMW, true, ABLV, LATEV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem); \
-        hipLaunchKernelGGL((gemm_nt_pp_kernel<HT, EPI, TMW, true, ABLV, LATEV>), g_, dim3(512), shmem, s, (const HT*)A, lda, (const HT*)B, ldb, M, N, K, e); } while (0)
-      if (ab && ab[0] == '1') { PP_ABL_LAUNCH(1, false); return; }
-      if (ab && ab[0] == '2') { PP_ABL_LAUNCH(2, false); return; }
-      if (ab && ab[0] == '3') { PP_ABL_LAUNCH(3, false); return; }
-      if (ab && ab[0] == '4') { PP_ABL_LAUNCH(4, false); return; }
-      if (ab && ab[0] == '5') { PP_ABL_LAUNCH(5, false); return; }
-      if (ab && ab[0] == '7') { PP_ABL_LAUNCH(7, false); return; }
-      if (ab && ab[0] == '8') { PP_ABL_LAUNCH(8, false); return; }
-      if (ab && ab[0] == '6') { PP_ABL_LAUNCH(6, false); return; }
-      if (ab && ab[0] == 'L') { PP_ABL_LAUNCH(0, true); return; }
-#undef PP_ABL_LAUNCH
-      (void)hipFuncSetAttribute((const void*)gemm_nt_pp_kernel<HT, EPI, TMW, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-      hipLaunchKernelGGL((gemm_nt_pp_kernel<HT, EPI, TMW, true>), g_, dim3(512), shmem, s, (const HT*)A, lda, (const HT*)B, ldb, M, N, K, e);
-      return;
+// true: an experiment arm took the launch that the plan `p` describes
+template <typename HT, int EPI>
+bool launch_pp_tuning(const GemmPlan& p, const void* A, int lda, const void* B, int ldb, int M, int N, int K, const EpiDev& e, hipStream_t s) {
+  const TimKnobs& kn = tim_knobs();
+  // TIMHIP_GEMM_DG=1: the dual-group persistent kernel where the shape allows - measured 13 % slower over the
+  // layer's eight shapes than the one-tile-per-block kernel: its 160 x 128 group tiles stage 72 KiB per step pair where the
+  // 160 x 256 tile stages 52, and the global -> LDS path (~30 B/clk/CU), not the matrix pipe, is what bounds these loops; the hidden
+  // epilogues do not pay for that - DESIGN.md section 5c; TIMHIP_GEMM_DG_OFFSET: barriers group 1 runs behind group 0 (odd)
+  if constexpr (dg_carries(EPI)) {
+    if (kn.gemm_dg == 1 && tim_gemm_dg_ok(M, N, K, e) && e.a_wrap == 0) {
+      launch_dg<HT, EPI>(A, lda, B, ldb, M, N, K, e, (kn.gemm_dg_offset < 1 ? 1 : kn.gemm_dg_offset) | 1, s);
+      return true;
     }
   }
-#endif
-  static PerDeviceOnce attr_set;   // idempotent; a benign race sets it twice at worst
-  if (attr_set.first()) {
-    if constexpr (TMW == 5)
-      (void)hipFuncSetAttribute((const void*)gemm_nt_pp_kernel<HT, EPI, TMW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-    (void)hipFuncSetAttribute((const void*)gemm_nt_ld_kernel<HT, EPI, TMW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+  if (p.family == GEMM_P8 || p.tm != 5) return false;   // the arms below are variants of the 160-row tile
+  constexpr int TMW = 5;
+  const size_t shmem = p.lds_bytes;
+  const int tiles_n = (N + PP_BN - 1) / PP_BN, tiles = (int)p.grid_x * p.tpb;
+  const dim3 grid(tiles);
+  if constexpr (EPI == TIMHIP_EPI_STORE_T) {   // per-phase cycle counters (tools/pp_phase.py)
+    if (getenv("TIMHIP_PP_PROF")) {
+      const char* ab = getenv("TIMHIP_PP_ABL");   // 1 no DMA, 2 no MFMAs, 3 DMA only, L the late wait (two-barrier loop)
+#define PP_ABL_LAUNCH(ABLV, LATEV) do { \
+        (void)hipFuncSetAttribute((const void*)gemm_nt_pp_kernel<HT, EPI, TMW, true, ABLV, LATEV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem); \
+        hipLaunchKernelGGL((gemm_nt_pp_kernel<HT, EPI, TMW, true, ABLV, LATEV>), grid, dim3(512), shmem, s, (const HT*)A, lda, (const HT*)B, ldb, M, N, K, e); } while (0)
+      if (ab && ab[0] == '1') { PP_ABL_LAUNCH(1, false); return true; }
+      if (ab && ab[0] == '2') { PP_ABL_LAUNCH(2, false); return true; }
+      if (ab && ab[0] == '3') { PP_ABL_LAUNCH(3, false); return true; }
+      if (ab && ab[0] == '4') { PP_ABL_LAUNCH(4, false); return true; }
+      if (ab && ab[0] == '5') { PP_ABL_LAUNCH(5, false); return true; }
+      if (ab && ab[0] == '7') { PP_ABL_LAUNCH(7, false); return true; }
+      if (ab && ab[0] == '8') { PP_ABL_LAUNCH(8, false); return true; }
+      if (ab && ab[0] == '6') { PP_ABL_LAUNCH(6, false); return true; }
+      if (ab && ab[0] == 'L') { PP_ABL_LAUNCH(0, true); return true; }
+#undef PP_ABL_LAUNCH
+      (void)hipFuncSetAttribute((const void*)gemm_nt_pp_kernel<HT, EPI, TMW, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+      hipLaunchKernelGGL((gemm_nt_pp_kernel<HT, EPI, TMW, true>), grid, dim3(512), shmem, s, (const HT*)A, lda, (const HT*)B, ldb, M, N, K, e);
+      return true;
+    }
   }
-  const TimKnobs& kn = tim_knobs();
-  const dim3 grid(((M + BM - 1) / BM) * ((N + PP_BN - 1) / PP_BN));
-#ifdef TIMHIP_TUNING
-  if constexpr (EPI != TIMHIP_EPI_DROP_RES_F32 && TMW == 5) {   // (that epilogue's residual prefetch leaves no registers for the tile loop's state)
-    // two or three full rounds of tiles: the 8-wave persistent-tile kernel - TIMHIP_GEMM_PT=1, tuning builds only (measured equal
+  if constexpr (EPI != TIMHIP_EPI_DROP_RES_F32) {   // (that epilogue's residual prefetch leaves no registers for the tile loop's state)
+    // two to four full rounds of tiles: the 8-wave persistent-tile kernel - TIMHIP_GEMM_PT=1 (measured equal
     // to one tile per block within the run-to-run spread, in_proj forward 71.8 vs 71.5 us, linear1 61.8 vs 60.3, linear2 input
     // gradient 50.7 vs 50.5 - profiles/r03_nt_kernel_variants_ab.txt)
-    const int tiles = (int)grid.x, tpb = (tiles + 255) / 256;
-    if (tpb >= 2 && tpb <= 4 && tiles % tpb == 0 && ((N + PP_BN - 1) / PP_BN) % tpb == 0 && K >= 128 && kn.gemm_pt == 1 && e.a_wrap == 0) {
+    const int tpb = gemm_pp_walk(tiles, tiles_n, K);
+    if (tpb > 1 && kn.gemm_pt == 1 && e.a_wrap == 0) {
       static PerDeviceOnce pt_attr;
       if (pt_attr.first())
         (void)hipFuncSetAttribute((const void*)gemm_nt_pt_kernel<HT, EPI, TMW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
       hipLaunchKernelGGL((gemm_nt_pt_kernel<HT, EPI, TMW>), dim3(tiles / tpb), dim3(512), shmem, s, (const HT*)A, lda, (const HT*)B, ldb,
                          M, N, K, e, tpb);
-      return;
+      return true;
     }
   }
-#endif
-  // Default: the loader-wave kernel with the L2 prefetch (round 3: in the step 5.66 ms with the 8-wave kernel, 5.60-5.65 with
-  // loader waves, 5.41-5.44 with loader waves + prefetch 4 stages ahead, NT GEMMs 763 -> 816 TFLOP/s; prefetch distance 2 / 3 / 5
-  // / 6 / 8: +1.0 / +0.5 / +0.2 / +0.7 / +0.8 % of the step; every tile prefetching ALL its lines: 5.83-5.89 ms, the
-  // prefetch loads then take the vector-memory path's time themselves).  TIMHIP_GEMM_LD=0: the 8-wave kernel (fallback).
-  if (kn.gemm_ld != 0 && e.a_wrap == 0) {
-    // multi-round shapes (more than 256 tiles; TIMHIP_GEMM_PF_MR): no prefetch - their tiles drift apart after the first round and
-    // a share covers a twelfth of a panel; in the step distance 0 / 2 / 4 / 6 / 8 / 12 for them: 5.29 / 5.32 / 5.32 / 5.34 / 5.34 / 5.34 ms
-    // Two to four full rounds of tiles run as ONE round of blocks that walk tpb column tiles each (gemm_nt_ldp_kernel;
-    // TIMHIP_GEMM_LDP=0: one tile per block) - the tiles of an XCD stay in step, so the prefetch shares apply to them.  In the
-    // step 5.343 -> 5.314 ms (four interleaved runs per arm, every run of the walk below every run of the one-tile kernel).
-    // The history of that number is in DESIGN.md section 5d: a first A/B had said -2.6 % against a one-tile instance that
-    // spilled; against the restored spill-free one-tile kernel the walk first LOST 1.3 % - it spilled 9-21 registers itself,
-    // the epilogue's loop-invariant lane arithmetic having been hoisted in front of the tile loop and held across the main
-    // loop; with the lane id laundered once per tile (8 / 5 / 1 spills on the three epilogues that use it) it wins 0.5 %.
-    const int tiles_ = (int)grid.x, tiles_n_ = (N + PP_BN - 1) / PP_BN;
-    int tpb = 1;
-    if (kn.gemm_ldp != 0 && tiles_ > 256) {
-      const int want = (tiles_ + 255) / 256;
-      if (want <= 4 && tiles_n_ % want == 0 && tiles_ % want == 0 && K >= 128) tpb = want;
-    }
-    const int pf_d_ = (grid.x > 256 && tpb == 1) ? kn.gemm_pf_mr : kn.gemm_pf;
-    const dim3 grid_(tiles_ / tpb);
-#ifdef TIMHIP_TUNING
-    if constexpr (TMW == 5) if (kn.gemm_ld1 == 1) {   // one barrier per contraction step (measured: +4.6 % isolated, +0.5 % in the step)
-      static PerDeviceOnce attr_l1;
-      if (attr_l1.first())
-        (void)hipFuncSetAttribute((const void*)gemm_nt_ld_kernel<HT, EPI, TMW, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-      hipLaunchKernelGGL((gemm_nt_ld_kernel<HT, EPI, TMW, true>), grid, dim3(768), shmem, s, (const HT*)A, lda, (const HT*)B, ldb, M, N, K, e,
-                         grid.x > 256 ? kn.gemm_pf_mr : kn.gemm_pf, kn.gemm_pf_mode);
-      return;
-    }
-#endif
-    if (tpb > 1) {
-      static PerDeviceOnce attr_p;
-      if (attr_p.first())
-        (void)hipFuncSetAttribute((const void*)gemm_nt_ldp_kernel<HT, EPI, TMW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-      hipLaunchKernelGGL((gemm_nt_ldp_kernel<HT, EPI, TMW>), grid_, dim3(768), shmem, s, (const HT*)A, lda, (const HT*)B, ldb, M, N,
-                         K, e, pf_d_, kn.gemm_pf_mode, tpb);
-      return;
-    }
-    hipLaunchKernelGGL((gemm_nt_ld_kernel<HT, EPI, TMW>), grid, dim3(768), shmem, s, (const HT*)A, lda, (const HT*)B, ldb, M, N, K, e,
-                       pf_d_, kn.gemm_pf_mode);
-    return;
+  if (p.family != GEMM_PP8W && kn.gemm_ld1 == 1) {   // one barrier per contraction step (measured: +4.6 % isolated, +0.5 % in the step)
+    static PerDeviceOnce attr_l1;
+    if (attr_l1.first())
+      (void)hipFuncSetAttribute((const void*)gemm_nt_ld_kernel<HT, EPI, TMW, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+    hipLaunchKernelGGL((gemm_nt_ld_kernel<HT, EPI, TMW, true>), grid, dim3(768), shmem, s, (const HT*)A, lda, (const HT*)B, ldb, M, N, K, e,
+                       tiles > 256 ? kn.gemm_pf_mr : kn.gemm_pf, kn.gemm_pf_mode);
+    return true;
   }
-  if constexpr (TMW == 5)
-    hipLaunchKernelGGL((gemm_nt_pp_kernel<HT, EPI, TMW>), grid, dim3(512), shmem, s, (const HT*)A, lda, (const HT*)B, ldb, M, N, K, e);
-}
-
-// Which row-panel height: 160 (the default: 98 FLOP per staged byte) or 128 (85)?  What a launch costs is (rounds of co-resident
-// blocks) x (tiles a block walks) x (bytes a tile stages per step); M = 7984 (detection, B = 16 x 499 tokens) and M = 8000
-// (Perception Test) give 50 panels of 160 rows - 200 tiles per 1024 columns on 256 CUs - but 63 panels of 128: 252.
-static int pp_cost(int M, int N, int K, int bm) {
-  const int tiles_n = (N + PP_BN - 1) / PP_BN, tiles = ((M + bm - 1) / bm) * tiles_n;
-  int tpb = 1;
-  if (tiles > 256) {
-    const int want = (tiles + 255) / 256;
-    if (want <= 4 && tiles_n % want == 0 && tiles % want == 0 && K >= 128) tpb = want;
-  }
-  const int blocks = tiles / tpb, rounds = (blocks + 255) / 256;
-  return rounds * tpb * (bm + PP_BN);
-}
-static int pp_tmw(int M, int N, int K) {
-  const int force = tim_knobs().gemm_tmw;   // (A/B knob)
-  if (force == 4 || force == 5) return force;
-  return pp_cost(M, N, K, 128) * 100 < pp_cost(M, N, K, 160) * 97 ? 4 : 5;
+  return false;
 }
 
 }  // namespace
@@ -1589,12 +1545,6 @@ static int pp_tmw(int M, int N, int K) {
 // `fail` (out): the device word the stand-alone LayerNorm behind this launch takes as run_if (see the kernel's header).
 int tim_gemm_nt_pp_ln(int precision, const void* A, int lda, const void* B, int ldb, int M, int N, int K, const void* epi_dev,
                       const TimLnFuse& lf, const uint32_t** fail, hipStream_t s) {
-#ifndef TIMHIP_TUNING
-  // Product builds do not carry the fused kernel: measured 64.2 us (fused GEMM 59.5 + the stand-by LayerNorm launch 4.7) against
-  // 62.5 us for the two kernels, it stays a tuning-build experiment; the layer runs its two-kernel path.
-  (void)precision; (void)A; (void)lda; (void)B; (void)ldb; (void)M; (void)N; (void)K; (void)epi_dev; (void)lf; (void)fail; (void)s;
-  return TIMHIP_EUNSUPPORTED;
-#else
   const EpiDev& e = *reinterpret_cast<const EpiDev*>(epi_dev);
   constexpr int TMW = 5, BM = 32 * TMW;
   // (N: the widths the stand-by LayerNorm behind this launch supports - the same predicate, so the pair is all-or-nothing)
@@ -1636,79 +1586,35 @@ int tim_gemm_nt_pp_ln(int precision, const void* A, int lda, const void* B, int 
                                             ldb, M, N, K, e, f, tim_knobs().gemm_pf));
   if (fail) *fail = scr[dev].ctl;   // (run_if convention of tim_layernorm_fwd: see the kernel's header)
   return hipGetLastError() == hipSuccess ? TIMHIP_OK : TIMHIP_ELAUNCH;
-#endif
 }
-
-// Is this problem one for the ping-pong kernel?  It needs enough 160 x 256 tiles to fill the 256 CUs about evenly: the
-// encoder-layer GEMMs of a production batch (M = B * S in the thousands, N a multiple of 256 from 1024 up).
-bool tim_gemm_pp_wins(int M, int N, int K, int splitk) {
-  if (splitk != 1 || N < 512 || M < 1280) return false;
-  const long long tiles = (long long)((M + 159) / 160) * ((N + PP_BN - 1) / PP_BN);
-  const long long rounds = (tiles + 255) / 256;
-  if (tiles < 256) return tiles >= tim_knobs().gemm_pp_min;   // (TIMHIP_GEMM_PP_MIN_TILES: half-batch chains run 124-tile launches side by side)
-  return tiles * 100 >= rounds * 256 * 75;   // the last round at least three quarters full on average
+#else
+namespace {
+template <typename HT, int EPI>
+bool launch_pp_tuning(const GemmPlan&, const void*, int, const void*, int, int, int, int, const EpiDev&, hipStream_t) { return false; }
+}  // namespace
+// Product builds do not carry the fused kernel: measured 64.2 us (fused GEMM 59.5 + the stand-by LayerNorm launch 4.7) against
+// 62.5 us for the two kernels, it stays a tuning-build experiment; the layer runs its two-kernel path.
+int tim_gemm_nt_pp_ln(int, const void*, int, const void*, int, int, int, int, const void*, const TimLnFuse&, const uint32_t**, hipStream_t) {
+  return TIMHIP_EUNSUPPORTED;
 }
-
-// Shapes for the dual-group persistent kernel: whole 160 x 256 tile pairs, at least two contraction steps, an even spread of the
-// pairs over the blocks, vectorised epilogue operands.
-#ifdef TIMHIP_TUNING
-static bool tim_gemm_dg_ok(int M, int N, int K, const EpiDev& e) {
-  if (M % DG_BM || N % (2 * DG_BN) || K % 64 || K < 128 || !e.vec || !e.vec8) return false;
-  const int npairs = (M / DG_BM) * (N / (2 * DG_BN));
-  const int ppb = (npairs + 255) / 256;
-  return npairs >= 192 && npairs % ppb == 0;
-}
-
 #endif
 
-// (tests / tools: which row tile of the eight-phase kernel a plain launch of this shape and epilogue would take - 8, 10 or 0)
-int tim_gemm_p8_choice(int epi, int M, int N, int K) {
-  EpiDev e{};
-  return p8_choice(epi, M, N, K, e);
+// one launch of the families of this file, from its plan
+template <typename HT, int EPI>
+static void launch_plan(const GemmPlan& p, const void* A, int lda, const void* B, int ldb, int M, int N, int K, const EpiDev& e, hipStream_t s) {
+  if (launch_pp_tuning<HT, EPI>(p, A, lda, B, ldb, M, N, K, e, s)) return;
+  if constexpr (gemm_p8_carries(EPI)) {
+    if (p.family == GEMM_P8)
+      return p.tm == 8 ? launch_p8<HT, EPI, 8>(p, A, lda, B, ldb, M, N, K, e, s) : launch_p8<HT, EPI, 10>(p, A, lda, B, ldb, M, N, K, e, s);
+  }
+  return p.tm == 5 ? launch_pp<HT, EPI, 5>(p, A, lda, B, ldb, M, N, K, e, s) : launch_pp<HT, EPI, 4>(p, A, lda, B, ldb, M, N, K, e, s);
 }
 
-int tim_gemm_nt_pp(int precision, int epi, const void* A, int lda, const void* B, int ldb, int M, int N, int K, const void* epi_dev,
-                   hipStream_t s) {
+int tim_gemm_nt_pp(const GemmPlan& p, int precision, int epi, const void* A, int lda, const void* B, int ldb, int M, int N, int K,
+                   const void* epi_dev, hipStream_t s) {
   const EpiDev& e = *reinterpret_cast<const EpiDev*>(epi_dev);
-  if (!h16_storage(precision)) return TIMHIP_EUNSUPPORTED;
-  const bool tall = pp_tmw(M, N, K) == 5;
-#ifdef TIMHIP_TUNING
-  // TIMHIP_GEMM_DG=1 (tuning builds): the dual-group persistent kernel where the shape allows - measured 13 % slower over the
-  // layer's eight shapes than the one-tile-per-block kernel: its 160 x 128 group tiles stage 72 KiB per step pair where the
-  // 160 x 256 tile stages 52, and the global -> LDS path (~30 B/clk/CU), not the matrix pipe, is what bounds these loops; the hidden
-  // epilogues do not pay for that - DESIGN.md section 5c; TIMHIP_GEMM_DG_OFFSET: barriers group 1 runs behind group 0 (odd)
-  if (tim_knobs().gemm_dg == 1 && tim_gemm_dg_ok(M, N, K, e) && e.a_wrap == 0) {
-    int off = tim_knobs().gemm_dg_offset;
-    if (off < 1) off = 1;
-    off |= 1;
-    switch (epi) {
-#define CASE(X) case X: DISPATCH_H16(precision, (launch_dg<HT, X>(A, lda, B, ldb, M, N, K, e, off, s))); break;
-      CASE(TIMHIP_EPI_STORE_T)
-      CASE(TIMHIP_EPI_DROP_RES_F32)
-      CASE(TIMHIP_EPI_ADD_F32)
-      CASE(TIMHIP_EPI_GELU_DROP_G2)
-      CASE(TIMHIP_EPI_MULAUX_T)
-#undef CASE
-      default: goto plain;
-    }
-    return hipGetLastError() == hipSuccess ? TIMHIP_OK : TIMHIP_ELAUNCH;
-  }
-plain:
-#endif
-  if (const int tm8 = p8_choice(epi, M, N, K, e)) {
-    switch (epi) {
-#define CASE(X) case X: DISPATCH_H16(precision, (tm8 == 8 ? launch_p8<HT, X, 8>(A, lda, B, ldb, M, N, K, e, s) : launch_p8<HT, X, 10>(A, lda, B, ldb, M, N, K, e, s))); break;
-      CASE(TIMHIP_EPI_STORE_T)
-      CASE(TIMHIP_EPI_GELU_DROP_G2)
-      CASE(TIMHIP_EPI_GELU_T)
-      CASE(TIMHIP_EPI_MULAUX_T)
-#undef CASE
-      default: return TIMHIP_EUNSUPPORTED;
-    }
-    return hipGetLastError() == hipSuccess ? TIMHIP_OK : TIMHIP_ELAUNCH;
-  }
-  switch (epi) {
-#define CASE(X) case X: DISPATCH_H16(precision, (tall ? launch_pp<HT, X, 5>(A, lda, B, ldb, M, N, K, e, s) : launch_pp<HT, X, 4>(A, lda, B, ldb, M, N, K, e, s))); break;
+  switch (epi) {   // (the epilogues of gemm_pp_carries: the plan names this file's families for no other)
+#define CASE(X) case X: DISPATCH_H16(precision, (launch_plan<HT, X>(p, A, lda, B, ldb, M, N, K, e, s))); break;
     CASE(TIMHIP_EPI_STORE_T)
     CASE(TIMHIP_EPI_RELU_T)
     CASE(TIMHIP_EPI_STORE_F32)

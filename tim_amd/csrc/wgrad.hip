@@ -435,34 +435,31 @@ int tim_wgrad_group_h16(int precision, const TimWgradItem* it, int n, int M, int
   if (!it || n < 1 || n > WG_MAX || M <= 0) return TIMHIP_EINVAL;
   // The argument contract of the group (include/timhip.h) is the same whichever kernel runs it and is checked here, before any
   // launch: a group is refused as a whole, no item of it is written.
+  double flops = 0.0;
   for (int i = 0; i < n; ++i) {
     const TimWgradItem& t = it[i];
     if (!t.dY || !t.X || !t.dW || t.Nout <= 0 || t.Kout <= 0) return TIMHIP_EINVAL;
     if ((t.ldy % 8) || (t.ldx % 8) || (((uintptr_t)t.dY | (uintptr_t)t.X | (uintptr_t)t.dW) & 15)) return TIMHIP_EALIGN;
     if (((long long)t.Nout * t.Kout) & 3) return TIMHIP_EUNSUPPORTED;
+    flops += 2.0 * M * t.Nout * t.Kout;
   }
   // two encoder layers of a production batch: one round of eight-phase 256 x 256 tiles (wgrad_pp.hip; TIMHIP_WGRAD_P8=0: A/B switch)
   // The tiled grids have a limit of their own (32-bit byte offsets: M * ld * 2 < 2^32) that the kernel below does not: a group they
   // decline as TIMHIP_EUNSUPPORTED - before launching anything - falls through to it instead of failing the call.
   if (tim_wgrad_p8_wins(it, n, M)) {
-    double fl = 0.0;
-    for (int i = 0; i < n; ++i) fl += 2.0 * M * it[i].Nout * it[i].Kout;
-    TimGemmScope timing(fl, s);
+    TimGemmScope timing(flops, s);
     const int rc = tim_wgrad_group_p8(precision, it, n, M, accumulate, out_scale, s);
     if (rc != TIMHIP_EUNSUPPORTED) return rc;
   }
   // an encoder layer of a production batch: the one-block-per-CU ping-pong grid (wgrad_pp.hip; TIMHIP_WGRAD_PP=0: A/B switch)
   if (tim_knobs().wgrad_pp != 0 && tim_wgrad_pp_wins(it, n, M)) {
-    double fl = 0.0;
-    for (int i = 0; i < n; ++i) fl += 2.0 * M * it[i].Nout * it[i].Kout;
-    TimGemmScope timing(fl, s);
+    TimGemmScope timing(flops, s);
     const int rc = tim_wgrad_group_pp(precision, it, n, M, accumulate, out_scale, s);
     if (rc != TIMHIP_EUNSUPPORTED) return rc;
   }
   WgGroup g;
   g.n = n; g.M = M; g.accumulate = accumulate ? 1 : 0; g.out_scale = out_scale;
   g.tile0[0] = 0; g.off[0] = 0; g.boff[0] = 0;
-  double flops = 0.0;
   for (int i = 0; i < WG_MAX; ++i) {
     if (i >= n) {
       g.dY[i] = g.X[i] = nullptr; g.dW[i] = g.db[i] = nullptr; g.ldy[i] = g.ldx[i] = g.N[i] = g.K[i] = 0;
@@ -470,15 +467,11 @@ int tim_wgrad_group_h16(int precision, const TimWgradItem* it, int n, int M, int
       continue;
     }
     const TimWgradItem& t = it[i];
-    if (!t.dY || !t.X || !t.dW || t.Nout <= 0 || t.Kout <= 0) return TIMHIP_EINVAL;
-    if ((t.ldy % 8) || (t.ldx % 8) || (((uintptr_t)t.dY | (uintptr_t)t.X | (uintptr_t)t.dW) & 15)) return TIMHIP_EALIGN;
-    if (((long long)t.Nout * t.Kout) & 3) return TIMHIP_EUNSUPPORTED;
     g.dY[i] = t.dY; g.X[i] = t.X; g.dW[i] = t.dW; g.db[i] = t.db;
     g.ldy[i] = t.ldy; g.ldx[i] = t.ldx; g.N[i] = t.Nout; g.K[i] = t.Kout;
     g.tile0[i + 1] = g.tile0[i] + ((t.Nout + WT - 1) / WT) * ((t.Kout + WT - 1) / WT);
     g.off[i + 1] = g.off[i] + (long long)t.Nout * t.Kout;
     g.boff[i + 1] = g.boff[i] + (t.db ? t.Nout : 0);
-    flops += 2.0 * M * t.Nout * t.Kout;
   }
   const int sk = splits_for_tiles(g.tile0[n], M);
   const int nsteps = (M + WM - 1) / WM;
