@@ -382,6 +382,18 @@ int timhip_attention_fwd(const TimDesc* d, const void* qkv, void* o, float* lse,
  * bit for bit; 32-row blocks that lie wholly below s0 are not run.  With s0 = F: the query rows, all the last layer of an
  * evaluation forward needs once nobody reads `feats` (timhip_stack_infer, tail_only). */
 int timhip_attention_fwd_rows(const TimDesc* d, const void* qkv, int s0, void* o_rows, void* stream);
+/* Query rows against keys and values kept elsewhere (evaluation only; d->p_drop must be 0: TIMHIP_EINVAL).  d: B = G groups, S = Q
+ * rows per group, F = keys per window, E, H.  qkv_q [G Q, 3E] (T): q | own k | own v of the query rows.  kv: the K columns of row 0
+ * of window 0; V lies E elements behind K in the same row; ldkv: row pitch in elements (>= 2E); wrows: rows from one window to the
+ * next (>= F); W: windows.  A compact cache is ldkv = 2E, wrows = F; the qkv of timhip_attention_fwd is read in place with
+ * kv = qkv + E, ldkv = 3E, wrows = S.  widx (device, G ints; NULL: group g reads window g, G == W required - else TIMHIP_EINVAL).
+ * Every row runs the softmax over the F keys of window widx[g] plus its own key: o[g Q + i, :] = sum_j p_j V_j + p_self v_own -
+ * the arithmetic of timhip_attention_fwd's kernels (one shared body), so the rows equal that call's query rows bit for bit on
+ * equal inputs: the matrix-core kernel for 16-bit precisions and the shapes it is built for, the fp32-arithmetic kernel for
+ * everything else (fp32 / bf16x3 included: there the equal bits are those of timhip_attention_fwd under TIMHIP_DESC_ATTN_FP32).
+ * A widx[g] outside [0, W): nothing is read through it and the group's o rows are quiet NaNs. */
+int timhip_attention_query_fwd(const TimDesc* d, const void* qkv_q, const void* kv, int ldkv, int wrows, int W, const int* widx,
+                               void* o, void* stream);
 /* The attention WEIGHTS of those rows - what the reference's TransformerEncoder.forward returns beside its output (transformers.py:
  * 45-48: nn.MultiheadAttention's head-averaged softmax weights) and the kernels above keep in registers.  A token attends to the F
  * feature tokens and to itself, so a row has F + 1 entries: w[b * (S - s0) + (s - s0), j] (fp32, row pitch ld >= F + 1 floats;
@@ -512,6 +524,35 @@ size_t timhip_stack_infer_maps_workspace_bytes(const TimDesc* d, int nlayers, in
 int timhip_stack_infer_maps(const TimDesc* d, int nlayers, const TimLayerParams* layers, const float* x_in, const void* x_in_T,
                             float* x_out, void* x_out_T, int tail_only, float* const* maps, int maps_s0, int ld,
                             void* workspace, size_t workspace_bytes, void* stream);
+/* ---- encode a window once, query it many times (evaluation only) ----
+ * Under TIM's mask the feature rows of a window never read a query row, and a query row reads the F feature rows' keys and values
+ * plus its own: the stack can run on the feature rows alone, keep every layer's K | V columns, and later run any number of query
+ * rows against them.
+ *
+ * timhip_stack_encode: timhip_stack_infer (tail_only = 0) on feature rows only - d: B = W windows, S = F.  x_in / x_in_T: the
+ * [W F, E] assembled feature rows.  Behind layer l's launches the K | V columns of its qkv are copied (one pitched device copy per
+ * layer: 2/3 of qkv read and written) into cache + l * W F 2E elements: cache is [nlayers][W F][2 E] in the operand dtype,
+ * timhip_window_cache_bytes(d, nlayers) bytes (0 for a descriptor the call refuses), 16-byte aligned (TIMHIP_EALIGN).
+ * feats_out (fp32 [W F, E], may be NULL): the last layer's output rows - the `feats` of a full forward.  S != F, NULL cache:
+ * TIMHIP_EINVAL.  workspace: timhip_stack_infer_workspace_bytes(d, nlayers, 0).
+ *
+ * timhip_stack_query: all nlayers layers on query rows only - d: B = G groups, S = Q query rows per group, F = the cached keys per
+ * window (Q < F is fine).  Group g reads window widx[g] of the W cached ones (widx: device, G entries; NULL: window g, G == W
+ * required).  Per layer: in-projection of the G Q rows (q | own k | own v), timhip_attention_query_fwd against cache block l,
+ * out-projection + residual, LayerNorm, FFN, LayerNorm as timhip_stack_infer chains them.  xq_in / xq_in_T: the [G Q, E] assembled
+ * query rows; xq_out (fp32, may be NULL) / xq_out_T (T): the last layer's rows - what a full forward computes for these tokens, up
+ * to the tiles the GEMMs pick at this row count.  workspace: timhip_stack_query_workspace_bytes(d, nlayers), one layer's arena for
+ * G Q rows.  Refused before the first launch: NULL pointers, p_drop != 0, W <= 0, NULL widx with G != W - TIMHIP_EINVAL; F > 192 -
+ * TIMHIP_EUNSUPPORTED; a short workspace - TIMHIP_EWORKSPACE.  An entry of widx outside [0, W) is not an error the host can see:
+ * that group's rows come out as NaN and nothing is read through the index (timhip_attention_query_fwd).
+ * Both: launches and device copies only, one stream, no events, no allocation - capturable as a linear graph. */
+size_t timhip_window_cache_bytes(const TimDesc* d, int nlayers);
+int timhip_stack_encode(const TimDesc* d, int nlayers, const TimLayerParams* layers, const float* x_in, const void* x_in_T,
+                        float* feats_out, void* cache, void* workspace, size_t workspace_bytes, void* stream);
+size_t timhip_stack_query_workspace_bytes(const TimDesc* d, int nlayers);
+int timhip_stack_query(const TimDesc* d, int nlayers, const TimLayerParams* layers, const void* cache, int W, const int* widx,
+                       const float* xq_in, const void* xq_in_T, float* xq_out, void* xq_out_T, void* workspace,
+                       size_t workspace_bytes, void* stream);
 /* dx_out: gradient w.r.t. the layer output (fp32 [M,E]).  dx_in: gradient w.r.t. the
  * layer input (fp32 [M,E]).  Parameter gradients are accumulated (+=) into *g.
  * This is timhip_layer_bwd_split (below: the form tim_amd calls) with dx_out_add = dx_in_add = NULL. */

@@ -34,6 +34,9 @@ def __getattr__(name):  # lazy: importing the package must not require torch on 
     if name == "AttentionMaps":
         from .attn_maps import AttentionMaps
         return AttentionMaps
+    if name == "WindowCache":
+        from .query import WindowCache
+        return WindowCache
     if name == "optim":
         import importlib
         return importlib.import_module(".optim", __name__)

@@ -132,6 +132,11 @@ _SIGS = {
                                        f32, u64, u32, vp, vp, vp, vp]),
     "timhip_attention_fwd": (C.c_int, [C.POINTER(TimDesc), vp, vp, vp, vp]),
     "timhip_attention_fwd_rows": (C.c_int, [C.POINTER(TimDesc), vp, i32, vp, vp]),
+    "timhip_attention_query_fwd": (C.c_int, [C.POINTER(TimDesc), vp, vp, i32, i32, i32, vp, vp, vp]),
+    "timhip_window_cache_bytes": (sz, [C.POINTER(TimDesc), i32]),
+    "timhip_stack_encode": (C.c_int, [C.POINTER(TimDesc), i32, C.POINTER(TimLayerParams), vp, vp, vp, vp, vp, sz, vp]),
+    "timhip_stack_query_workspace_bytes": (sz, [C.POINTER(TimDesc), i32]),
+    "timhip_stack_query": (C.c_int, [C.POINTER(TimDesc), i32, C.POINTER(TimLayerParams), vp, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
     "timhip_attention_weights": (C.c_int, [C.POINTER(TimDesc), vp, i32, i32, vp, i32, vp]),
     "timhip_attention_bwd": (C.c_int, [C.POINTER(TimDesc), vp, vp, vp, vp, vp, vp, sz, vp]),
     "timhip_attention_bwd_workspace_bytes": (sz, [C.POINTER(TimDesc)]),

@@ -351,16 +351,20 @@ int timhip_wgrad(int precision, const void* dY, int ldy, int Nout, const void* X
 //   lse == NULL    attention skips its log-sum-exp store
 //   s0 > 0         "tail": everything behind the in-projection runs on the token rows s0 .. S - 1 of every window only, compactly
 //                  (B (S - s0) rows: o, y1, x1t, h, y2, the outputs - and the residual rows the caller hands in)
+//   kv != NULL     every row is a query row of one of d.B groups: its keys and values are the K | V rows of window widx[g] of a
+//                  cache (timhip_stack_query; tim_attention_query_fwd) plus its own.  d.F: the cached keys per window (may exceed d.S)
 struct LayerBufs {
   void* qkv; void* o; float* lse; float* y1; float* st1; void* x1t; void* u; void* h; float* y2; float* st2;
   uint8_t* ffn_mask; const unsigned long long* attn_keep;
+  const void* kv; int ldkv, wrows, W; const int* widx;
 };
 
 static LayerBufs saved_bufs(const TimDesc& d, void* saved) {
   const SavedLayout L = saved_layout(d);
   return LayerBufs{L.qkv.at(saved), L.o.at(saved), (float*)L.lse.at(saved), (float*)L.y1.at(saved), (float*)L.st1.at(saved),
                    L.x1t.at(saved), L.u.at(saved), L.h.at(saved), (float*)L.y2.at(saved), (float*)L.st2.at(saved),
-                   (uint8_t*)L.ffn_mask.at(saved), reinterpret_cast<const unsigned long long*>(L.attn_keep.at(saved))};
+                   (uint8_t*)L.ffn_mask.at(saved), reinterpret_cast<const unsigned long long*>(L.attn_keep.at(saved)),
+                   nullptr, 0, 0, 0, nullptr};
 }
 
 static int layer_fwd_body(const TimDesc& d, const TimLayerParams* w, const float* x_in, const float* x_in_prenorm,
@@ -378,7 +382,9 @@ static int layer_fwd_body(const TimDesc& d, const TimLayerParams* w, const float
   e.out0 = qkv; e.ld0 = 3 * E; e.bias = w->in_b;
   if ((rc = linear_fwd(prec, TIMHIP_EPI_STORE_T, x_in_T, w->in_w, Mall, 3 * E, E, split(TIMHIP_DESC_INPROJ_SPLIT), e, s))) return rc;
   // 2. structured attention (keys and values of all rows; the rows from s0 on)
-  if ((rc = tim_attention_fwd(d, qkv, o, bufs.lse, s, layer_pass(d, bufs.attn_keep).akeep, s0))) return rc;
+  if (bufs.kv) {
+    if ((rc = tim_attention_query_fwd(d, qkv, bufs.kv, bufs.ldkv, bufs.wrows, bufs.W, bufs.widx, o, s))) return rc;
+  } else if ((rc = tim_attention_fwd(d, qkv, o, bufs.lse, s, layer_pass(d, bufs.attn_keep).akeep, s0))) return rc;
   // 3. out-projection + dropout1 + residual
   e = epi0();
   e.out0 = y1; e.ld0 = E; e.bias = w->out_b; e.ldres = E;
@@ -490,8 +496,8 @@ size_t timhip_stack_infer_workspace_bytes(const TimDesc* d, int nlayers, int tai
 // layer l's launches - its qkv is live in the arena until layer l + 1's in-projection - the weights kernel writes maps[l].
 static int stack_infer_body(const TimDesc* dp, int nlayers, const TimLayerParams* layers, const float* x_in, const void* x_in_T,
                             float* x_out, void* x_out_T, int tail_only, float* const* maps, int maps_s0, int ld,
-                            void* workspace, size_t workspace_bytes, void* stream) {
-  if (!dp || !layers || nlayers <= 0 || !x_in || !x_in_T || !x_out_T || !workspace) return TIMHIP_EINVAL;
+                            void* workspace, size_t workspace_bytes, void* stream, void* kv_cache = nullptr) {
+  if (!dp || !layers || nlayers <= 0 || !x_in || !x_in_T || (!x_out_T && !kv_cache) || !workspace) return TIMHIP_EINVAL;
   TimDesc d = *dp;
   int rc = check_layer_desc(d);
   if (rc) return rc;
@@ -507,7 +513,7 @@ static int stack_infer_body(const TimDesc* dp, int nlayers, const TimLayerParams
   hipStream_t s = (hipStream_t)stream;
   void* ws = workspace;
   const LayerBufs bufs{L.qkv.at(ws), L.o.at(ws), nullptr, (float*)L.y1.at(ws), (float*)L.st1.at(ws), L.x1t.at(ws), nullptr,
-                       L.h.at(ws), (float*)L.y2.at(ws), (float*)L.st2.at(ws), nullptr, nullptr};
+                       L.h.at(ws), (float*)L.y2.at(ws), (float*)L.st2.at(ws), nullptr, nullptr, nullptr, 0, 0, 0, nullptr};
   d.reserved &= ~TIMHIP_DESC_ATTN_KEEP_BITS;
   for (int l = 0; l < nlayers; ++l) {
     const bool last = l == nlayers - 1;
@@ -525,8 +531,15 @@ static int stack_infer_body(const TimDesc* dp, int nlayers, const TimLayerParams
     }
     const void* in_T = l == 0 ? x_in_T : (const void*)L.xt.at(ws);
     if ((rc = layer_fwd_body(d, &layers[l], res, pre, pst, l ? layers[l - 1].n2_w : nullptr, l ? layers[l - 1].n2_b : nullptr, in_T,
-                             last ? x_out : nullptr, last ? x_out_T : (void*)L.xt.at(ws), bufs, s0, s))) return rc;
+                             last ? x_out : nullptr, (last && x_out_T) ? x_out_T : (void*)L.xt.at(ws), bufs, s0, s))) return rc;
     if (maps && maps[l] && (rc = tim_attention_weights(d, bufs.qkv, maps_s0, 0, maps[l], ld, s))) return rc;
+    // kv_cache (timhip_stack_encode: S == F, every row a feature row): the K | V columns of the layer's qkv - live in the arena until
+    // the next in-projection - as rows of 2 E elements into block l of the cache; one pitched device copy, 2/3 of qkv read and written
+    if (kv_cache) {
+      const size_t ts = opsize(d.precision), rowb = (size_t)2 * d.E * ts, rows = (size_t)d.B * d.S;
+      if (hipMemcpy2DAsync((char*)kv_cache + (size_t)l * rows * rowb, rowb, (const char*)bufs.qkv + (size_t)d.E * ts, (size_t)3 * d.E * ts,
+                           rowb, rows, hipMemcpyDeviceToDevice, s) != hipSuccess) return TIMHIP_ELAUNCH;
+    }
   }
   return TIMHIP_OK;
 }
@@ -548,6 +561,66 @@ int timhip_stack_infer_maps(const TimDesc* dp, int nlayers, const TimLayerParams
   if (!maps) return TIMHIP_EINVAL;
   return stack_infer_body(dp, nlayers, layers, x_in, x_in_T, x_out, x_out_T, tail_only, maps, maps_s0, ld, workspace,
                           workspace_bytes, stream);
+}
+
+// ---- encode a window once, query it many times (timhip_stack_encode / timhip_stack_query) -----------------------------------------
+// The feature rows of a window never read a query row, and a query row reads the feature rows' keys and values and itself: the
+// stack on the feature rows alone (S == F) is the feature stream of a full forward, and its per-layer K | V columns are all a later
+// pass over query rows needs.  cache: [nlayers][W F][2 E] in the operand dtype.
+size_t timhip_window_cache_bytes(const TimDesc* d, int nlayers) {
+  if (!d || nlayers <= 0 || check_layer_desc(*d) != TIMHIP_OK || d->S != d->F) return 0;
+  return (size_t)nlayers * d->B * d->F * 2 * d->E * opsize(d->precision);
+}
+
+int timhip_stack_encode(const TimDesc* dp, int nlayers, const TimLayerParams* layers, const float* x_in, const void* x_in_T,
+                        float* feats_out, void* cache, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!dp || !cache || dp->S != dp->F) return TIMHIP_EINVAL;
+  if (((uintptr_t)cache & 15) != 0) return TIMHIP_EALIGN;
+  return stack_infer_body(dp, nlayers, layers, x_in, x_in_T, feats_out, nullptr, 0, nullptr, 0, 0, workspace, workspace_bytes, stream,
+                          cache);
+}
+
+// a query descriptor: B = groups, S = query rows per group, F = cached keys per window (no relation to S)
+static int check_query_desc(const TimDesc& d) {
+  if (d.F <= 0) return TIMHIP_EINVAL;
+  TimDesc c = d;
+  c.F = 1;
+  return check_layer_desc(c);
+}
+
+size_t timhip_stack_query_workspace_bytes(const TimDesc* d, int nlayers) {
+  (void)nlayers;   // (one layer's arena, as timhip_stack_infer_workspace_bytes)
+  return (d && check_query_desc(*d) == TIMHIP_OK) ? infer_layout(*d, 0).total : 0;
+}
+
+int timhip_stack_query(const TimDesc* dp, int nlayers, const TimLayerParams* layers, const void* cache, int W, const int* widx,
+                       const float* xq_in, const void* xq_in_T, float* xq_out, void* xq_out_T, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+  if (!dp || !layers || nlayers <= 0 || !cache || !xq_in || !xq_in_T || !xq_out_T || !workspace) return TIMHIP_EINVAL;
+  TimDesc d = *dp;
+  int rc = check_query_desc(d);
+  if (rc) return rc;
+  if (d.p_drop != 0.f || W <= 0 || (!widx && d.B != W)) return TIMHIP_EINVAL;
+  if (d.F > 192) return TIMHIP_EUNSUPPORTED;   // (the attention kernels' key limit; refused here, before the first launch)
+  if (((uintptr_t)cache & 15) != 0) return TIMHIP_EALIGN;
+  const InferLayout L = infer_layout(d, 0);
+  if (workspace_bytes < L.total) return TIMHIP_EWORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  void* ws = workspace;
+  LayerBufs bufs{L.qkv.at(ws), L.o.at(ws), nullptr, (float*)L.y1.at(ws), (float*)L.st1.at(ws), L.x1t.at(ws), nullptr,
+                 L.h.at(ws), (float*)L.y2.at(ws), (float*)L.st2.at(ws), nullptr, nullptr, nullptr, 2 * d.E, d.F, W, widx};
+  d.reserved &= ~TIMHIP_DESC_ATTN_KEEP_BITS;
+  const size_t layer_bytes = (size_t)W * d.F * 2 * d.E * opsize(d.precision);
+  for (int l = 0; l < nlayers; ++l) {
+    const bool last = l == nlayers - 1;
+    d.layer = l;
+    bufs.kv = (const char*)cache + (size_t)l * layer_bytes;
+    if ((rc = layer_fwd_body(d, &layers[l], l == 0 ? xq_in : nullptr, l == 0 ? nullptr : bufs.y2, l == 0 ? nullptr : bufs.st2,
+                             l ? layers[l - 1].n2_w : nullptr, l ? layers[l - 1].n2_b : nullptr,
+                             l == 0 ? xq_in_T : (const void*)L.xt.at(ws), last ? xq_out : nullptr,
+                             last ? xq_out_T : (void*)L.xt.at(ws), bufs, 0, s))) return rc;
+  }
+  return TIMHIP_OK;
 }
 
 size_t timhip_layer_ln_partial_bytes(const TimDesc* d) { return d ? 2 * tim_layernorm_bwd_ws(d->B * d->S, d->E) : 0; }

@@ -11,89 +11,10 @@
 
 namespace {
 
-__device__ __forceinline__ float attn_keep(const AttnArgs& a, int b, int h, int row, int j) {
-  if (a.thr == 0u) return 1.f;
-  const uint64_t base = (((uint64_t)b * a.H + h) * a.S + row) * (uint64_t)a.LP + (uint64_t)j;
-  return drop_mask1(a.seed, a.site, base, a.thr, a.dscale);
-}
-
-constexpr int KPL = 3;  // keys per lane: F <= 192
-
 template <typename T>
 __global__ __launch_bounds__(256) void attn_fwd_simple(const T* __restrict__ qkv, T* __restrict__ o,
                                                        float* __restrict__ lse, AttnArgs a) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int b = blockIdx.x / a.H, h = blockIdx.x % a.H;
-  const int Dh = a.Dh, F = a.F, S = a.S, E = a.E;
-  const int KS = Dh + (sizeof(T) == 2 ? 2 : 1);
-  T* sK = reinterpret_cast<T*>(smem);
-  T* sV = sK + (size_t)F * KS;
-  float* sQ = reinterpret_cast<float*>(smem + align_up((size_t)2 * F * KS * sizeof(T), 16));
-  float* sP = sQ + 4 * Dh;
-  const int PP = F + 4;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const size_t ld = (size_t)3 * E;
-  const T* base = qkv + (size_t)b * S * ld + (size_t)h * Dh;
-  for (int idx = tid; idx < F * Dh; idx += 256) {
-    const int j = idx / Dh, c = idx % Dh;
-    sK[j * KS + c] = base[(size_t)j * ld + E + c];
-    sV[j * KS + c] = base[(size_t)j * ld + 2 * E + c];
-  }
-  __syncthreads();
-  for (int r0 = a.s0; r0 < S; r0 += 4) {
-    const int row = r0 + wave;
-    const bool active = row < S;
-    const T* qp = base + (size_t)(active ? row : 0) * ld;
-    for (int c = lane; c < Dh; c += 64) sQ[wave * Dh + c] = OpT<T>::to_f(qp[c]) * a.scale;
-    __syncthreads();
-    float sc[KPL];
-    float mx = -INFINITY;
-#pragma unroll
-    for (int kk = 0; kk < KPL; ++kk) {
-      const int j = lane + 64 * kk;
-      float s = -INFINITY;
-      if (j < F) {
-        s = 0.f;
-        for (int c = 0; c < Dh; ++c) s = fmaf(sQ[wave * Dh + c], OpT<T>::to_f(sK[j * KS + c]), s);
-      }
-      sc[kk] = s;
-      mx = fmaxf(mx, s);
-    }
-    const bool isq = row >= F;
-    float sself = -INFINITY;
-    if (isq && active) {
-      float t = 0.f;
-      for (int c = lane; c < Dh; c += 64) t = fmaf(sQ[wave * Dh + c], OpT<T>::to_f(qp[E + c]), t);
-      sself = wave_sum(t);
-    }
-    mx = fmaxf(wave_max(mx), sself);
-    float sum = 0.f;
-#pragma unroll
-    for (int kk = 0; kk < KPL; ++kk) {
-      sc[kk] = (lane + 64 * kk < F) ? __expf(sc[kk] - mx) : 0.f;
-      sum += sc[kk];
-    }
-    const float pself_un = isq ? __expf(sself - mx) : 0.f;
-    sum = wave_sum(sum) + pself_un;
-    const float inv = 1.f / sum;
-    if (active && lane == 0 && lse) lse[((size_t)b * a.H + h) * S + row] = mx + __logf(sum);
-#pragma unroll
-    for (int kk = 0; kk < KPL; ++kk) {
-      const int j = lane + 64 * kk;
-      if (j < F) sP[wave * PP + j] = sc[kk] * inv * (active ? attn_keep(a, b, h, row, j) : 0.f);
-    }
-    const float pself = (isq && active) ? pself_un * inv * attn_keep(a, b, h, row, F) : 0.f;
-    __syncthreads();
-    if (active) {
-      for (int c = lane; c < Dh; c += 64) {
-        float acc = 0.f;
-        for (int j = 0; j < F; ++j) acc = fmaf(sP[wave * PP + j], OpT<T>::to_f(sV[j * KS + c]), acc);
-        if (isq) acc = fmaf(pself, OpT<T>::to_f(qp[2 * E + c]), acc);
-        o[((size_t)b * (S - a.s0) + (row - a.s0)) * E + (size_t)h * Dh + c] = OpT<T>::from_f(acc);
-      }
-    }
-    __syncthreads();
-  }
+  attn_fwd_simple_body<T, false>(qkv, o, lse, a, AttnQuerySrc{});
 }
 
 // Backward, one block per (window, head):
@@ -203,13 +124,6 @@ __global__ __launch_bounds__(256) void attn_bwd_simple(const T* __restrict__ qkv
       dbase[(size_t)j * ld + 2 * E + c] = OpT<T>::from_f(av);
     }
   }
-}
-
-size_t simple_lds(const TimDesc& d, int nrowbuf) {
-  const int Dh = d.E / d.H;
-  const size_t ts = opsize(d.precision);
-  const int KS = Dh + (ts == 2 ? 2 : 1);
-  return align_up((size_t)2 * d.F * KS * ts, 16) + (size_t)nrowbuf * 4 * Dh * 4 + (size_t)4 * (d.F + 4) * 4;
 }
 
 int check_desc(const TimDesc& d) {

@@ -32,219 +32,7 @@ namespace {
 template <typename HT, int DH, int NJB, bool KB = false>
 __global__ __launch_bounds__(512) void attn_fwd_mfma(const HT* __restrict__ qkv, HT* __restrict__ o,
                                                      float* __restrict__ lse, AttnArgs a) {
-  constexpr int FP = NJB * 32, NKK = DH / 16, NDB = DH / 32;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* sK = smem;
-  char* sV = smem + FP * DH * 2;
-  // (window, head) = blockIdx.x / rsplit; a long sequence (detection: S = 499, B * H = 128) spreads its row blocks over rsplit
-  // workgroups that each stage the K / V tile themselves (51 KB from L2) - 128 workgroups would leave half of the 256 CUs idle
-  const int bh = blockIdx.x / a.rsplit, part = blockIdx.x - bh * a.rsplit;
-  const int b = bh / a.H, h = bh % a.H;
-  const int S = a.S, F = a.F, E = a.E;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const size_t ld = (size_t)3 * E;
-  const HT* base = qkv + (size_t)b * S * ld + (size_t)h * DH;
-  const int li = lane & 31, g = lane >> 5;
-  const int rb0 = a.s0 >> 5;
-  const int nrb = min((S + 31) >> 5, rb0 + (part + 1) * a.rper);
-  const int nwaves = blockDim.x >> 6;
-  // (five key blocks - F > 128 - hold 80 score registers per lane: no room for operands in flight, the requests stay where
-  //  they are consumed)
-  constexpr bool PRE = NJB <= 4;
-  // Operand prefetch (round 4).  The block used to run a chain of dependent memory latencies - K tile, V tile, then per row
-  // block its q / self-k rows, its self-v rows at the store - with two workgroups per CU to hide them: 31.5 us for 82 MB.  Now
-  // every load is issued as early as its registers allow: the first row block's q / self-k rows BEFORE the K / V staging
-  // loads (one latency for all three), K and V staged as a pair, the self-v rows and the NEXT row block's q / self-k rows
-  // right after the S^T products (under the softmax and the P V products).
-  auto load_rows = [&](int rbx, vec8<HT> (&qf)[NKK], vec8<HT> (&kself)[NKK]) {
-    const int rowx = min(rbx * 32 + li, S - 1);
-    const HT* qx = base + (size_t)rowx * ld;
-#pragma unroll
-    for (int kk = 0; kk < NKK; ++kk) qf[kk] = *reinterpret_cast<const vec8<HT>*>(qx + kk * 16 + g * 8);
-    if (!PRE || rowx >= F) {   // (feature tokens have no self term; without operand prefetch the plain unconditional form)
-#pragma unroll
-      for (int kk = 0; kk < NKK; ++kk) kself[kk] = *reinterpret_cast<const vec8<HT>*>(qx + E + kk * 16 + g * 8);
-    }
-  };
-  // one 32-row block of queries; qf / kself: its q rows and (query tokens) own-key rows, already requested
-  auto row_block = [&](int rb, vec8<HT> (&qf)[NKK], vec8<HT> (&kself)[NKK]) {
-    const int row = rb * 32 + li;
-    const bool valid = row < S && row >= a.s0;   // (rows of the first block below s0: computed like the padding rows, not stored)
-    const int rowc = row < S ? row : S - 1;
-    const bool isq = rowc >= F;
-    const HT* qp = base + (size_t)rowc * ld;
-    unsigned long long kw = 0ull;   // KB: this lane's keep-bits, bit 4 c + t = key 8 c + 4 g + t (requested ahead of the products)
-    if constexpr (KB) kw = a.kbits[((((size_t)b * a.H + h) * S + rowc) << 1) + g];
-
-    // S^T = K Q^T : lane owns query row `row`, registers hold keys 32jb + (r&3) + 8(r>>2) + 4g
-    f32x16_t sc[NJB];
-#pragma unroll
-    for (int jb = 0; jb < NJB; ++jb) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) sc[jb][r] = 0.f;
-#pragma unroll
-      for (int kk = 0; kk < NKK; ++kk) {
-        const vec8<HT> kf = *reinterpret_cast<const vec8<HT>*>(sK + tile_off<DH>(jb * 32 + li, kk * 2 + g));
-        sc[jb] = mfma16<HT>(kf, qf[kk], sc[jb]);
-      }
-      __builtin_amdgcn_sched_barrier(0);  // keep the K-fragment reads of later key blocks from being hoisted
-    }
-    // self score of query tokens (raw, unscaled like sc)
-    float sself = -INFINITY;
-    {
-      float t = 0.f;
-      if (isq) {
-#pragma unroll
-        for (int kk = 0; kk < NKK; ++kk) t += dot8(qf[kk], kself[kk]);
-      }
-      const float other = __shfl_xor(t, 32, 64);
-      if (isq) sself = t + other;
-    }
-    // only the last key block can hold padded keys
-    {
-      constexpr int jb = NJB - 1;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int key = jb * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
-        if (key >= F) sc[jb][r] = -INFINITY;
-      }
-    }
-    float mx = sself;
-#pragma unroll
-    for (int jb = 0; jb < NJB; ++jb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sc[jb][r]);
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    // p = exp(scale*(s - mx)) = exp2(c*s - c*mx)
-    const float c2 = a.scale * 1.4426950408889634f;
-    const float mc = mx * c2;
-    float sum = 0.f;
-#pragma unroll
-    for (int jb = 0; jb < NJB; ++jb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float p = __builtin_amdgcn_exp2f(fmaf(sc[jb][r], c2, -mc));
-        sc[jb][r] = p;
-        sum += p;
-      }
-    sum += __shfl_xor(sum, 32, 64);
-    const float pself_un = isq ? __builtin_amdgcn_exp2f(fmaf(sself, c2, -mc)) : 0.f;
-    sum += pself_un;
-    const float inv = 1.f / sum;
-    if (valid && g == 0 && lse) lse[((size_t)b * a.H + h) * S + row] = mx * a.scale + __logf(sum);
-    const uint64_t rowbase = (((uint64_t)b * a.H + h) * S + rowc) * (uint64_t)a.LP;
-#pragma unroll
-    for (int jb = 0; jb < NJB; ++jb)
-#pragma unroll
-      for (int qp = 0; qp < 2; ++qp) {
-        float ka[4] = {1.f, 1.f, 1.f, 1.f}, kb[4] = {1.f, 1.f, 1.f, 1.f};
-        if constexpr (KB) {
-          const int w32 = (int)(uint32_t)(kw >> (32 * (jb >> 1)));   // keys of key blocks 2 (jb >> 1), + 1: one dword
-          const int ds = __float_as_int(a.dscale);
-#pragma unroll
-          for (int t = 0; t < 4; ++t) {
-            ka[t] = __int_as_float(__builtin_amdgcn_sbfe(w32, 16 * (jb & 1) + 8 * qp + t, 1) & ds);
-            kb[t] = __int_as_float(__builtin_amdgcn_sbfe(w32, 16 * (jb & 1) + 8 * qp + 4 + t, 1) & ds);
-          }
-        } else if (a.thr != 0u) keep_pair(a, rowbase, jb * 32 + 16 * qp, g, ka, kb);   // (both lanes of a pair take this branch)
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          sc[jb][8 * qp + t] *= inv * ka[t];
-          sc[jb][8 * qp + 4 + t] *= inv * kb[t];
-        }
-      }
-    float pself = pself_un * inv;
-    if (isq && a.thr != 0u) pself *= keep1(a, rowbase, F);
-
-    // O^T = V^T P^T.  P is packed to bf16 first (frees the fp32 score registers); the head dim is
-    // processed in halves so only NDB/2 accumulator tiles are live at a time.
-    vec8<HT> pf[NJB][2];
-#pragma unroll
-    for (int jb = 0; jb < NJB; ++jb) {
-      pf[jb][0] = pack8<HT>(sc[jb], 0);
-      pf[jb][1] = pack8<HT>(sc[jb], 1);
-    }
-    // the self-v rows of this block (used at the store) go out now - the score registers are free - under the P V products
-    vec8<HT> vself[NKK];
-    if (PRE && isq) {
-#pragma unroll
-      for (int kk = 0; kk < NKK; ++kk) vself[kk] = *reinterpret_cast<const vec8<HT>*>(qp + 2 * E + kk * 16 + g * 8);
-    }
-    constexpr int NH = NDB >= 2 ? 2 : 1, DBH = NDB / NH;
-    HT* op = o + ((size_t)b * (S - a.s0) + (valid ? row - a.s0 : 0)) * E + (size_t)h * DH;
-#pragma unroll
-    for (int hh = 0; hh < NH; ++hh) {
-      f32x16_t oa[DBH];
-#pragma unroll
-      for (int d2 = 0; d2 < DBH; ++d2)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) oa[d2][r] = 0.f;
-#pragma unroll
-      for (int jb = 0; jb < NJB; ++jb)
-#pragma unroll
-        for (int aa = 0; aa < 2; ++aa)
-#pragma unroll
-          for (int d2 = 0; d2 < DBH; ++d2) {
-            const vec8<HT> vf = tr_frag<DH, HT>(sV, jb * 32 + 16 * aa, hh * DBH + d2, lane);
-            oa[d2] = mfma16<HT>(vf, pf[jb][aa], oa[d2]);
-            if (d2 == DBH - 1 && aa == 1) __builtin_amdgcn_sched_barrier(0);
-          }
-      // lanes l and l ^ 32 trade quads so that each stores 8 contiguous head-dim columns (16 bytes) per pair of quads;
-      // the exchange is executed by every lane (shuffles), the store only by valid rows
-#pragma unroll
-      for (int d2 = 0; d2 < DBH; ++d2)
-#pragma unroll
-        for (int p2 = 0; p2 < 2; ++p2) {
-          float v[8];
-          pair_exchange(v, oa[d2][8 * p2], oa[d2][8 * p2 + 1], oa[d2][8 * p2 + 2], oa[d2][8 * p2 + 3], oa[d2][8 * p2 + 4],
-                        oa[d2][8 * p2 + 5], oa[d2][8 * p2 + 6], oa[d2][8 * p2 + 7], g);
-          const int dh = 32 * (hh * DBH + d2) + 16 * p2 + 8 * g;
-          if (valid) {
-            if (isq) {
-              // columns dh .. dh + 7 = 16 (dh / 16) + 8 g: the chunk requested above (PRE), or read here
-              const vec8<HT> sv = PRE ? vself[2 * (hh * DBH + d2) + p2] : *reinterpret_cast<const vec8<HT>*>(qp + 2 * E + dh);
-#pragma unroll
-              for (int u = 0; u < 8; ++u) v[u] = fmaf(pself, (float)sv[u], v[u]);
-            }
-            store8_h<HT>(op + dh, v);
-          }
-        }
-    }
-  };
-
-  // The wave's first row block is peeled out of the loop: its operands were requested before the K / V staging, and keeping
-  // them in registers of their own (not loop-carried) is what lets the compiler fit the kernel without spills.
-  int rb = rb0 + part * a.rper + wave;
-  if constexpr (!PRE) {   // the plain loop: operands requested where they are consumed
-    stage_tile<DH>(sK, base + E, ld, FP, F, tid, blockDim.x);
-    stage_tile<DH>(sV, base + 2 * E, ld, FP, F, tid, blockDim.x);
-    __syncthreads();
-    for (; rb < nrb; rb += nwaves) {
-      vec8<HT> q1[NKK], k1[NKK];
-      load_rows(rb, q1, k1);
-      row_block(rb, q1, k1);
-    }
-    return;
-  }
-  {
-    vec8<HT> q0[NKK], k0[NKK];
-    if (PRE && rb < nrb) load_rows(rb, q0, k0);
-    if constexpr (PRE) {
-      stage_tile_pair<DH>(sK, base + E, sV, base + 2 * E, ld, FP, F, tid, blockDim.x);
-    } else {
-      stage_tile<DH>(sK, base + E, ld, FP, F, tid, blockDim.x);
-      stage_tile<DH>(sV, base + 2 * E, ld, FP, F, tid, blockDim.x);
-    }
-    __syncthreads();
-    if (!PRE && rb < nrb) load_rows(rb, q0, k0);
-    if (rb < nrb) row_block(rb, q0, k0);
-  }
-  for (rb += nwaves; rb < nrb; rb += nwaves) {
-    vec8<HT> q1[NKK], k1[NKK];
-    load_rows(rb, q1, k1);
-    row_block(rb, q1, k1);
-  }
+  attn_fwd_mfma_body<HT, DH, NJB, KB, false>(qkv, o, lse, a, AttnQuerySrc{});
 }
 
 // One wave per 32-row block of queries, but at most FOUR per block: the kernel needs 212 VGPRs (two waves per SIMD = eight wave

@@ -461,6 +461,10 @@ int tim_attn_keep_bits(const TimDesc& d, int first_layer, int n, unsigned long l
 size_t tim_attention_bwd_ws(const TimDesc& d);
 // attn_maps.hip: the head-averaged (per_head: per-head) softmax weights of the rows s0 .. S - 1, [.., S - s0, ld] fp32
 int tim_attention_weights(const TimDesc& d, const void* qkv, int s0, int per_head, float* w, int ld, hipStream_t s);
+// attention_query.hip: d.B groups of d.S query rows (qkv_q: q | own k | own v, compact) against the K | V rows of window widx[g] (or g)
+// of a cache - kv: K of row 0 of window 0, V E elements behind it, row pitch ldkv, wrows rows per window, W windows
+int tim_attention_query_fwd(const TimDesc& d, const void* qkv_q, const void* kv, int ldkv, int wrows, int W, const int* widx, void* o,
+                            hipStream_t s);
 
 // operand storage: bf16 for TIMHIP_PREC_BF16, fp16 for TIMHIP_PREC_F16, fp32 for TIMHIP_PREC_FP32 and TIMHIP_PREC_BF16X3
 static inline bool h16_storage(int precision) { return precision == TIMHIP_PREC_BF16 || precision == TIMHIP_PREC_F16; }

@@ -175,6 +175,62 @@ class TIM(_TIMBase):
             outputs = self._run(inputs, feature_times, target, False, label_queries, maps=req)
         return outputs, req.result
 
+    # ---- encode a window once, query it many times (tim_amd/query.py) ---------------------------------
+    def encode_windows(self, inputs, feature_times, want_feats=False):
+        """The feature rows of W windows through the stack, once -> `query.WindowCache`.  feature_times: [W, F, 2], what
+        `forward_inference` takes; the time MLP runs here.  Needs `eval()`, runs under no-grad."""
+        from . import query
+        query._need_eval(self, "encode_windows")
+        if feature_times.dim() != 3 or feature_times.shape[1] < self.cfg.F or feature_times.shape[2] != 2:
+            raise ValueError("feature_times must be [W, >= %d, 2], got %s" % (self.cfg.F, tuple(feature_times.shape)))
+        _require_gpu(feature_times, "encode_windows")
+        with torch.no_grad():
+            te = self._time_mlp(feature_times[:, :self.cfg.F].contiguous())
+        return query.encode(self, inputs[0], inputs[1], te, want_feats)
+
+    def query_windows(self, cache, v_queries=None, a_queries=None, window_index=None, validate=True):
+        """Segments [G, Nq, 2] in window coordinates against the cached windows -> (cls_scores, reg_scores) as `forward_inference`
+        returns them (they feed `DetectionCollector` unchanged).  None: the model's own inference pyramid, for each modality in
+        `data_modality`.  window_index, validate, errors: as the recognition model's `query_windows`."""
+        from . import query
+        query._need_eval(self, "query_windows")
+        query.check_cache(self, cache)
+        given = [t for t in (v_queries, a_queries) if t is not None]
+        for t in given:
+            if t.dim() != 3 or t.shape[2] != 2:
+                raise ValueError("queries must be [G, Nq, 2] segments, got %s" % (tuple(t.shape),))
+        if len(given) == 2 and v_queries.shape[0] != a_queries.shape[0]:
+            raise ValueError("v_queries and a_queries name %d and %d groups" % (v_queries.shape[0], a_queries.shape[0]))
+        for t, mod in ((v_queries, "visual"), (a_queries, "audio")):
+            if t is not None and mod not in self.data_modality:
+                raise ValueError("%s queries for a model whose data_modality is %s" % (mod, self.data_modality))
+        if given:
+            G = given[0].shape[0]
+        elif window_index is not None:
+            G = len(window_index)
+        else:
+            G = cache.W
+        dev = cache.kv.device
+        widx = query.resolve_window_index(window_index, G, cache.W, dev, validate)
+        pyramids = self.__dict__.setdefault("_pyramid_dev", {})
+
+        def own():
+            t = pyramids.get(("inference_queries", dev))
+            if t is None:
+                t = pyramids[("inference_queries", dev)] = self.inference_queries.to(device=dev)
+            return t.expand(G, -1, -1)
+        parts = []
+        for t, mod in ((v_queries, "visual"), (a_queries, "audio")):
+            if mod in self.data_modality:
+                parts.append((own() if t is None else t).to(device=dev, dtype=torch.float32))
+        nv = parts[0].shape[1] if "visual" in self.data_modality else 0
+        na = parts[-1].shape[1] if "audio" in self.data_modality else 0
+        _require_gpu(cache.kv, "query_windows")
+        with torch.no_grad():
+            te_q = self._time_mlp(torch.concat(parts, dim=1).contiguous())
+        o = query.query(self, cache, te_q, nv, na, widx, validate=False)   # (the index was judged above)
+        return (o.get("verb"), o.get("noun"), o.get("action"), o.get("audio")), (o.get("reg_visual"), o.get("reg_audio"))
+
     def forward_encoder(self, inputs, feature_times, target, label_queries=False):
         if self.training:
             return self.forward_train(inputs, feature_times, target)

@@ -532,6 +532,33 @@ class TIM(nn.Module):
             outputs = self.forward_encoder(inputs, time_encodings, num_v_queries, num_a_queries, _maps=req)
         return outputs, req.result
 
+    # ---- encode a window once, query it many times (tim_amd/query.py) ---------------------------------
+    def encode_windows(self, inputs, time_encodings, want_feats=False):
+        """The feature rows of W windows through the stack, once -> an opaque `query.WindowCache` (per layer the keys and values
+        of the F feature tokens; `cache.feats` [W, F, E] - the `feats` of a full forward - when want_feats).  inputs: as for
+        `forward_encoder` (the AVGA pre-step of a `pool_features` model is applied as there); time_encodings: [W, >= F, d], the
+        first F rows are used - the usual [B, T, d] tensor passes unchanged.  Needs `eval()` (ValueError under `.train()`), runs
+        under no-grad; nothing differentiates through a cache."""
+        from . import query
+        query._need_eval(self, "encode_windows")
+        if self.pool is not None:
+            self.pool.bind(self)
+            with torch.no_grad():
+                inputs = [self.pool(inputs[1], inputs[0]), inputs[1]]
+        return query.encode(self, inputs[0], inputs[1], time_encodings, want_feats)
+
+    def query_windows(self, cache, query_time_encodings, num_v_queries, num_a_queries, window_index=None, validate=True):
+        """The queries of G groups against the cached windows -> (verb, noun, action, audio) as `forward` returns them ([G n, C],
+        None for absent heads).  query_time_encodings: [G, nv + na, d], visual queries first and then audio - the tail
+        te[:, F:] of the usual tensor.  window_index: None (group g reads window g, G == W), or one window number per group - a
+        list, numpy array or CPU tensor (range-checked on the host, ValueError), or a CUDA int32 tensor (range-checked with one
+        reduction and a device synchronisation, unless validate=False: captured graphs, where the caller owns the range and an
+        index outside it yields NaN rows for that group, never a read).  RuntimeError for a cache whose parameters changed
+        since it was encoded; ValueError under `.train()`."""
+        from . import query
+        o = query.query(self, cache, query_time_encodings, int(num_v_queries or 0), int(num_a_queries or 0), window_index, validate)
+        return (o.get("verb"), o.get("noun"), o.get("action"), o.get("audio"))
+
     def _time_mlp(self, times):
         m = self.time_mlp
         return TimeMlpFn.apply(self.rt, times, m[0].weight, m[0].bias, m[2].weight, m[2].bias, m[4].weight,

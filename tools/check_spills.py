@@ -36,6 +36,7 @@ BUDGET = {
     "wgrad_pp.hip": [(r"wgrad_ld_kernel", 0), (r"wgrad_pp_kernel", 0), (r"wgrad_p8_kernel", 0)],
     "wgrad.hip": [(r"wgrad_group_kernel", 0), (r"wgrad_tn_kernel", 0)],
     "attention_mfma.hip": [(r"attn_fwd_mfma", 0)],
+    "attention_query.hip": [(r"attn_query_mfma", 0)],   # attn_fwd_mfma's body on query rows (attention.h): the same registers
     # the attention-weights kernels: the scores of a head and the running head mean both live in registers (202 VGPRs at head width
     # 128, F = 100; 229 at five key blocks) - scratch traffic would sit inside the loop over the heads
     "attn_maps.hip": [(r"attn_w_mfma", 0), (r"attn_w_generic", 0)],
