@@ -4,6 +4,7 @@
 #include <atomic>
 #include "common.h"
 #include "gemm_plan.h"
+#include "wgrad_plan.h"
 
 namespace {
 
@@ -766,7 +767,7 @@ int timhip_layer_wgrad_pair_wins(const TimDesc* dp) {
   TimWgradItem it[8];
   layer_products(d, nullptr, nullptr, nullptr, nullptr, it);
   layer_products(d, nullptr, nullptr, nullptr, nullptr, it + 4);
-  return tim_wgrad_p8_wins(it, 8, d.B * d.S) ? 1 : 0;
+  return wgrad_group_plan(tim_knobs(), it, 8, d.B * d.S).family == WGRAD_P8 ? 1 : 0;   // what the pair launch takes
 }
 
 // single-stream form: the data chain followed by the weight gradients, `dy` behind the data chain's workspace

@@ -420,16 +420,15 @@ size_t tim_wgrad_tn_ws(int Nout, int Kout, int M);
 // multiplied by S and passes 1/S here, see timhip_grad_scale)
 int tim_wgrad_tn_h16(int precision, const void* dY, int ldy, int Nout, const void* X, int ldx, int Kout, int M, float* dW,
                      float* db, void* ws, size_t ws_bytes, hipStream_t s, int accumulate = 1, const float* out_scale = nullptr);
+// which kernel a group gets, its geometry and its workspace: wgrad_plan.h (tim_wgrad_group_ws = the plan's ws_bytes)
 size_t tim_wgrad_group_ws(const TimWgradItem* it, int n, int M);
-int tim_wgrad_group_splits(const TimWgradItem* it, int n, int M);
 int tim_wgrad_group_h16(int precision, const TimWgradItem* it, int n, int M, int accumulate, void* ws, size_t ws_bytes,
                         const float* out_scale, hipStream_t s);
-// wgrad_pp.hip: the grouped weight gradients as one-block-per-CU ping-pong blocks (no split of the contraction, no workspace)
-bool tim_wgrad_pp_wins(const TimWgradItem* it, int n, int M);
-int tim_wgrad_group_pp(int precision, const TimWgradItem* it, int n, int M, int accumulate, const float* out_scale, hipStream_t s);
-// its eight-phase form (256 x 256 tiles; wins for groups of whole rounds of 256 such tiles: two encoder layers at C2a)
-bool tim_wgrad_p8_wins(const TimWgradItem* it, int n, int M);
-int tim_wgrad_group_p8(int precision, const TimWgradItem* it, int n, int M, int accumulate, const float* out_scale, hipStream_t s);
+// wgrad_pp.hip: launches a plan of one of the one-block-per-CU families (ping-pong, loader-wave, eight-phase: no split of the
+// contraction, no workspace); the caller has checked the group's contract
+struct WgradPlan;
+int tim_wgrad_group_pp(const WgradPlan& p, int precision, const TimWgradItem* it, int n, int M, int accumulate, const float* out_scale,
+                       hipStream_t s);
 int tim_colsum(int precision, const void* src, int rows, int cols, int ld, float* out, hipStream_t s);
 // mask_out != NULL: additionally writes the dropout keep-bits of a [rows, mask_cols] site (1 bit per element, row stride
 // mask_cols / 8 bytes, element index r * mask_cols + c as in the GEMM epilogues) - see drop_bits32

@@ -1,4 +1,5 @@
-// A/B knobs of the launchers (plain C++: no HIP types, so host-only code such as gemm_plan.h can take them).
+// A/B knobs of the launchers (plain C++: no HIP types, so host-only code such as gemm_plan.h and wgrad_plan.h can take them;
+// what a TIMHIP_GEMM_* / TIMHIP_WGRAD_* routing knob does to a launch is stated there).
 #pragma once
 
 // Read from the environment ONCE (first launch) instead of per launch - the step issues 144 launches and the host is within

@@ -15,6 +15,7 @@
 #include <cstdlib>
 #include "common.h"
 #include "mfma_tiles.h"
+#include "wgrad_plan.h"   // WT x WT output tile, WM contraction rows per step; which launch a call gets
 
 namespace {
 
@@ -23,9 +24,6 @@ __device__ __forceinline__ int xcd_remap_w(int b, int nb) {  // bijective for an
   const int xcd = b & 7, idx = b >> 3;
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
 }
-
-constexpr int WT = 128;   // output tile: 128 (n) x 128 (k)
-constexpr int WM = 64;    // contraction rows per step
 
 // One work item: the 128 x 128 tile (n0, k0) of dW over the contraction steps [s0, s1) of 64 rows.  `out` is an [N, K] fp32
 // matrix (a slab of partial sums, or dW itself when the contraction is not split), `db_out` an [N] vector (first k-tile
@@ -244,13 +242,12 @@ __global__ __launch_bounds__(256) void wgrad_tn_kernel(const HT* __restrict__ dY
 // 512 tiles = exactly the 512 block slots, so the contraction is not split at all - every block runs the whole M and writes
 // (or accumulates into) dW / db directly: no slabs (was 330 MB of slab writes + reads per layer), no reduce launches, one
 // tail instead of four.
-constexpr int WG_MAX = 8;
 struct WgGroup {
-  const void* dY[WG_MAX]; const void* X[WG_MAX]; float* dW[WG_MAX]; float* db[WG_MAX];
-  int ldy[WG_MAX], ldx[WG_MAX], N[WG_MAX], K[WG_MAX];
-  int tile0[WG_MAX + 1];          // first work tile of every item (prefix sums), tile0[n] = total
-  long long off[WG_MAX + 1];      // element offset of every item's [N, K] block inside one slab
-  int boff[WG_MAX + 1];           // same for the bias slabs
+  const void* dY[WGRAD_MAX_ITEMS]; const void* X[WGRAD_MAX_ITEMS]; float* dW[WGRAD_MAX_ITEMS]; float* db[WGRAD_MAX_ITEMS];
+  int ldy[WGRAD_MAX_ITEMS], ldx[WGRAD_MAX_ITEMS], N[WGRAD_MAX_ITEMS], K[WGRAD_MAX_ITEMS];
+  int tile0[WGRAD_MAX_ITEMS + 1];          // first work tile of every item (prefix sums), tile0[n] = total
+  long long off[WGRAD_MAX_ITEMS + 1];      // element offset of every item's [N, K] block inside one slab
+  int boff[WGRAD_MAX_ITEMS + 1];           // same for the bias slabs
   int n, M, steps_per_split, splits, accumulate;
   float* slab; float* db_slab;    // [splits][off[n]] and [splits][boff[n]] (splits > 1 only)
   const float* out_scale;         // device scalar or NULL: factor on the final outputs (1 / gradient scale of the fp16 mode)
@@ -270,7 +267,7 @@ __global__ __launch_bounds__(256) void wgrad_group_kernel(const WgGroup g) {
   float* dW = nullptr;
   float* db = nullptr;
 #pragma unroll
-  for (int i = 0; i < WG_MAX; ++i) {   // static indexing of the kernel-argument arrays (uniform select)
+  for (int i = 0; i < WGRAD_MAX_ITEMS; ++i) {   // static indexing of the kernel-argument arrays (uniform select)
     if (i < g.n && t >= g.tile0[i]) {
       a.dY = (const HT*)g.dY[i]; a.X = (const HT*)g.X[i]; a.ldy = g.ldy[i]; a.ldx = g.ldx[i]; a.N = g.N[i]; a.K = g.K[i];
       tl = t - g.tile0[i]; tiles_k = (g.K[i] + WT - 1) / WT;
@@ -306,7 +303,7 @@ __global__ void wgrad_group_reduce_kernel(const WgGroup g) {
       const long long i = q << 2;
       float* dst = nullptr;
 #pragma unroll
-      for (int it = 0; it < WG_MAX; ++it)
+      for (int it = 0; it < WGRAD_MAX_ITEMS; ++it)
         if (it < g.n && i >= g.off[it]) dst = g.dW[it] + (i - g.off[it]);
       float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
       for (int z = 0; z < g.splits; ++z) {
@@ -324,7 +321,7 @@ __global__ void wgrad_group_reduce_kernel(const WgGroup g) {
       const int j = (int)(q - nq);
       float* dst = nullptr;
 #pragma unroll
-      for (int it = 0; it < WG_MAX; ++it)
+      for (int it = 0; it < WGRAD_MAX_ITEMS; ++it)
         if (it < g.n && j >= g.boff[it]) dst = g.db[it] + (j - g.boff[it]);   // items without a bias have an empty range
       if (!dst) continue;
       float acc = 0.f;
@@ -384,111 +381,41 @@ __global__ void slab_reduce2_kernel(const float* __restrict__ slab, long long n,
 
 }  // namespace
 
-// Number of splits of the contraction (token) dimension.  Work items = tiles x splits run two per CU (512 slots).
-// Cost model in units of one 64-row K-step of one block, fitted to tools/wgrad_splits.py on the C2a shapes:
-//   steps per item x (full rounds + a partial round priced at 0.5 + 0.5 x its fill) + slab traffic per split
-// e.g. in-proj (192 tiles): 3 splits = 576 items (1.125 rounds) 108 us, 5 splits = 960 items 100 us.
-static int splits_for_tiles(int tiles, int M) {
-  const int nsteps = (M + WM - 1) / WM;
+// The split count, the route and the workspace of every call below: wgrad_plan.h.  TIMHIP_WGRAD_SPLITS (TUNING=1 builds,
+// tools/wgrad_splits.py) forces a split count IN FRONT of the plan - for the launchers and the sizing calls alike, so that a
+// forced count and its workspace agree; a product build's plan never sees one.
 #ifdef TIMHIP_TUNING
-  if (const char* v = getenv("TIMHIP_WGRAD_SPLITS")) { int sk = atoi(v); if (sk >= 1 && sk <= nsteps) return sk; }
+static int force_splits() { const char* v = getenv("TIMHIP_WGRAD_SPLITS"); return v ? atoi(v) : 0; }
+#else
+static int force_splits() { return 0; }
 #endif
-  int maxsk = nsteps / 4;
-  if (maxsk > 16) maxsk = 16;
-  if (maxsk < 1) maxsk = 1;
-  int best = 1;
-  float best_cost = 0.f;
-  for (int sk = 1; sk <= maxsk; ++sk) {
-    const float per = (float)((nsteps + sk - 1) / sk);
-    const float r = (float)tiles * sk / 512.f;
-    const float full = floorf(r), frac = r - full;
-    const float cost = per * (full + (frac > 0.f ? 0.5f + 0.5f * frac : 0.f)) + 1.5f * (float)tiles / 128.f * sk;
-    if (sk == 1 || cost < best_cost) { best = sk; best_cost = cost; }
-  }
-  return best;
-}
-
-int tim_wgrad_splits(int Nout, int Kout, int M) {
-  return splits_for_tiles(((Nout + WT - 1) / WT) * ((Kout + WT - 1) / WT), M);
-}
 
 // ---- grouped launch (one encoder layer's four weight gradients) ------------------------------------------------------
-static int group_tiles(const TimWgradItem* it, int n) {
-  int tiles = 0;
-  for (int i = 0; i < n; ++i) tiles += ((it[i].Nout + WT - 1) / WT) * ((it[i].Kout + WT - 1) / WT);
-  return tiles;
-}
-
-int tim_wgrad_group_splits(const TimWgradItem* it, int n, int M) { return splits_for_tiles(group_tiles(it, n), M); }
-
-size_t tim_wgrad_group_ws(const TimWgradItem* it, int n, int M) {
-  const int sk = tim_wgrad_group_splits(it, n, M);
-  if (sk == 1) return 0;
-  size_t elems = 0, bias = 0;
-  for (int i = 0; i < n; ++i) { elems += (size_t)it[i].Nout * it[i].Kout; bias += (size_t)it[i].Nout; }
-  return align_up(sk * elems * 4, 256) + align_up(sk * bias * 4, 256);
-}
+size_t tim_wgrad_group_ws(const TimWgradItem* it, int n, int M) { return wgrad_group_plan(tim_knobs(), it, n, M, force_splits()).ws_bytes; }
 
 int tim_wgrad_group_h16(int precision, const TimWgradItem* it, int n, int M, int accumulate, void* ws, size_t ws_bytes,
                         const float* out_scale, hipStream_t s) {
   if (!h16_storage(precision)) return TIMHIP_EUNSUPPORTED;
-  if (!it || n < 1 || n > WG_MAX || M <= 0) return TIMHIP_EINVAL;
-  // The argument contract of the group (include/timhip.h) is the same whichever kernel runs it and is checked here, before any
-  // launch: a group is refused as a whole, no item of it is written.
+  if (const int rc = wgrad_group_contract(it, n, M)) return rc;
+  const WgradPlan p = wgrad_group_plan(tim_knobs(), it, n, M, force_splits());
+  if (p.splits > 1 && (ws_bytes < p.ws_bytes || !ws || ((uintptr_t)ws & 15))) return TIMHIP_EWORKSPACE;
   double flops = 0.0;
-  for (int i = 0; i < n; ++i) {
-    const TimWgradItem& t = it[i];
-    if (!t.dY || !t.X || !t.dW || t.Nout <= 0 || t.Kout <= 0) return TIMHIP_EINVAL;
-    if ((t.ldy % 8) || (t.ldx % 8) || (((uintptr_t)t.dY | (uintptr_t)t.X | (uintptr_t)t.dW) & 15)) return TIMHIP_EALIGN;
-    if (((long long)t.Nout * t.Kout) & 3) return TIMHIP_EUNSUPPORTED;
-    flops += 2.0 * M * t.Nout * t.Kout;
-  }
-  // two encoder layers of a production batch: one round of eight-phase 256 x 256 tiles (wgrad_pp.hip; TIMHIP_WGRAD_P8=0: A/B switch)
-  // The tiled grids have a limit of their own (32-bit byte offsets: M * ld * 2 < 2^32) that the kernel below does not: a group they
-  // decline as TIMHIP_EUNSUPPORTED - before launching anything - falls through to it instead of failing the call.
-  if (tim_wgrad_p8_wins(it, n, M)) {
-    TimGemmScope timing(flops, s);
-    const int rc = tim_wgrad_group_p8(precision, it, n, M, accumulate, out_scale, s);
-    if (rc != TIMHIP_EUNSUPPORTED) return rc;
-  }
-  // an encoder layer of a production batch: the one-block-per-CU ping-pong grid (wgrad_pp.hip; TIMHIP_WGRAD_PP=0: A/B switch)
-  if (tim_knobs().wgrad_pp != 0 && tim_wgrad_pp_wins(it, n, M)) {
-    TimGemmScope timing(flops, s);
-    const int rc = tim_wgrad_group_pp(precision, it, n, M, accumulate, out_scale, s);
-    if (rc != TIMHIP_EUNSUPPORTED) return rc;
-  }
-  WgGroup g;
-  g.n = n; g.M = M; g.accumulate = accumulate ? 1 : 0; g.out_scale = out_scale;
-  g.tile0[0] = 0; g.off[0] = 0; g.boff[0] = 0;
-  for (int i = 0; i < WG_MAX; ++i) {
-    if (i >= n) {
-      g.dY[i] = g.X[i] = nullptr; g.dW[i] = g.db[i] = nullptr; g.ldy[i] = g.ldx[i] = g.N[i] = g.K[i] = 0;
-      g.tile0[i + 1] = g.tile0[i]; g.off[i + 1] = g.off[i]; g.boff[i + 1] = g.boff[i];
-      continue;
-    }
-    const TimWgradItem& t = it[i];
-    g.dY[i] = t.dY; g.X[i] = t.X; g.dW[i] = t.dW; g.db[i] = t.db;
-    g.ldy[i] = t.ldy; g.ldx[i] = t.ldx; g.N[i] = t.Nout; g.K[i] = t.Kout;
-    g.tile0[i + 1] = g.tile0[i] + ((t.Nout + WT - 1) / WT) * ((t.Kout + WT - 1) / WT);
-    g.off[i + 1] = g.off[i] + (long long)t.Nout * t.Kout;
-    g.boff[i + 1] = g.boff[i] + (t.db ? t.Nout : 0);
-  }
-  const int sk = splits_for_tiles(g.tile0[n], M);
-  const int nsteps = (M + WM - 1) / WM;
-  const int per = (nsteps + sk - 1) / sk;
-  const int sk_eff = (nsteps + per - 1) / per;  // no empty splits
-  g.steps_per_split = per; g.splits = sk_eff;
-  g.slab = nullptr; g.db_slab = nullptr;
-  if (sk_eff > 1) {
-    if (ws_bytes < tim_wgrad_group_ws(it, n, M) || !ws || ((uintptr_t)ws & 15)) return TIMHIP_EWORKSPACE;
-    g.slab = (float*)ws;
-    g.db_slab = (float*)((char*)ws + align_up((size_t)sk * g.off[n] * 4, 256));
-  }
+  for (int i = 0; i < n; ++i) flops += 2.0 * M * it[i].Nout * it[i].Kout;
   TimGemmScope timing(flops, s);   // kernel (+ reduce)
-  const size_t shmem = 2 * 2 * WM * WT * 2;
-  DISPATCH_H16(precision, hipLaunchKernelGGL(wgrad_group_kernel<HT>, dim3((unsigned)(g.tile0[n] * sk_eff)), dim3(256), shmem, s, g));
+  if (p.family != WGRAD_SPLIT) return tim_wgrad_group_pp(p, precision, it, n, M, accumulate, out_scale, s);   // (the tiled families)
+  WgGroup g;
+  wgrad_fill_group(g, p, it, n, M, accumulate, out_scale);
+  g.off[0] = 0; g.boff[0] = 0;
+  for (int i = 0; i < WGRAD_MAX_ITEMS; ++i) {
+    g.off[i + 1] = g.off[i] + (long long)g.N[i] * g.K[i];
+    g.boff[i + 1] = g.boff[i] + (g.db[i] ? g.N[i] : 0);
+  }
+  g.steps_per_split = p.steps_per_split; g.splits = p.splits;
+  g.slab = p.splits > 1 ? (float*)ws : nullptr;
+  g.db_slab = p.splits > 1 ? (float*)((char*)ws + p.db_off) : nullptr;
+  DISPATCH_H16(precision, hipLaunchKernelGGL(wgrad_group_kernel<HT>, dim3(p.grid_x), dim3(p.block), p.lds_bytes, s, g));
   if (hipGetLastError() != hipSuccess) return TIMHIP_ELAUNCH;
-  if (sk_eff > 1) {
+  if (p.splits > 1) {
     long long blocks = ((g.off[n] >> 2) + g.boff[n] + 255) / 256;
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(wgrad_group_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, g);
@@ -497,42 +424,33 @@ int tim_wgrad_group_h16(int precision, const TimWgradItem* it, int n, int M, int
   return TIMHIP_OK;
 }
 
-// workspace: [slab sk*N*K fp32][db slab sk*N fp32]
-size_t tim_wgrad_tn_ws(int Nout, int Kout, int M) {
-  const int sk = tim_wgrad_splits(Nout, Kout, M);
-  return align_up((size_t)sk * Nout * Kout * 4, 256) + align_up((size_t)sk * Nout * 4, 256);
-}
+// ---- one product: workspace [slab sk*N*K fp32][db slab sk*N fp32] -----------------------------------------------------------
+size_t tim_wgrad_tn_ws(int Nout, int Kout, int M) { return wgrad_tn_plan(Nout, Kout, M, force_splits()).ws_bytes; }
 
 int tim_wgrad_tn_h16(int precision, const void* dY, int ldy, int Nout, const void* X, int ldx, int Kout, int M, float* dW,
                      float* db, void* ws, size_t ws_bytes, hipStream_t s, int accumulate, const float* out_scale) {
   if (!h16_storage(precision)) return TIMHIP_EUNSUPPORTED;
-  if (ws_bytes < tim_wgrad_tn_ws(Nout, Kout, M)) return TIMHIP_EWORKSPACE;
+  const WgradPlan p = wgrad_tn_plan(Nout, Kout, M, force_splits());
+  if (ws_bytes < p.ws_bytes) return TIMHIP_EWORKSPACE;
   if ((ldy % 8) || (ldx % 8) || (((uintptr_t)dY | (uintptr_t)X | (uintptr_t)ws) & 15)) return TIMHIP_EALIGN;
-  const int sk = tim_wgrad_splits(Nout, Kout, M);
   TimGemmScope timing(2.0 * M * Nout * Kout, s);   // kernel + slab reduce
-  char* w = (char*)ws;
-  float* slab = (float*)w;
-  float* dbs = (float*)(w + align_up((size_t)sk * Nout * Kout * 4, 256));
-  const int nsteps = (M + WM - 1) / WM;
-  const int per = (nsteps + sk - 1) / sk;
-  const int sk_eff = (nsteps + per - 1) / per;  // no empty splits
-  dim3 grid(((Nout + WT - 1) / WT) * ((Kout + WT - 1) / WT) * sk_eff, 1, 1);
-  const size_t shmem = 2 * 2 * WM * WT * 2;
-  DISPATCH_H16(precision, hipLaunchKernelGGL(wgrad_tn_kernel<HT>, grid, dim3(256), shmem, s, (const HT*)dY, ldy, (const HT*)X, ldx,
-                                             M, Nout, Kout, per, slab, (long long)Nout * Kout, db ? dbs : nullptr));
+  float* slab = (float*)ws;
+  float* dbs = (float*)((char*)ws + p.db_off);
+  DISPATCH_H16(precision, hipLaunchKernelGGL(wgrad_tn_kernel<HT>, dim3(p.grid_x), dim3(p.block), p.lds_bytes, s, (const HT*)dY, ldy, (const HT*)X,
+                                             ldx, M, Nout, Kout, p.steps_per_split, slab, (long long)Nout * Kout, db ? dbs : nullptr));
   if (hipGetLastError() != hipSuccess) return TIMHIP_ELAUNCH;
   const long long n = (long long)Nout * Kout;
   if ((n & 3) == 0) {
     long long blocks = (n / 4 + Nout + 255) / 256;
     if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, slab, n, sk_eff, dW, dbs, Nout, db, accumulate, out_scale);
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, slab, n, p.splits, dW, dbs, Nout, db, accumulate, out_scale);
     return hipGetLastError() == hipSuccess ? TIMHIP_OK : TIMHIP_ELAUNCH;
   }
-  hipLaunchKernelGGL(slab_reduce2_kernel, dim3(256), dim3(256), 0, s, slab, n, n, sk_eff, dW, accumulate, out_scale);
+  hipLaunchKernelGGL(slab_reduce2_kernel, dim3(256), dim3(256), 0, s, slab, n, n, p.splits, dW, accumulate, out_scale);
   if (hipGetLastError() != hipSuccess) return TIMHIP_ELAUNCH;
   if (db) {
     hipLaunchKernelGGL(slab_reduce2_kernel, dim3((Nout + 255) / 256), dim3(256), 0, s, dbs, (long long)Nout,
-                       (long long)Nout, sk_eff, db, accumulate, out_scale);
+                       (long long)Nout, p.splits, db, accumulate, out_scale);
     if (hipGetLastError() != hipSuccess) return TIMHIP_ELAUNCH;
   }
   return TIMHIP_OK;

@@ -31,18 +31,14 @@
 
 #include "common.h"
 #include "mfma_tiles.h"
+#include "wgrad_plan.h"   // the tile constants (WP_*, W8_*); which of this file's kernels a group gets
 
 namespace {
 
-constexpr int WP_TN = 128, WP_TK = 256, WP_M = 64, WP_NST = 3;
-constexpr int WP_SUB = WP_M * 256;            // bytes of one [64][128] 16-bit sub-tile (256-byte rows)
-constexpr int WP_STAGE = 3 * WP_SUB;          // dY | X[:, 0:128] | X[:, 128:256]
-constexpr int WP_MAX = 8;
-
 struct WpGroup {
-  const void* dY[WP_MAX]; const void* X[WP_MAX]; float* dW[WP_MAX]; float* db[WP_MAX];
-  int ldy[WP_MAX], ldx[WP_MAX], N[WP_MAX], K[WP_MAX];
-  int tile0[WP_MAX + 1];
+  const void* dY[WGRAD_MAX_ITEMS]; const void* X[WGRAD_MAX_ITEMS]; float* dW[WGRAD_MAX_ITEMS]; float* db[WGRAD_MAX_ITEMS];
+  int ldy[WGRAD_MAX_ITEMS], ldx[WGRAD_MAX_ITEMS], N[WGRAD_MAX_ITEMS], K[WGRAD_MAX_ITEMS];
+  int tile0[WGRAD_MAX_ITEMS + 1];
   int n, M, accumulate;
   const float* out_scale;
   int pf_dist;   // wgrad_ld_kernel: L2 prefetch distance in 64-row stages (0: off)
@@ -574,7 +570,7 @@ __global__ __launch_bounds__(768) void wgrad_ld_kernel(const WpGroup g) {
   float* dW = nullptr;
   float* db = nullptr;
 #pragma unroll
-  for (int i = 0; i < WP_MAX; ++i) {
+  for (int i = 0; i < WGRAD_MAX_ITEMS; ++i) {
     if (i < g.n && t >= g.tile0[i]) {
       a.dY = (const char*)g.dY[i]; a.X = (const char*)g.X[i]; a.ldy = g.ldy[i]; a.ldx = g.ldx[i]; a.N = g.N[i]; a.K = g.K[i];
       tl = t - g.tile0[i]; tiles_k = (g.K[i] + WP_TK - 1) / WP_TK;
@@ -666,7 +662,7 @@ __global__ __launch_bounds__(512) void wgrad_pp_kernel(const WpGroup g) {
   float* dW = nullptr;
   float* db = nullptr;
 #pragma unroll
-  for (int i = 0; i < WP_MAX; ++i) {   // static indexing of the kernel-argument arrays (uniform select)
+  for (int i = 0; i < WGRAD_MAX_ITEMS; ++i) {   // static indexing of the kernel-argument arrays (uniform select)
     if (i < g.n && t >= g.tile0[i]) {
       a.dY = (const char*)g.dY[i]; a.X = (const char*)g.X[i]; a.ldy = g.ldy[i]; a.ldx = g.ldx[i]; a.N = g.N[i]; a.K = g.K[i];
       tl = t - g.tile0[i]; tiles_k = (g.K[i] + WP_TK - 1) / WP_TK;
@@ -762,7 +758,6 @@ __global__ __launch_bounds__(512) void wgrad_pp_kernel(const WpGroup g) {
 //   * two stage buffers (128 KiB); restaging one phase after a sub-tile's last fragment read, as in p8_mainloop: phase 1: X_0 of
 //     step t + 1 -> other buffer; phases 2 / 3 / 4: Y_0 / X_1 / Y_1 of step t + 2 -> this buffer; one counted wait per step.
 // Hazards: gemm_pp.hip (identical segment structure).  Bias gradients: one ones-MFMA per wave and step, see the kernel.
-constexpr int W8_T = 256, W8_SUB = WP_M * 256, W8_STAGE = 4 * W8_SUB;
 struct W8Tab { uint32_t offY[2][2], offX[2][2]; };
 
 // ABL (tuning builds, tools/wg_pair_ab.py): timing-only ablations - 1: no bias MFMAs, 2: the X pieces gathered in 128-byte runs
@@ -1037,7 +1032,7 @@ __global__ __launch_bounds__(512) void wgrad_p8_kernel(const WpGroup g) {
   float* dW = nullptr;
   float* db = nullptr;
 #pragma unroll
-  for (int i = 0; i < WP_MAX; ++i) {   // static indexing of the kernel-argument arrays (uniform select)
+  for (int i = 0; i < WGRAD_MAX_ITEMS; ++i) {   // static indexing of the kernel-argument arrays (uniform select)
     if (i < g.n && t >= g.tile0[i]) {
       pY = (const char*)g.dY[i]; pX = (const char*)g.X[i]; ldy = g.ldy[i]; ldx = g.ldx[i]; N = g.N[i]; K = g.K[i];
       tl = t - g.tile0[i]; tiles_k = g.K[i] / W8_T;
@@ -1130,128 +1125,64 @@ __global__ __launch_bounds__(512) void wgrad_p8_kernel(const WpGroup g) {
   (void)N;
 }
 
-}  // namespace
-
-// Does the ping-pong grid suit this group?  Its blocks run the whole contraction (no split), one per CU: it needs about a
-// multiple of 256 tiles of 128 x 256 and a long M (the encoder layers of a production batch).
-bool tim_wgrad_pp_wins(const TimWgradItem* it, int n, int M) {
-  if (!it || n < 1 || n > WP_MAX || M < 2048) return false;
-  long long tiles = 0;
-  for (int i = 0; i < n; ++i) {
-    if (it[i].Nout < 64 || it[i].Kout < 128) return false;
-    tiles += (long long)((it[i].Nout + WP_TN - 1) / WP_TN) * ((it[i].Kout + WP_TK - 1) / WP_TK);
-  }
-  const long long rounds = (tiles + 255) / 256;
-  return tiles >= 192 && tiles * 100 >= rounds * 256 * 75;
+// One launch of a kernel instance of this file as its plan says (wgrad_plan.h: WGRAD_PP8W / WGRAD_LD / WGRAD_P8); nothing is
+// decided here.  The dynamic-LDS attribute is set once per device and instance.
+template <void (*KERNEL)(const WpGroup)>
+void launch_tiled(const WgradPlan& p, const WpGroup& g, hipStream_t s) {
+  static PerDeviceOnce attr_set;
+  if (attr_set.first()) (void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
+  hipLaunchKernelGGL(KERNEL, dim3(p.grid_x), dim3(p.block), p.lds_bytes, s, g);
 }
 
-int tim_wgrad_group_pp(int precision, const TimWgradItem* it, int n, int M, int accumulate, const float* out_scale, hipStream_t s) {
-  if (!h16_storage(precision)) return TIMHIP_EUNSUPPORTED;
-  WpGroup g;
-  g.n = n; g.M = M; g.accumulate = accumulate ? 1 : 0; g.out_scale = out_scale;
-  g.pf_dist = tim_knobs().wgrad_pf;
-  g.tile0[0] = 0;
-  for (int i = 0; i < WP_MAX; ++i) {
-    if (i >= n) {
-      g.dY[i] = g.X[i] = nullptr; g.dW[i] = g.db[i] = nullptr; g.ldy[i] = g.ldx[i] = g.N[i] = g.K[i] = 0; g.tile0[i + 1] = g.tile0[i];
-      continue;
-    }
-    const TimWgradItem& t = it[i];
-    if (!t.dY || !t.X || !t.dW || t.Nout <= 0 || t.Kout <= 0) return TIMHIP_EINVAL;
-    if ((t.ldy % 8) || (t.ldx % 8) || (((uintptr_t)t.dY | (uintptr_t)t.X | (uintptr_t)t.dW) & 15)) return TIMHIP_EALIGN;
-    if ((size_t)M * t.ldy * 2 >= (1ull << 32) || (size_t)M * t.ldx * 2 >= (1ull << 32)) return TIMHIP_EUNSUPPORTED;
-    g.dY[i] = t.dY; g.X[i] = t.X; g.dW[i] = t.dW; g.db[i] = t.db; g.ldy[i] = t.ldy; g.ldx[i] = t.ldx; g.N[i] = t.Nout; g.K[i] = t.Kout;
-    g.tile0[i + 1] = g.tile0[i] + ((t.Nout + WP_TN - 1) / WP_TN) * ((t.Kout + WP_TK - 1) / WP_TK);
-  }
-  const size_t shmem = (size_t)WP_NST * WP_STAGE;
-  static PerDeviceOnce attr_set[2];
-  const int hi = precision == TIMHIP_PREC_F16 ? 1 : 0;
-  if (attr_set[hi].first()) {
-    DISPATCH_H16(precision, (void)hipFuncSetAttribute((const void*)wgrad_pp_kernel<HT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-    DISPATCH_H16(precision, (void)hipFuncSetAttribute((const void*)wgrad_ld_kernel<HT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-  }
-  // the 12-wave loader form is the default; TIMHIP_WGRAD_LD=0 selects the 8-wave merged-phase kernel (A/B switch)
-  const bool ld_on = tim_knobs().wgrad_ld != 0;
 #ifdef TIMHIP_TUNING
-  if (const char* v = getenv("TIMHIP_WGPP_ABL")) {
-    const int abl = atoi(v);
+// Experiment arms of a TUNING=1 build, in FRONT of the plan (a product build's plan can never name them): timing-only ablations
+// and schedule arms of the family the plan chose, fp16 instances.  true: an arm took the launch.
+//   TIMHIP_WGPP_ABL + TIMHIP_WGPP_MODE (tools/wgpp_abl.py): ABL / MODE of wgrad_pp_kernel, MODE 4 (default) = wgrad_ld_kernel
+//   TIMHIP_W8_ABL, TIMHIP_W8_SCH (tools/w8_abl.py): ABL / SCH of the four-phase, whole-stage wgrad_p8_kernel
+bool launch_wgrad_tuning(const WgradPlan& p, const WpGroup& g, hipStream_t s) {
+  const dim3 grid(p.grid_x);
+  const size_t shmem = p.lds_bytes;
+#define ARM(BLOCK, ...) { (void)hipFuncSetAttribute((const void*)__VA_ARGS__, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem); \
+    hipLaunchKernelGGL((__VA_ARGS__), grid, dim3(BLOCK), shmem, s, g); return true; }
+  if (p.family == WGRAD_P8) {
+    if (const char* v = getenv("TIMHIP_W8_ABL")) {
+#define W8A(X) case X: ARM(512, wgrad_p8_kernel<f16_t, X>)
+      switch (atoi(v)) { W8A(1) W8A(2) W8A(4) W8A(8) W8A(16) W8A(24) W8A(7) default: break; }
+#undef W8A
+    }
+    if (const char* v = getenv("TIMHIP_W8_SCH")) {
+#define W8S(X) case X: ARM(512, wgrad_p8_kernel<f16_t, 0, X>)
+      switch (atoi(v)) { W8S(1) W8S(2) W8S(4) W8S(5) W8S(8) W8S(3) default: break; }
+#undef W8S
+    }
+  } else if (const char* v = getenv("TIMHIP_WGPP_ABL")) {
     const int mode = getenv("TIMHIP_WGPP_MODE") ? atoi(getenv("TIMHIP_WGPP_MODE")) : 4;
-#define WABL(X, MD) case X + 8 * MD: (void)hipFuncSetAttribute((const void*)wgrad_pp_kernel<f16_t, X, MD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem); \
-    hipLaunchKernelGGL((wgrad_pp_kernel<f16_t, X, MD>), dim3((unsigned)g.tile0[n]), dim3(512), shmem, s, g); return TIMHIP_OK;
-#define WLD(X) case X + 8 * 4: (void)hipFuncSetAttribute((const void*)wgrad_ld_kernel<f16_t, X>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem); \
-    hipLaunchKernelGGL((wgrad_ld_kernel<f16_t, X>), dim3((unsigned)g.tile0[n]), dim3(768), shmem, s, g); return TIMHIP_OK;
-    switch (abl + 8 * mode) { WLD(0) WLD(1) WLD(2) WLD(4) WLD(6) WABL(0, 0) WABL(1, 0) WABL(2, 0) WABL(4, 0) WABL(6, 0) WABL(7, 0) WABL(0, 1) WABL(2, 1) WABL(4, 1) WABL(6, 1) WABL(0, 2) WABL(1, 2) WABL(2, 2) WABL(4, 2) WABL(6, 2) default: break; }
+#define WABL(X, MD) case X + 8 * MD: ARM(512, wgrad_pp_kernel<f16_t, X, MD>)
+#define WLD(X) case X + 8 * 4: ARM(768, wgrad_ld_kernel<f16_t, X>)
+    switch (atoi(v) + 8 * mode) { WLD(0) WLD(1) WLD(2) WLD(4) WLD(6) WABL(0, 0) WABL(1, 0) WABL(2, 0) WABL(4, 0) WABL(6, 0) WABL(7, 0) WABL(0, 1) WABL(2, 1) WABL(4, 1) WABL(6, 1) WABL(0, 2) WABL(1, 2) WABL(2, 2) WABL(4, 2) WABL(6, 2) default: break; }
 #undef WABL
 #undef WLD
   }
+#undef ARM
+  return false;
+}
+#else
+bool launch_wgrad_tuning(const WgradPlan&, const WpGroup&, hipStream_t) { return false; }
 #endif
-  if (ld_on) {
-    DISPATCH_H16(precision, hipLaunchKernelGGL(wgrad_ld_kernel<HT>, dim3((unsigned)g.tile0[n]), dim3(768), shmem, s, g));
-  } else {
-    DISPATCH_H16(precision, hipLaunchKernelGGL(wgrad_pp_kernel<HT>, dim3((unsigned)g.tile0[n]), dim3(512), shmem, s, g));
-  }
-  return hipGetLastError() == hipSuccess ? TIMHIP_OK : TIMHIP_ELAUNCH;
-}
 
-// Does the eight-phase grid suit this group?  Whole 256 x 256 tiles (any contraction length: a ragged last stage is handled) and rounds of 256
-// tiles filled to 90 %: at C2a that is the eight gradients of TWO encoder layers (TIMHIP_WGRAD_P8=0: off).
-bool tim_wgrad_p8_wins(const TimWgradItem* it, int n, int M) {
-  if (tim_knobs().wgrad_p8 == 0 || !it || n < 1 || n > WP_MAX || M < 2048) return false;
-  long long tiles = 0;
-  for (int i = 0; i < n; ++i) {
-    if (it[i].Nout % W8_T || it[i].Kout % W8_T || it[i].Nout <= 0 || it[i].Kout < 4 * W8_T) return false;   // (>= 4 k tiles: one bias MFMA per wave)
-    tiles += (long long)(it[i].Nout / W8_T) * (it[i].Kout / W8_T);
-  }
-  const long long rounds = (tiles + 255) / 256;
-  return tiles * 100 >= rounds * 256 * 90;
-}
+}  // namespace
 
-int tim_wgrad_group_p8(int precision, const TimWgradItem* it, int n, int M, int accumulate, const float* out_scale, hipStream_t s) {
-  if (!h16_storage(precision)) return TIMHIP_EUNSUPPORTED;
-  if (!it || n < 1 || n > WP_MAX || M < 2 * WP_M) return TIMHIP_EINVAL;
+int tim_wgrad_group_pp(const WgradPlan& p, int precision, const TimWgradItem* it, int n, int M, int accumulate, const float* out_scale,
+                       hipStream_t s) {
   WpGroup g;
-  g.n = n; g.M = M; g.accumulate = accumulate ? 1 : 0; g.out_scale = out_scale; g.pf_dist = 0;
-  g.tile0[0] = 0;
-  for (int i = 0; i < WP_MAX; ++i) {
-    if (i >= n) {
-      g.dY[i] = g.X[i] = nullptr; g.dW[i] = g.db[i] = nullptr; g.ldy[i] = g.ldx[i] = g.N[i] = g.K[i] = 0; g.tile0[i + 1] = g.tile0[i];
-      continue;
-    }
-    const TimWgradItem& t = it[i];
-    if (!t.dY || !t.X || !t.dW || t.Nout <= 0 || t.Kout < 4 * W8_T || t.Nout % W8_T || t.Kout % W8_T) return TIMHIP_EINVAL;
-    if ((t.ldy % 8) || (t.ldx % 8) || (((uintptr_t)t.dY | (uintptr_t)t.X | (uintptr_t)t.dW) & 15)) return TIMHIP_EALIGN;
-    if ((size_t)M * t.ldy * 2 >= (1ull << 32) || (size_t)M * t.ldx * 2 >= (1ull << 32)) return TIMHIP_EUNSUPPORTED;
-    g.dY[i] = t.dY; g.X[i] = t.X; g.dW[i] = t.dW; g.db[i] = t.db; g.ldy[i] = t.ldy; g.ldx[i] = t.ldx; g.N[i] = t.Nout; g.K[i] = t.Kout;
-    g.tile0[i + 1] = g.tile0[i] + (t.Nout / W8_T) * (t.Kout / W8_T);
-  }
-  const size_t shmem = (size_t)2 * W8_STAGE;
-  static PerDeviceOnce attr_set[2];
-  const int hi = precision == TIMHIP_PREC_F16 ? 1 : 0;
-  if (attr_set[hi].first())
-    DISPATCH_H16(precision, (void)hipFuncSetAttribute((const void*)wgrad_p8_kernel<HT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-#ifdef TIMHIP_TUNING
-  if (const char* v = getenv("TIMHIP_W8_ABL")) {
-#define W8A(X) case X: (void)hipFuncSetAttribute((const void*)wgrad_p8_kernel<f16_t, X>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem); \
-    hipLaunchKernelGGL((wgrad_p8_kernel<f16_t, X>), dim3((unsigned)g.tile0[n]), dim3(512), shmem, s, g); return TIMHIP_OK;
-    switch (atoi(v)) { W8A(1) W8A(2) W8A(4) W8A(8) W8A(16) W8A(24) W8A(7) default: break; }
-#undef W8A
-  }
-  if (const char* v = getenv("TIMHIP_W8_SCH")) {
-#define W8S(X) case X: (void)hipFuncSetAttribute((const void*)wgrad_p8_kernel<f16_t, 0, X>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem); \
-    hipLaunchKernelGGL((wgrad_p8_kernel<f16_t, 0, X>), dim3((unsigned)g.tile0[n]), dim3(512), shmem, s, g); return TIMHIP_OK;
-    switch (atoi(v)) { W8S(1) W8S(2) W8S(4) W8S(5) W8S(8) W8S(3) default: break; }
-#undef W8S
-  }
-#endif
-  const bool two = tim_knobs().wgrad_p8_ph != 4;   // two 32-MFMA phases per step (TIMHIP_WGRAD_P8_PH=4: four 16-MFMA phases)
-  const bool rag = (M % WP_M) != 0;
-#define W8_LAUNCH(PH2_, RAG_) do { \
-    DISPATCH_H16(precision, (void)hipFuncSetAttribute((const void*)wgrad_p8_kernel<HT, 0, 0, PH2_, RAG_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem)); \
-    DISPATCH_H16(precision, hipLaunchKernelGGL((wgrad_p8_kernel<HT, 0, 0, PH2_, RAG_>), dim3((unsigned)g.tile0[n]), dim3(512), shmem, s, g)); } while (0)
-  if (two && rag) W8_LAUNCH(true, true);
-  else if (two) W8_LAUNCH(true, false);
-  else if (rag) W8_LAUNCH(false, true);
-  else W8_LAUNCH(false, false);
-#undef W8_LAUNCH
+  wgrad_fill_group(g, p, it, n, M, accumulate, out_scale);
+  g.pf_dist = p.pf_dist;
+  if (launch_wgrad_tuning(p, g, s)) return hipGetLastError() == hipSuccess ? TIMHIP_OK : TIMHIP_ELAUNCH;
+  if (p.family == WGRAD_LD) DISPATCH_H16(precision, launch_tiled<wgrad_ld_kernel<HT>>(p, g, s));
+  else if (p.family == WGRAD_PP8W) DISPATCH_H16(precision, launch_tiled<wgrad_pp_kernel<HT>>(p, g, s));
+  else if (p.phases == 2 && p.ragged) DISPATCH_H16(precision, (launch_tiled<wgrad_p8_kernel<HT, 0, 0, true, true>>(p, g, s)));
+  else if (p.phases == 2) DISPATCH_H16(precision, (launch_tiled<wgrad_p8_kernel<HT, 0, 0, true, false>>(p, g, s)));
+  else if (p.ragged) DISPATCH_H16(precision, (launch_tiled<wgrad_p8_kernel<HT, 0, 0, false, true>>(p, g, s)));
+  else DISPATCH_H16(precision, (launch_tiled<wgrad_p8_kernel<HT, 0, 0, false, false>>(p, g, s)));
   return hipGetLastError() == hipSuccess ? TIMHIP_OK : TIMHIP_ELAUNCH;
 }
