@@ -3,7 +3,8 @@ recognition/scripts/train.py:190-366 with every piece served by tim_amd:
 
     DeviceWindowDataset.batch()      <- DataLoader workers + default_collate + .cuda()      (sliding_window.py:341-421)
     model(times, "time_mlp"), model(inputs, "encoder", ...)                                  (models/tim.py)
-    mixup of the inputs              <- utils/mixup.py:4-22 (three lerps; stays torch ops on the device)
+    mixup of the inputs              <- utils/mixup.py:4-22 (host draws + three lerps here: an eager loop may; the captured
+                                        form with device-side draws, tim_amd.mixup, is examples/train_graphed_synthetic.py)
     losses.mixup_cross_entropy       <- criterion + mixup_criterion per head                (train.py:218-316)
     losses.dense_relative_localization_loss_crossmodal                                       (train.py:318-349)
     torch.optim.AdamW                                                                        (train.py:66-70)

@@ -727,6 +727,61 @@ int timhip_drloc_scatter_add(const float* d_pts, int ldg, float* dx1, float* dx2
                              int64_t row_stride, int n, int l, int D, const int64_t* pos1, const int64_t* pos2, int m,
                              void* stream);
 
+/* The same cross entropy with lam read from DEVICE memory (a mixup state that a captured step redraws, below): the arguments,
+ * the launches and the bits of timhip_ce_mixup_fwd / _bwd called with the float lam[0] holds when the forward's kernel runs.
+ * accum is [8] here: words 0-3 as above, word 4 = the lam the forward used; the backward reads THAT copy (it takes no lam),
+ * so a state redrawn between forward and backward does not reach it.  lam NULL: TIMHIP_EINVAL. */
+int timhip_ce_mixup_fwd_dev(const float* logits, int rows, int C, int ld, const int64_t* target_a, const int64_t* target_b,
+                            const float* lam, float smoothing, float* stats, float* accum, float* loss, void* stream);
+int timhip_ce_mixup_bwd_dev(const float* logits, int rows, int C, int ld, const int64_t* target_a, const int64_t* target_b,
+                            float smoothing, const float* stats, const float* accum, const float* grad_out,
+                            float* dlogits, int ldd, void* stream);
+
+/* ---------------------------------------------------------------- mixup of the inputs on the device (utils/mixup.py:4-22) */
+/* Draw: n independent mixup sets in one launch, nothing on the host taking part.  lam float[n]; perm, inv int32[n * B] with
+ * inv[s * B + perm[s * B + b]] == b.  counter: one 64-bit word in device memory, the number of sets drawn so far; the kernel
+ * reads it (c) and stores c + n (one thread, after every thread has read it), so the k-th set of a seed is the same bits
+ * whether its launch is eager or the k-th replay of a captured graph.  Set s of the launch is draw number D = c + s.
+ *   randomness  philox4x32_7 (csrc/common.h) with key = seed, site = SITE_MIXUP (8) and Philox counter (D << 24) | j, block
+ *               j = 0, 1, ... of four 32-bit words; D counts modulo 2^40.  The dropout salt is NOT added: a draw does not depend on
+ *               how many encoder forwards ran in between.
+ *   lam         ~ Beta(alpha, alpha), sampled exactly (up to the 2^-32 grid of a uniform u = (word + 0.5) / 2^32) by rejection,
+ *               in double precision, rounded to float at the end:
+ *                 alpha < 1   Johnk: X = u0^(1/alpha), Y = u1^(1/alpha) from words 0, 1 of block j = trial; accepted when
+ *                             X + Y <= 1; lam = X / (X + Y).  At most 64 trials; a trial is rejected with probability
+ *                             1 - Gamma(alpha+1)^2 / Gamma(2 alpha+1) <= 1/2, so the bound is hit with probability <= 2^-64
+ *                             per draw; lam is then 0.5.
+ *                 alpha >= 1  lam = G1 / (G1 + G2), two Marsaglia-Tsang Gamma(alpha) variates: d = alpha - 1/3, c = 1/sqrt(9d),
+ *                             x = sqrt(-2 ln u0) cos(2 pi u1), v = (1 + c x)^3, accepted when v > 0 and
+ *                             ln u2 < x^2/2 + d - d v + d ln v; G = d v.  G1 reads blocks 0..31, G2 blocks 32..63 (words
+ *                             0, 1, 2 of block = trial).  A trial is rejected with probability < 0.06 for every alpha >= 1, so
+ *                             32 trials all fail with probability < 1e-39 per variate; the variate is then d.
+ *               alpha <= 0: lam = 1 (utils/mixup.py:6) and the permutation is still drawn.  Supported:
+ *               TIMHIP_MIXUP_ALPHA_MIN <= alpha <= TIMHIP_MIXUP_ALPHA_MAX (below it u^(1/alpha) leaves the double range); any
+ *               other positive alpha, or NaN: TIMHIP_EINVAL.
+ *   perm        Fisher-Yates from the identity, i = B-1 .. 1: j = (uint64(r) * (i + 1)) >> 32, swap(perm[i], perm[j]); r = word
+ *               i & 3 of block 256 + (i >> 2).  Integer arithmetic only: a CPU restatement gives the same bits.  j is not
+ *               exactly uniform on 0..i: each value's probability is off by at most 2^-32, a total bias of at most B / 2^32
+ *               per swap.
+ * 1 <= B <= 2^20, 1 <= n <= 65536, else TIMHIP_EINVAL.  One thread per set, one block: a few microseconds at n = 1. */
+#define TIMHIP_MIXUP_ALPHA_MIN 0.05f
+#define TIMHIP_MIXUP_ALPHA_MAX 16.0f
+#define TIMHIP_MIXUP_MAX_TENSORS 4
+int timhip_mixup_draw(uint64_t seed, uint64_t* counter, float alpha, int B, int n, float* lam, int32_t* perm, int32_t* inv,
+                      void* stream);
+
+/* Apply: dst_t[b] = lam * src_t[b] + (1 - lam) * src_t[index[b]] for nt <= TIMHIP_MIXUP_MAX_TENSORS tensors in one launch;
+ * b = 0..B-1, item b of tensor t being the contiguous slab of elems[t] >= 1 elements at element offset b * elems[t].
+ * src, dst, elems, dtype: HOST arrays of nt entries; dtype[t] = TIMHIP_PREC_FP32, _F16 or _BF16 is the STORAGE type of src_t
+ * and dst_t (anything else: TIMHIP_EINVAL); the arithmetic is fp32 - two rounded products, one rounded sum, no fused
+ * multiply-add - and the result is rounded once to the storage type.  lam: device float; index: device int32[B] with entries
+ * in [0, B) (not checked).  dst_t must not overlap any src.  The backward of the mix is the same call on the output gradients
+ * with the inverse permutation as index.  Pointers need the alignment of their element only: items whose three slabs are
+ * 16-byte aligned move as 16-byte accesses, the tail of an item (elems not a multiple of 16 bytes) and items off that
+ * alignment element by element.  Byte-bound: two reads and one write per element. */
+int timhip_mixup_apply(int nt, const void* const* src, void* const* dst, const int64_t* elems, const int32_t* dtype, int B,
+                       const float* lam, const int32_t* index, void* stream);
+
 /* ---------------------------------------------------------------- detection losses */
 /* sigmoid focal loss (detection models/helpers/losses/sigmoid.py:5-52) under get_loss(.., weights, reduction="sum")
  * (losses/loss.py:5-14):  loss_sum = sum_{r: valid[r]} w[r] * sum_c focal(logits[r,c], targets[r,c]);  targets are the

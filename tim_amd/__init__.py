@@ -37,7 +37,10 @@ def __getattr__(name):  # lazy: importing the package must not require torch on 
     if name == "WindowCache":
         from .query import WindowCache
         return WindowCache
-    if name == "optim":
+    if name in ("Mixup", "mixup_data"):
+        from . import mixup as _mixup
+        return getattr(_mixup, name)
+    if name in ("optim", "mixup"):
         import importlib
-        return importlib.import_module(".optim", __name__)
+        return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

@@ -20,6 +20,8 @@ H16 = (PREC_BF16, PREC_F16)   # 16-bit operand storage (the MFMA GEMM / attentio
 
 # dropout site ids (csrc/common.h)
 SITE_FEAT_V, SITE_FEAT_A, SITE_SEQ = 1, 2, 3
+SITE_MIXUP = 8   # mixup.hip: lam and the permutation (its own device counter, no dropout salt)
+MIXUP_ALPHA_MIN, MIXUP_ALPHA_MAX, MIXUP_MAX_TENSORS = 0.05, 16.0, 4   # include/timhip.h: TIMHIP_MIXUP_*
 SITE_L_ATTN, SITE_L_DROP1, SITE_L_FFN, SITE_L_DROP2 = 0, 1, 2, 3
 
 
@@ -176,6 +178,10 @@ _SIGS = {
     "timhip_gather_rows": (C.c_int, [i32, vp, i32, i32, i32, i32, i32, vp, vp]),
     "timhip_ce_mixup_fwd": (C.c_int, [vp, i32, i32, i32, vp, vp, f32, f32, vp, vp, vp, vp]),
     "timhip_ce_mixup_bwd": (C.c_int, [vp, i32, i32, i32, vp, vp, f32, f32, vp, vp, vp, vp, i32, vp]),
+    "timhip_ce_mixup_fwd_dev": (C.c_int, [vp, i32, i32, i32, vp, vp, vp, f32, vp, vp, vp, vp]),
+    "timhip_ce_mixup_bwd_dev": (C.c_int, [vp, i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, i32, vp]),
+    "timhip_mixup_draw": (C.c_int, [u64, vp, f32, i32, i32, vp, vp, vp, vp]),
+    "timhip_mixup_apply": (C.c_int, [i32, vp, vp, vp, vp, i32, vp, vp, vp]),
     "timhip_focal_loss_fwd": (C.c_int, [vp, vp, i32, i32, vp, vp, f32, f32, vp, vp, vp]),
     "timhip_focal_loss_bwd": (C.c_int, [vp, vp, i32, i32, vp, vp, f32, f32, vp, vp, vp]),
     "timhip_diou_1d": (C.c_int, [vp, vp, i32, vp, f32, vp, vp, vp, vp]),

@@ -57,8 +57,11 @@ __global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ 
 }
 
 // loss = lam * sum_a / n_a + (1 - lam) * sum_b / n_b   (a term with no valid row is 0, as the training loop skips it)
+// lam_dev (NULL on the float path): lam lives in device memory - a mixup state a captured step redraws - and the value used is
+// kept in accum[4] for the backward (accum is [8] on that path)
 __global__ __launch_bounds__(256) void ce_finish_kernel(const float* __restrict__ stats, int rows, float lam,
-                                                        float* __restrict__ accum, float* __restrict__ loss) {
+                                                        const float* __restrict__ lam_dev, float* __restrict__ accum,
+                                                        float* __restrict__ loss) {
   __shared__ float red[4][4];
   float v[4] = {0.f, 0.f, 0.f, 0.f};
   for (int r = threadIdx.x; r < rows; r += 256) {
@@ -76,6 +79,7 @@ __global__ __launch_bounds__(256) void ce_finish_kernel(const float* __restrict_
     for (int k = 0; k < 4; ++k) { t[k] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]); accum[k] = t[k]; }
     const float la = t[1] > 0.f ? t[0] / t[1] : 0.f;
     const float lb = t[3] > 0.f ? t[2] / t[3] : 0.f;
+    if (lam_dev) { lam = lam_dev[0]; accum[4] = lam; }
     loss[0] = lam * la + (1.f - lam) * lb;
   }
 }
@@ -84,13 +88,15 @@ __global__ __launch_bounds__(256) void ce_finish_kernel(const float* __restrict_
 //   wa = lam / n_a if ya valid, wb = (1-lam) / n_b if yb valid
 __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ x, int rows, int C, int ld,
                                                      const long long* __restrict__ ya,
-                                                     const long long* __restrict__ yb, float lam, float eps,
+                                                     const long long* __restrict__ yb, float lam,
+                                                     const float* __restrict__ lam_dev, float eps,
                                                      const float* __restrict__ stats,
                                                      const float* __restrict__ accum, const float* __restrict__ gout,
                                                      float* __restrict__ dx, int ldd) {
   const int r = blockIdx.y;
   const float g = gout ? gout[0] : 1.f;
   const long long a = ya[r], b = yb ? yb[r] : -1;
+  if (lam_dev) lam = lam_dev[0];   // (the forward's copy, accum[4])
   const float wa = (a >= 0 && a < C && accum[1] > 0.f) ? g * lam / accum[1] : 0.f;
   const float wb = (b >= 0 && b < C && accum[3] > 0.f) ? g * (1.f - lam) / accum[3] : 0.f;
   const float lse = stats[4 * r], w = wa + wb, u = w * eps / (float)C;
@@ -408,8 +414,11 @@ int timhip_det_side_loss_bwd(const float* const* logits, const float* const* tar
   return TIMHIP_OK;
 }
 
-int timhip_ce_mixup_fwd(const float* logits, int rows, int C, int ld, const int64_t* target_a, const int64_t* target_b,
-                        float lam, float smoothing, float* stats, float* accum, float* loss, void* stream) {
+}  // extern "C"
+
+namespace {
+int ce_mixup_fwd(const float* logits, int rows, int C, int ld, const int64_t* target_a, const int64_t* target_b, float lam,
+                 const float* lam_dev, float smoothing, float* stats, float* accum, float* loss, void* stream) {
   if (!logits || !target_a || !stats || !accum || !loss || rows <= 0 || C <= 0 || ld < C) return TIMHIP_EINVAL;
   if (smoothing < 0.f || smoothing >= 1.f) return TIMHIP_EINVAL;
   hipStream_t s = (hipStream_t)stream;
@@ -420,22 +429,51 @@ int timhip_ce_mixup_fwd(const float* logits, int rows, int C, int ld, const int6
     hipLaunchKernelGGL(ce_rows_kernel<1>, dim3((rows + 3) / 4), dim3(256), 0, s, logits, rows, C, ld,
                        (const long long*)target_a, (const long long*)target_b, smoothing, stats);
   TIM_CHECK_LAUNCH();
-  hipLaunchKernelGGL(ce_finish_kernel, dim3(1), dim3(256), 0, s, stats, rows, lam, accum, loss);
+  hipLaunchKernelGGL(ce_finish_kernel, dim3(1), dim3(256), 0, s, stats, rows, lam, lam_dev, accum, loss);
   TIM_CHECK_LAUNCH();
   return TIMHIP_OK;
+}
+
+int ce_mixup_bwd(const float* logits, int rows, int C, int ld, const int64_t* target_a, const int64_t* target_b, float lam,
+                 const float* lam_dev, float smoothing, const float* stats, const float* accum, const float* grad_out,
+                 float* dlogits, int ldd, void* stream) {
+  if (!logits || !target_a || !stats || !accum || !dlogits || rows <= 0 || C <= 0 || ld < C || ldd < C)
+    return TIMHIP_EINVAL;
+  dim3 grid((C + 1023) / 1024 > 8 ? 8 : (C + 1023) / 1024, rows);
+  hipLaunchKernelGGL(ce_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, logits, rows, C, ld,
+                     (const long long*)target_a, (const long long*)target_b, lam, lam_dev, smoothing, stats, accum, grad_out,
+                     dlogits, ldd);
+  TIM_CHECK_LAUNCH();
+  return TIMHIP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int timhip_ce_mixup_fwd(const float* logits, int rows, int C, int ld, const int64_t* target_a, const int64_t* target_b,
+                        float lam, float smoothing, float* stats, float* accum, float* loss, void* stream) {
+  return ce_mixup_fwd(logits, rows, C, ld, target_a, target_b, lam, nullptr, smoothing, stats, accum, loss, stream);
 }
 
 int timhip_ce_mixup_bwd(const float* logits, int rows, int C, int ld, const int64_t* target_a, const int64_t* target_b,
                         float lam, float smoothing, const float* stats, const float* accum, const float* grad_out,
                         float* dlogits, int ldd, void* stream) {
-  if (!logits || !target_a || !stats || !accum || !dlogits || rows <= 0 || C <= 0 || ld < C || ldd < C)
-    return TIMHIP_EINVAL;
-  dim3 grid((C + 1023) / 1024 > 8 ? 8 : (C + 1023) / 1024, rows);
-  hipLaunchKernelGGL(ce_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, logits, rows, C, ld,
-                     (const long long*)target_a, (const long long*)target_b, lam, smoothing, stats, accum, grad_out,
-                     dlogits, ldd);
-  TIM_CHECK_LAUNCH();
-  return TIMHIP_OK;
+  return ce_mixup_bwd(logits, rows, C, ld, target_a, target_b, lam, nullptr, smoothing, stats, accum, grad_out, dlogits, ldd,
+                      stream);
+}
+
+int timhip_ce_mixup_fwd_dev(const float* logits, int rows, int C, int ld, const int64_t* target_a, const int64_t* target_b,
+                            const float* lam, float smoothing, float* stats, float* accum, float* loss, void* stream) {
+  if (!lam) return TIMHIP_EINVAL;
+  return ce_mixup_fwd(logits, rows, C, ld, target_a, target_b, 0.f, lam, smoothing, stats, accum, loss, stream);
+}
+
+int timhip_ce_mixup_bwd_dev(const float* logits, int rows, int C, int ld, const int64_t* target_a, const int64_t* target_b,
+                            float smoothing, const float* stats, const float* accum, const float* grad_out,
+                            float* dlogits, int ldd, void* stream) {
+  if (!accum) return TIMHIP_EINVAL;
+  return ce_mixup_bwd(logits, rows, C, ld, target_a, target_b, 0.f, accum + 4, smoothing, stats, accum, grad_out, dlogits,
+                      ldd, stream);
 }
 
 int timhip_drloc_gather(int precision, const float* x1, const float* x2, int64_t batch_stride, int64_t row_stride,

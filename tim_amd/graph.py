@@ -13,6 +13,9 @@ What makes the HIP path capturable:
   * workspaces / saved activations come from torch's allocator, so they land in the graph's private pool;
   * dropout seeds are launch arguments, which a graph would freeze - `functional.graph_safe_dropout` moves the per-step part
     of the seed into a device word that a node of the graph advances (include/timhip.h: timhip_dropout_salt);
+  * mixup's lam and permutation are host draws in the reference, which a graph would freeze as well - a step that calls
+    `tim_amd.mixup.Mixup.draw()` inside `fn` redraws both on EVERY replay (the draw kernel numbers its sets with a counter it
+    advances in device memory; `Mixup.mix`, `Mixup.targets` and the cross entropy read the state from device memory);
   * the operand-dtype weight copies are rebuilt by a cast kernel at the head of the captured step, so an optimizer update
     between (or inside) replays is always picked up; with `optimizer=` a `tim_amd.optim.FusedAdamW` the captured update
     writes them itself and that cast is dropped.

@@ -21,6 +21,11 @@ from .functional import _f32c, _require_gpu, _ru, _stream
 # ==================================================================================================
 # label-smoothed cross entropy (+ mixup)
 # ==================================================================================================
+def _is_device_lam(lam):
+    """a one-element CUDA tensor: the loss stays a function of that device word (no host read, capturable, redrawn per replay)"""
+    return isinstance(lam, torch.Tensor) and lam.is_cuda and lam.numel() == 1
+
+
 class _MixupCEFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, target_a, target_b, lam, smoothing):
@@ -40,11 +45,20 @@ class _MixupCEFn(torch.autograd.Function):
             ctx.shape = tuple(x.shape)
             return loss.zero_()
         stats = torch.empty((rows, 4), dtype=torch.float32, device=dev)
-        accum = torch.empty(4, dtype=torch.float32, device=dev)
-        call("timhip_ce_mixup_fwd", ptr(x), rows, Cn, x.stride(0), ptr(ta), ptr(tb), float(lam), float(smoothing),
-             ptr(stats), ptr(accum), ptr(loss), _stream())
+        ctx.lam_dev = _is_device_lam(lam)
+        if ctx.lam_dev:   # lam is a device word (tim_amd.mixup): it is read when the kernel runs, and kept in accum[4] for the backward
+            lam_t = lam.detach().to(device=dev, dtype=torch.float32).reshape(1)
+            accum = torch.empty(8, dtype=torch.float32, device=dev)
+            call("timhip_ce_mixup_fwd_dev", ptr(x), rows, Cn, x.stride(0), ptr(ta), ptr(tb), ptr(lam_t), float(smoothing),
+                 ptr(stats), ptr(accum), ptr(loss), _stream())
+            ctx.lam = None
+        else:
+            accum = torch.empty(4, dtype=torch.float32, device=dev)
+            call("timhip_ce_mixup_fwd", ptr(x), rows, Cn, x.stride(0), ptr(ta), ptr(tb), float(lam), float(smoothing),
+                 ptr(stats), ptr(accum), ptr(loss), _stream())
+            ctx.lam = float(lam)
         ctx.empty = False
-        ctx.lam, ctx.smoothing = float(lam), float(smoothing)
+        ctx.smoothing = float(smoothing)
         ctx.save_for_backward(x, ta, tb if tb is not None else ta.new_empty(0), stats, accum)
         ctx.has_b = tb is not None
         return loss
@@ -57,6 +71,10 @@ class _MixupCEFn(torch.autograd.Function):
         rows, Cn = x.shape
         gout = _f32c(g).reshape(1)
         dx = torch.empty_like(x)
+        if ctx.lam_dev:
+            call("timhip_ce_mixup_bwd_dev", ptr(x), rows, Cn, x.stride(0), ptr(ta), ptr(tb) if ctx.has_b else None, ctx.smoothing,
+                 ptr(stats), ptr(accum), ptr(gout), ptr(dx), dx.stride(0), _stream())
+            return dx, None, None, None, None
         call("timhip_ce_mixup_bwd", ptr(x), rows, Cn, x.stride(0), ptr(ta), ptr(tb) if ctx.has_b else None, ctx.lam,
              ctx.smoothing, ptr(stats), ptr(accum), ptr(gout), ptr(dx), dx.stride(0), _stream())
         return dx, None, None, None, None
@@ -64,7 +82,9 @@ class _MixupCEFn(torch.autograd.Function):
 
 def mixup_cross_entropy(logits, target_a, target_b, lam, label_smoothing=0.2):
     """lam * CE(logits[target_a != -1], target_a[...]).mean() + (1-lam) * CE(logits[target_b != -1], target_b[...]).mean()
-    with label smoothing - the value train.py:243-258 computes per head - in one pass over `logits`."""
+    with label smoothing - the value train.py:243-258 computes per head - in one pass over `logits`.  `lam`: a Python number,
+    or the one-element CUDA tensor of a `tim_amd.mixup.Mixup` - then the kernels read it from device memory, and the backward
+    uses the value its forward read even if the state was redrawn in between."""
     return _MixupCEFn.apply(logits, target_a, target_b, lam, label_smoothing)
 
 
@@ -83,7 +103,13 @@ class CrossEntropyLoss(torch.nn.Module):
 
 
 def mixup_criterion(criterion, pred_a, pred_b, y_a, y_b, lam, weights=None):
-    """utils/mixup.py:24-39, same arguments.  (`weights` scales the two terms exactly as the reference does.)"""
+    """utils/mixup.py:24-39, same arguments.  (`weights` scales the two terms exactly as the reference does.)  `lam` may be the
+    one-element CUDA tensor of a `tim_amd.mixup.Mixup`; with this module's `CrossEntropyLoss` as the criterion, equal predictions
+    and no weights that is the one-pass device form (`mixup_cross_entropy`), otherwise two criterion calls blended by tensor ops."""
+    if _is_device_lam(lam):
+        if isinstance(criterion, CrossEntropyLoss) and pred_a is pred_b and weights is None:
+            return mixup_cross_entropy(pred_a, y_a, y_b, lam, criterion.label_smoothing)
+        lam = lam.reshape(())
     loss_a = criterion(pred_a, y_a)
     loss_b = criterion(pred_b, y_b)
     if weights is not None:
