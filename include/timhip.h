@@ -423,6 +423,11 @@ int timhip_attention_bwd(const TimDesc* d, const void* qkv, const void* o, const
                          const void* d_o, void* dqkv, void* workspace, size_t workspace_bytes,
                          void* stream);
 size_t timhip_attention_bwd_workspace_bytes(const TimDesc* d);
+/* timhip_attention_bwd handed the keep-bits of the layer's attention dropout (timhip_attn_keep_bits' words, [B * H * S][2], 16-byte
+ * aligned; NULL: exactly timhip_attention_bwd), as the layer backward hands them to it: the fused kernels of the geometry that call
+ * serves read the bits instead of drawing the mask themselves; every other kernel ignores them.  The same results, bit for bit. */
+int timhip_attention_bwd_keep_bits(const TimDesc* d, const void* qkv, const void* o, const float* lse, const void* d_o, void* dqkv,
+                                   void* workspace, size_t workspace_bytes, const void* keep_bits, void* stream);
 
 /* dW[Nout,Kout] += dY[M,Nout]^T X[M,Kout] and (db != NULL) db[Nout] += colsum(dY): weight/bias
  * gradients of one nn.Linear.  workspace (timhip_wgrad_workspace_bytes) holds the transposed

@@ -142,6 +142,7 @@ _SIGS = {
     "timhip_attention_weights": (C.c_int, [C.POINTER(TimDesc), vp, i32, i32, vp, i32, vp]),
     "timhip_attention_bwd": (C.c_int, [C.POINTER(TimDesc), vp, vp, vp, vp, vp, vp, sz, vp]),
     "timhip_attention_bwd_workspace_bytes": (sz, [C.POINTER(TimDesc)]),
+    "timhip_attention_bwd_keep_bits": (C.c_int, [C.POINTER(TimDesc), vp, vp, vp, vp, vp, vp, sz, vp, vp]),
     "timhip_time_l1_fwd": (C.c_int, [i32, vp, i32, i32, vp, vp, vp, i32, vp]),
     "timhip_time_l1_fwd_split3": (C.c_int, [i32, vp, i32, i32, vp, vp, vp, i32, vp]),
     "timhip_time_l1_bwd": (C.c_int, [i32, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp]),

@@ -224,6 +224,7 @@ void read_knobs(TimKnobs& k) {
   k.gemm_small_nst = env_int("TIMHIP_GEMM_SMALL_NST", k.gemm_small_nst); k.gemm_small_w8 = env_int("TIMHIP_GEMM_SMALL_W8", k.gemm_small_w8); k.gemm_p8_ph = env_int("TIMHIP_GEMM_P8_PH", k.gemm_p8_ph);
   k.gemm_pp_min = env_int("TIMHIP_GEMM_PP_MIN_TILES", k.gemm_pp_min);
   k.attn_ks = env_int("TIMHIP_ATTN_KS", k.attn_ks);
+  k.attn_bwd_co = env_int("TIMHIP_ATTN_BWD_CO", k.attn_bwd_co);
   k.gemm_p8 = env_int("TIMHIP_GEMM_P8", k.gemm_p8);
   k.ln_pair = env_int("TIMHIP_LN_PAIR", k.ln_pair);
   k.epi_pair = env_int("TIMHIP_EPI_PAIR", k.epi_pair);

@@ -204,6 +204,13 @@ int timhip_attention_bwd(const TimDesc* d, const void* qkv, const void* o, const
   if (!d) return TIMHIP_EINVAL;
   return tim_attention_bwd(*d, qkv, o, lse, d_o, dqkv, workspace, workspace_bytes, (hipStream_t)stream);
 }
+int timhip_attention_bwd_keep_bits(const TimDesc* d, const void* qkv, const void* o, const float* lse, const void* d_o, void* dqkv,
+                                   void* workspace, size_t workspace_bytes, const void* keep_bits, void* stream) {
+  if (!d) return TIMHIP_EINVAL;
+  if (reinterpret_cast<uintptr_t>(keep_bits) & 15) return TIMHIP_EALIGN;
+  return tim_attention_bwd(*d, qkv, o, lse, d_o, dqkv, workspace, workspace_bytes, (hipStream_t)stream,
+                           static_cast<const unsigned long long*>(keep_bits));
+}
 int timhip_attention_fwd_rows(const TimDesc* d, const void* qkv, int s0, void* o_rows, void* stream) {
   if (!d || d->p_drop != 0.f) return TIMHIP_EINVAL;
   return tim_attention_fwd(*d, qkv, o_rows, nullptr, (hipStream_t)stream, nullptr, s0);

@@ -11,6 +11,7 @@
 #include <stdlib.h>
 
 #include "attention.h"
+#include "attn_bwd_plan.h"
 #include "mfma_tiles.h"
 
 namespace {
@@ -707,6 +708,332 @@ __global__ __launch_bounds__(256) void attn_bwd_keys(const HT* __restrict__ dS_s
   }
 }
 
+// CO (co-resident form of the key-split fused backward; TIMHIP_ATTN_BWD_CO): the same arithmetic per element - the same products
+// on the same 16-bit dS / P~ - in a FOUR-wave block of 80 KiB, so that two blocks share a CU and one's loads and stores run under
+// the other's arithmetic.  What the 149 KB form keeps for a phase 2 at the end (dS and P~ of every row) lives for one 32-row sweep
+// only: dK and dV are accumulated per sweep in registers (wave w: head-dim block w of all four key blocks, 8 tiles = 128
+// accumulator registers), in row order.  LDS: attn_bwd_plan.h.  Per sweep s, five LDS-only barriers:
+//   P0  every thread: its Q / dO chunks of the sweep (requested one sweep ahead) into the sweep space; delta, the self terms and
+//       a query token's own key / value gradient rows on the way (as the key-split form's sweep_store)
+//   P1  wave w: the TRANSPOSED fragments of Q and dO it needs for dK / dV (head-dim block w, 32 rows: 16 registers), then
+//       S^T and dP^T of key block w from row-major fragments read as they are consumed
+//   P2  the sweep space is dead: the rows' (delta, dS self term, lse) into the first 16 bytes that lane (row, g = 0) of wave w
+//       will store dS to - four copies, one per wave; the next sweep's Q / dO / lse requests go out
+//   P3  lane (row, g) of wave w reads its row's scalars (program order keeps the read ahead of the stores of its own pair of
+//       lanes; no other lane touches those bytes), forms dS / P~ of key block w and stores them over Q / dO
+//   P4  wave w: dK += dS^T Q and dV += P~^T dO with the fragments of P1; then - those fragments are dead - the next sweep's O and
+//       own key / value requests; then dQ of head-dim block w (as the key-split form's 1b unit)
+// Every wave does the same work in every phase: there are no uneven roles to rotate between co-resident blocks.
+template <typename HT, bool KB>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void attn_bwd_co(const HT* __restrict__ qkv, const HT* __restrict__ o, const float* __restrict__ lse, const HT* __restrict__ d_o,
+                 HT* __restrict__ dqkv, AttnArgs a) {
+  constexpr int DH = 128, NKK = DH / 16, NJB = 4;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* sK = smem;
+  char* sV = sK + 128 * DH * 2;
+  char* sS = sV + 128 * DH * 2;   // [32][128]: Q of the sweep, then its dS
+  char* sP = sS + 32 * 128 * 2;   // [32][128]: dO of the sweep, then its P~
+  const int bh = blockIdx.x;
+  const int b = bh / a.H, h = bh % a.H;
+  const int S = a.S, F = a.F, E = a.E;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int li = lane & 31, g = lane >> 5;
+  const size_t ld = (size_t)3 * E;
+  const HT* base = qkv + (size_t)b * S * ld + (size_t)h * DH;
+  HT* dbase = dqkv + (size_t)b * S * ld + (size_t)h * DH;
+  const HT* dobase = d_o + (size_t)b * S * E + (size_t)h * DH;
+  const HT* obase = o + (size_t)b * S * E + (size_t)h * DH;
+  const float* lsebase = lse + ((size_t)b * a.H + h) * S;
+  const int nsw = (S + 31) >> 5;
+  const int c = tid & 15, r0 = tid >> 4;   // this thread's 16-byte chunk and its rows r0, r0 + 16 of a sweep
+
+  // one sweep's operand chunks of this thread: Q, dO, O, and (query rows) the own key / value rows; the rows' lse
+  vec8<HT> q8[2], d8[2], o8[2], k8[2], v8[2];
+  float ls[2];
+  auto load_qd = [&](int sw, int c, int r0) {
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const int row = 32 * sw + r0 + 16 * p;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { q8[p][e] = (HT)0.f; d8[p][e] = (HT)0.f; }
+      ls[p] = 0.f;
+      if (row < S) {
+        q8[p] = *reinterpret_cast<const vec8<HT>*>(base + (size_t)row * ld + c * 8);
+        d8[p] = *reinterpret_cast<const vec8<HT>*>(dobase + (size_t)row * E + c * 8);
+        ls[p] = lsebase[row];
+      }
+    }
+  };
+  auto load_okv = [&](int sw, int c, int r0) {
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const int row = 32 * sw + r0 + 16 * p;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { o8[p][e] = (HT)0.f; k8[p][e] = (HT)0.f; v8[p][e] = (HT)0.f; }
+      if (row < S) {
+        o8[p] = *reinterpret_cast<const vec8<HT>*>(obase + (size_t)row * E + c * 8);
+        if (row >= F) {
+          k8[p] = *reinterpret_cast<const vec8<HT>*>(base + (size_t)row * ld + E + c * 8);
+          v8[p] = *reinterpret_cast<const vec8<HT>*>(base + (size_t)row * ld + 2 * E + c * 8);
+        }
+      }
+    }
+  };
+  {
+    // request order = arrival order: the K / V tiles (rows r0 + 16 u; rows >= F are zeros, not loads), then sweep 0
+    vec8<HT> kst[8], vst[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int row = r0 + 16 * u;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { kst[u][e] = (HT)0.f; vst[u][e] = (HT)0.f; }
+      if (row < F) {
+        kst[u] = *reinterpret_cast<const vec8<HT>*>(base + (size_t)row * ld + E + c * 8);
+        vst[u] = *reinterpret_cast<const vec8<HT>*>(base + (size_t)row * ld + 2 * E + c * 8);
+      }
+    }
+    load_qd(0, c, r0);
+    load_okv(0, c, r0);
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int to = tile_off<128>(r0 + 16 * u, c);
+      *reinterpret_cast<vec8<HT>*>(sK + to) = kst[u];
+      *reinterpret_cast<vec8<HT>*>(sV + to) = vst[u];
+    }
+  }
+  uint32_t kw_cur = 0u, kw_next = 0u;
+  // KB: the 16 keep-bits of (row, key half g, key block = wave): bit 8 qp + 4 t' + t = key 32 jb + 16 qp + 8 t' + 4 g + t
+  auto load_kw = [&](int sw, int li, int g) -> uint32_t {
+    const int rowc = min(sw * 32 + li, S - 1);
+    return (uint32_t)*reinterpret_cast<const unsigned short*>(reinterpret_cast<const char*>(a.kbits) +
+                                                              ((((size_t)bh * S + rowc) << 1) + g) * 8 + 2 * wave);
+  };
+  if constexpr (KB) kw_cur = load_kw(0, li, g);
+
+  // Lane-derived LDS offsets are recomputed per phase from a laundered lane id: hoisted out of the sweep loop, the ~90 swizzled
+  // offsets of a sweep's reads would live (and spill) beside the 128 accumulator registers
+  auto fresh = [](int x) { asm volatile("" : "+v"(x)); return x; };
+  // transposing-read offsets of the key-side products (phase 2 of the 149 KB form): column chunk 4 cb + ... of a [32][128] tile,
+  // + 4096 per 16 rows.  X = Q / dO: cb = head-dim block `wave`; Y = dS / P~: cb = key block j
+  auto tr_off = [&](int ln, int cb, int hh) {
+    const int gid = ln >> 4, p = ln & 15, g2 = gid >> 1;
+    return tile_off<128>(4 * g2 + (p >> 2) + 8 * hh, 4 * cb + 2 * (gid & 1) + ((p & 3) >> 1)) + (p & 1) * 8;
+  };
+  f32x16_t accK[NJB], accV[NJB];
+#pragma unroll
+  for (int j = 0; j < NJB; ++j)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { accK[j][r] = 0.f; accV[j][r] = 0.f; }
+
+#pragma unroll 1
+  for (int sw = 0; sw < nsw; ++sw) {
+    const int tf = fresh(tid), lane = tf & 63, li = lane & 31, g = lane >> 5, c = tf & 15, r0 = tf >> 4;   // (shadow the hoistable ones)
+    // ---- P0: Q / dO of the sweep into LDS; per-row scalars; own key / value gradient rows of query tokens
+    float dl_[2], dss_[2];
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const int rl = r0 + 16 * p, row = 32 * sw + rl;
+      const bool isq = row < S && row >= F;
+      const int to = tile_off<128>(rl, c);
+      *reinterpret_cast<vec8<HT>*>(sS + to) = q8[p];
+      *reinterpret_cast<vec8<HT>*>(sP + to) = d8[p];
+      const float dl = row16_sum(dot8(d8[p], o8[p]));
+      float t = 0.f, u = 0.f;
+      if (32 * sw + 31 >= F) {   // (block-uniform: the sweep holds query rows)
+        t = row16_sum(dot8(q8[p], k8[p]));
+        u = row16_sum(dot8(d8[p], v8[p]));
+      }
+      float ds_self = 0.f, pt_self = 0.f;
+      if (isq) {
+        const uint64_t rowbase = (((uint64_t)b * a.H + h) * S + row) * (uint64_t)a.LP;
+        const float pr = __expf(t * a.scale - ls[p]);
+        const float keep = a.thr != 0u ? keep1(a, rowbase, F) : 1.f;
+        ds_self = pr * (u * keep - dl) * a.scale;
+        pt_self = pr * keep;
+        HT* dq = dbase + (size_t)row * ld + c * 8;
+        float kself[8], vself[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { kself[e] = ds_self * (float)q8[p][e]; vself[e] = pt_self * (float)d8[p][e]; }
+        store8_h<HT>(dq + E, kself);
+        store8_h<HT>(dq + 2 * E, vself);
+      }
+      dl_[p] = dl; dss_[p] = ds_self;
+    }
+    lds_barrier();
+
+    // ---- P1: transposed Q / dO fragments for the key side; S^T and dP^T of key block `wave`
+    vec8<HT> xq[2], xd[2];
+    {
+      const int l1 = fresh(lane), x0 = tr_off(l1, wave, 0), x1 = tr_off(l1, wave, 1);
+#pragma unroll
+      for (int ms = 0; ms < 2; ++ms) {
+        xq[ms] = cat8<HT>(tr_read<HT>(sS + x0 + ms * 4096), tr_read<HT>(sS + x1 + ms * 4096));
+        xd[ms] = cat8<HT>(tr_read<HT>(sP + x0 + ms * 4096), tr_read<HT>(sP + x1 + ms * 4096));
+      }
+    }
+    f32x16_t sc, dp;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { sc[r] = 0.f; dp[r] = 0.f; }
+    const int l1 = fresh(lane), i1 = l1 & 31, g1 = l1 >> 5;
+#pragma unroll
+    for (int kk = 0; kk < NKK; ++kk) {
+      const vec8<HT> kf = *reinterpret_cast<const vec8<HT>*>(sK + tile_off<DH>(wave * 32 + i1, kk * 2 + g1));
+      const vec8<HT> qf = *reinterpret_cast<const vec8<HT>*>(sS + tile_off<128>(i1, kk * 2 + g1));
+      const vec8<HT> vf = *reinterpret_cast<const vec8<HT>*>(sV + tile_off<DH>(wave * 32 + i1, kk * 2 + g1));
+      const vec8<HT> df = *reinterpret_cast<const vec8<HT>*>(sP + tile_off<128>(i1, kk * 2 + g1));
+      sc = mfma16<HT>(kf, qf, sc);
+      dp = mfma16<HT>(vf, df, dp);
+      if (kk & 1) __builtin_amdgcn_sched_barrier(0);   // (at most two steps' fragments in flight: the accumulators own the registers)
+    }
+    lds_barrier();
+
+    // ---- P2: the rows' scalars through the dead sweep space (one copy per wave), then the next sweep's requests
+    if (c < 4) {
+#pragma unroll
+      for (int p = 0; p < 2; ++p) {
+        typedef float f4_t __attribute__((ext_vector_type(4)));
+        f4_t v; v[0] = dl_[p]; v[1] = dss_[p]; v[2] = ls[p]; v[3] = 0.f;
+        *reinterpret_cast<f4_t*>(sS + tile_off<128>(r0 + 16 * p, 4 * c)) = v;
+      }
+    }
+    if (sw + 1 < nsw) {
+      load_qd(sw + 1, c, r0);
+      if constexpr (KB) kw_next = load_kw(sw + 1, li, g);
+    }
+    lds_barrier();
+
+    // ---- P3: dS / P~ of (sweep, key block `wave`) over the sweep's Q / dO
+    const int row = sw * 32 + li;
+    const bool valid = row < S;
+    const int rowc = valid ? row : S - 1;
+    float ds_self;
+    {
+      typedef float f4_t __attribute__((ext_vector_type(4)));
+      const f4_t v = *reinterpret_cast<const f4_t*>(sS + tile_off<128>(li, 4 * wave));
+      const float delta = v[0], l2 = v[2] * 1.44269504088896341f, c2 = a.scale * 1.44269504088896341f;
+      ds_self = v[1];
+      asm volatile("" ::: "memory");   // the read above stays ahead of the 16-bit stores below (other types, the same bytes)
+      const uint64_t rowbase = (((uint64_t)b * a.H + h) * S + rowc) * (uint64_t)a.LP;
+#pragma unroll
+      for (int qp2 = 0; qp2 < 2; ++qp2) {
+        float kk2[2][4] = {{1.f, 1.f, 1.f, 1.f}, {1.f, 1.f, 1.f, 1.f}};
+        if constexpr (KB) {
+          const int ds = __float_as_int(a.dscale);
+#pragma unroll
+          for (int h2 = 0; h2 < 2; ++h2)
+#pragma unroll
+            for (int t = 0; t < 4; ++t) kk2[h2][t] = __int_as_float(__builtin_amdgcn_sbfe((int)kw_cur, 8 * qp2 + 4 * h2 + t, 1) & ds);
+        } else if (a.thr != 0u) keep_pair(a, rowbase, wave * 32 + 16 * qp2, g, kk2[0], kk2[1]);
+#pragma unroll
+        for (int h2 = 0; h2 < 2; ++h2)
+#pragma unroll
+          for (int t = 0; t < 4; ++t) {
+            const int q = 2 * qp2 + h2, r = 4 * q + t;
+            const int key = wave * 32 + 8 * q + 4 * g + t;
+            // p = exp(s scale - lse) as one fma + v_exp_f32 (base 2); dS = p scale (dP keep - delta)
+            const float pr = key < F ? __builtin_amdgcn_exp2f(fmaf(sc[r], c2, -l2)) : 0.f;
+            sc[r] = (pr * a.scale) * fmaf(dp[r], kk2[h2][t], -delta);
+            dp[r] = pr * kk2[h2][t];
+          }
+      }
+#pragma unroll
+      for (int p2 = 0; p2 < 2; ++p2) {
+        float vs[8], vp[8];
+        pair_exchange(vs, sc[8 * p2], sc[8 * p2 + 1], sc[8 * p2 + 2], sc[8 * p2 + 3], sc[8 * p2 + 4], sc[8 * p2 + 5],
+                      sc[8 * p2 + 6], sc[8 * p2 + 7], g);
+        pair_exchange(vp, dp[8 * p2], dp[8 * p2 + 1], dp[8 * p2 + 2], dp[8 * p2 + 3], dp[8 * p2 + 4], dp[8 * p2 + 5],
+                      dp[8 * p2 + 6], dp[8 * p2 + 7], g);
+        if (!valid) {   // padded rows of the last sweep contribute nothing to dK / dV (nor to a dQ that is never stored)
+#pragma unroll
+          for (int u = 0; u < 8; ++u) { vs[u] = 0.f; vp[u] = 0.f; }
+        }
+        const int to = tile_off<128>(li, wave * 4 + 2 * p2 + g);
+        store8_h<HT>(reinterpret_cast<HT*>(sS + to), vs);
+        store8_h<HT>(reinterpret_cast<HT*>(sP + to), vp);
+      }
+      kw_cur = kw_next;
+    }
+    lds_barrier();
+
+    // ---- P4: the key side of the sweep, then dQ of head-dim block `wave` over all keys (dS from LDS in tr_frag's k-order)
+    const int lk = fresh(lane);
+#pragma unroll
+    for (int ms = 0; ms < 2; ++ms)
+#pragma unroll
+      for (int j = 0; j < NJB; ++j) {
+        const int y0 = tr_off(lk, j, 0) + ms * 4096, y1 = tr_off(lk, j, 1) + ms * 4096;
+        const vec8<HT> ys = cat8<HT>(tr_read<HT>(sS + y0), tr_read<HT>(sS + y1));
+        const vec8<HT> yp = cat8<HT>(tr_read<HT>(sP + y0), tr_read<HT>(sP + y1));
+        accK[j] = mfma16<HT>(xq[ms], ys, accK[j]);
+        accV[j] = mfma16<HT>(xd[ms], yp, accV[j]);
+        if (j & 1) __builtin_amdgcn_sched_barrier(0);
+      }
+    if (sw + 1 < nsw) load_okv(sw + 1, c, r0);   // (O and the own key / value rows: wanted by the next P0's scalars only)
+    {
+      const bool isq = rowc >= F;
+      const HT* qp = base + (size_t)rowc * ld;
+      f32x16_t qa;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) qa[r] = 0.f;
+      vec8<HT> ksf[2];   // a query row's own key (the self term of dQ): requested before the products
+#pragma unroll
+      for (int p2 = 0; p2 < 2; ++p2) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) ksf[p2][e] = (HT)0.f;
+        if (isq) ksf[p2] = *reinterpret_cast<const vec8<HT>*>(qp + E + 32 * wave + 16 * p2 + 8 * g);
+      }
+      const int l4 = fresh(lane), i4 = l4 & 31, g4 = l4 >> 5;
+#pragma unroll
+      for (int jb = 0; jb < NJB; ++jb)
+#pragma unroll
+        for (int aa = 0; aa < 2; ++aa) {
+          // k-slot u of lane (row, g) <-> key 32 jb + 16 aa + 8 (u >> 2) + 4 g + (u & 3)   (mfma_tiles.h: tr_frag)
+          typedef HT h4_t __attribute__((ext_vector_type(4)));
+          const h4_t lo = *reinterpret_cast<const h4_t*>(sS + tile_off<128>(i4, jb * 4 + 2 * aa) + 8 * g4);
+          const h4_t hi = *reinterpret_cast<const h4_t*>(sS + tile_off<128>(i4, jb * 4 + 2 * aa + 1) + 8 * g4);
+          vec8<HT> sf;
+          sf[0] = lo[0]; sf[1] = lo[1]; sf[2] = lo[2]; sf[3] = lo[3]; sf[4] = hi[0]; sf[5] = hi[1]; sf[6] = hi[2]; sf[7] = hi[3];
+          const vec8<HT> kf = tr_frag<DH, HT>(sK, jb * 32 + 16 * aa, wave, l4);
+          qa = mfma16<HT>(kf, sf, qa);
+          if (aa) __builtin_amdgcn_sched_barrier(0);
+        }
+      HT* dq = dbase + (size_t)row * ld;
+#pragma unroll
+      for (int p2 = 0; p2 < 2; ++p2) {
+        float v[8];
+        pair_exchange(v, qa[8 * p2], qa[8 * p2 + 1], qa[8 * p2 + 2], qa[8 * p2 + 3], qa[8 * p2 + 4], qa[8 * p2 + 5],
+                      qa[8 * p2 + 6], qa[8 * p2 + 7], g);
+        if (valid) {
+#pragma unroll
+          for (int u = 0; u < 8; ++u) v[u] = fmaf(ds_self, (float)ksf[p2][u], v[u]);   // (ds_self = 0 for feature rows)
+          store8_h<HT>(dq + 32 * wave + 16 * p2 + 8 * g, v);
+        }
+      }
+    }
+    lds_barrier();
+  }
+
+  // dK / dV of the F feature keys: lane owns key 32 j + li, head-dim columns 32 wave + 16 p2 + 8 g .. + 7
+#pragma unroll
+  for (int prod = 0; prod < 2; ++prod) {
+    HT* out = dbase + (prod ? 2 * E : E);
+#pragma unroll
+    for (int j = 0; j < NJB; ++j) {
+      const f32x16_t& acc = prod ? accV[j] : accK[j];
+      const int n = j * 32 + li;
+#pragma unroll
+      for (int p2 = 0; p2 < 2; ++p2) {
+        float v[8];
+        pair_exchange(v, acc[8 * p2], acc[8 * p2 + 1], acc[8 * p2 + 2], acc[8 * p2 + 3], acc[8 * p2 + 4], acc[8 * p2 + 5],
+                      acc[8 * p2 + 6], acc[8 * p2 + 7], g);
+        if (n < F) store8_h<HT>(out + (size_t)n * ld + 32 * wave + 16 * p2 + 8 * g, v);
+      }
+    }
+  }
+}
+
 // fused form: DH = 128, 97..128 feature keys, K / V / dS / P~ within the 160 KB of LDS: S <= 192 for the one-wave-per-row-block
 // form; the key-split pipeline (KS) keeps 12 bytes of per-row scalars more and fits S <= 160
 static inline bool fused_fits(const TimDesc& d, bool ks) {
@@ -734,6 +1061,25 @@ int launch_bwd_fused(const TimDesc& d, const void* qkv, const void* o, const flo
   (void)hipFuncSetAttribute((const void*)attn_bwd_rows<HT, 128, 4, true, KS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   hipLaunchKernelGGL((attn_bwd_rows<HT, 128, 4, true, KS>), dim3(d.B * d.H), dim3(512), lds, s, (const HT*)qkv, (const HT*)o, lse,
                      (const HT*)d_o, (HT*)dqkv, (HT*)stamps, (HT*)nullptr, a);
+  return hipGetLastError() == hipSuccess ? TIMHIP_OK : TIMHIP_ELAUNCH;
+}
+
+// the co-resident form (TIMHIP_ATTN_BWD_CO=1) serves what the key-split form serves
+template <typename HT>
+int launch_bwd_co(const TimDesc& d, const void* qkv, const void* o, const float* lse, const void* d_o, void* dqkv, hipStream_t s,
+                  const unsigned long long* kbits) {
+  const AttnBwdCoPlan p = attn_bwd_co_plan(d.S, d.F, d.E / d.H);
+  AttnArgs a = make_attn_args(d);
+  if (kbits && a.thr != 0u) {
+    a.kbits = kbits;
+    (void)hipFuncSetAttribute((const void*)attn_bwd_co<HT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
+    hipLaunchKernelGGL((attn_bwd_co<HT, true>), dim3(d.B * d.H), dim3(256), p.lds_bytes, s, (const HT*)qkv, (const HT*)o, lse,
+                       (const HT*)d_o, (HT*)dqkv, a);
+    return hipGetLastError() == hipSuccess ? TIMHIP_OK : TIMHIP_ELAUNCH;
+  }
+  (void)hipFuncSetAttribute((const void*)attn_bwd_co<HT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
+  hipLaunchKernelGGL((attn_bwd_co<HT, false>), dim3(d.B * d.H), dim3(256), p.lds_bytes, s, (const HT*)qkv, (const HT*)o, lse,
+                     (const HT*)d_o, (HT*)dqkv, a);
   return hipGetLastError() == hipSuccess ? TIMHIP_OK : TIMHIP_ELAUNCH;
 }
 
@@ -770,6 +1116,8 @@ int tim_attention_bwd2_mfma(const TimDesc& d, const void* qkv, const void* o, co
   if (!h16_storage(d.precision) || (d.E % 8) != 0 || d.B * d.H > 65535) return TIMHIP_EUNSUPPORTED;
   const bool ks_ok = tim_knobs().attn_ks != 0 && fused_fits(d, true);
   if (ks_ok || fused_fits(d, false)) {   // (160 < S <= 192: the key-split form does not fit, the plain fused form still does)
+    if (ks_ok && tim_knobs().attn_bwd_co != 0 && attn_bwd_co_plan(d.S, d.F, d.E / d.H).fits && !((d.reserved >> 8) & 0xff))
+      DISPATCH_H16(d.precision, return (launch_bwd_co<HT>(d, qkv, o, lse, d_o, dqkv, s, kbits)));
     void* stamps = nullptr;   // (tuning builds, abl bit 16: per-block phase stamps into the caller's workspace, 64 B per block)
 #ifdef TIMHIP_TUNING
     if (((d.reserved >> 8) & 16) && ws && ws_bytes >= (size_t)d.B * d.H * 64) stamps = ws;

@@ -39,5 +39,6 @@ struct TimKnobs {
   int epi_pair = 1;       // TIMHIP_EPI_PAIR     dropout + residual NT epilogue: lane pairs share the Philox calls of their keep factors (default 1)
   int ln_pair = 1;        // TIMHIP_LN_PAIR      LayerNorm backward: lane pairs share the Philox calls of their dropout keep factors (default 1)
   int gemm_p8 = 1;        // TIMHIP_GEMM_P8      eight-phase 256 / 320 x 256 tiles for the multi-round NT shapes: 0 off, 1 by shape (default), 2 + the mulaux epilogue, 8 / 10 forced
+  int attn_bwd_co = 1;    // TIMHIP_ATTN_BWD_CO  0: the key-split fused attention backward as ONE 8-wave block per CU with a phase 2 at the end (default 1: two co-resident 4-wave blocks per CU, dK / dV accumulated per row sweep)
 };
 const TimKnobs& tim_knobs();

@@ -41,7 +41,9 @@ BUDGET = {
     # 128, F = 100; 229 at five key blocks) - scratch traffic would sit inside the loop over the heads
     "attn_maps.hip": [(r"attn_w_mfma", 0), (r"attn_w_generic", 0)],
     # the fp16 fused backward (C2a / C3 / C4), with the kernel's own draws and with the keep-bits of round 6
-    "attention_bwd2.hip": [(r"attn_bwd_rowsIDF16_Li128ELi4ELb1E", 0), (r"attn_bwd_rowsIDF16[_b]Li128ELi4ELb1ELb1ELb1E", 0)],
+    "attention_bwd2.hip": [(r"attn_bwd_rowsIDF16_Li128ELi4ELb1E", 0), (r"attn_bwd_rowsIDF16[_b]Li128ELi4ELb1ELb1ELb1E", 0),
+                           # the co-resident form: two waves per SIMD, 256 registers of which 128 are dK / dV accumulators
+                           (r"attn_bwd_coIDF16[_b]Lb[01]E", 0)],
     "rowops.hip": [(r"ln_fwd8", 0), (r"ln_bwd_kernel", 0)],
     "optim.hip": [(r"optim_norm_kernel", 0), (r"optim_update_kernel", 0)],   # streaming kernels: scratch traffic would share their HBM budget
     "mixup.hip": [(r"mixup_apply_kernel", 0)],   # streaming: two reads and one write per element, nothing else may touch memory
