@@ -27,6 +27,9 @@
  *     pointer registered by timhip_dropout_salt() (HIP-graph replay) and the measurement hooks
  *     timhip_gemm_timing_start/stop() (bench.py) - and timhip_softnms_1d(), which synchronises its
  *     stream once (it returns the number of kept segments to the host).
+ *   - State that a captured step must redraw lives in caller-owned 64-bit device counters which the drawing kernel itself
+ *     advances: the mixup set counter, the batch sampler's iteration counter and the DRLoc draw counter
+ *     (timhip_mixup_draw, timhip_sampler_draw, timhip_drloc_draw below).
  *   - All work is enqueued on the `stream` argument (a hipStream_t passed as void*).
  *   - Return value: 0 on success, a negative TIMHIP_E* code otherwise (timhip_strerror()).
  *     No exception crosses the ABI.
@@ -1002,6 +1005,81 @@ int timhip_window_times(const float* v_feat_times, int v_ld, const int64_t* v_ro
                         const int64_t* a_row0, const int32_t* feat_indices, int num_feats, const int32_t* windows, int B,
                         const float* v_queries, int max_v, const float* a_queries, int max_a, const float* start_sec,
                         float window_size, float* times, void* stream);
+
+/* ---------------------------------------------------------------- device-side batch sampler (additive to ABI 6) */
+/* Draw: the batch of ONE training iteration of a seeded, epoch-shuffled, rank-sharded order, nothing on the host taking part.
+ * counter: one 64-bit word in device memory, the number of the NEXT iteration; the kernel (one block) reads it (t), stores t + 1
+ * (one thread, after every thread has read it) and writes iteration t's batch, so the k-th draw is the same bits whether its
+ * launch is eager or the k-th replay of a captured graph.  Everything below is integer arithmetic on (seed, t, the arguments).
+ *   geometry    N = num_windows, W = world, r = rank, B.  per_rank = ceil(N / W) (torch's DistributedSampler with drop_last =
+ *               False); I = iterations per epoch = ceil(per_rank / B) with last = TIMHIP_SAMPLER_WRAP, floor(per_rank / B) with
+ *               TIMHIP_SAMPLER_DROP (I = 0: TIMHIP_EINVAL).  e = t / I, k = t % I.  Row b: p = k * B + b, valid[b] = p < per_rank,
+ *               g = (p % per_rank) * W + r, i = g % N, window[b] = shuffle ? perm(seed, e, i) : i.  The valid rows of an epoch
+ *               over all ranks are the epoch's permutation followed by its own head as padding, dealt round-robin - the lists
+ *               DistributedSampler builds (its own randperm stream is not reproduced); a short last batch becomes rows with
+ *               valid = 0, which still carry a real (wrapped) window number.
+ *   perm        a keyed bijection of [0, N) computed per element, no table: a balanced Feistel network with cycle walking.
+ *               bits = max(2, bit_length(N - 1)), h = (bits + 1) / 2, domain 2^(2h) in [N, 4N).  v = (L << h) | R; 6 rounds
+ *               (L, R) <- (R, L ^ (F & (2^h - 1))) with F = word x of philox4x32_7(key = seed, site = SITE_SAMPLER (9), counter
+ *               ((e mod 2^23) << 40) | (round << 32) | R); repeated while the value is >= N (a bijection of the domain returns
+ *               to [0, N): the walk needs no cap; the longest over all elements is 40 passes at N = 4097, 26 at N = 100000).
+ *               The order repeats after 2^23 epochs; the Python wrapper refuses to be set beyond.
+ *   aug         v_aug / a_aug int32 [B, num_feats] (NULL: modality absent), one index per (row, feature, modality) in
+ *               [0, num_aug): (uint64(word) * num_aug) >> 32 with element q = b * num_feats + j reading word q & 3 of the Philox
+ *               block with counter 2^63 | ((t mod 2^40) << 23) | (modality << 22) | (q >> 2), modality 0 visual, 1 audio (bit
+ *               63 keeps these blocks apart from the permutation's).  B * num_feats <= TIMHIP_SAMPLER_MAX_AUG, else TIMHIP_EINVAL.
+ *   outputs     window int32 [B], valid uint8 [B]; epoch, iteration: int64 words (NULL: not written) = e and k of the batch
+ *               just written.
+ * TIMHIP_EINVAL: counter / window / valid NULL, N < 1, W < 1, rank outside [0, W), B outside [1, 2^20], last not one of the two,
+ * an aug pointer with num_aug < 1 or num_feats < 1.  A refused call launches nothing: the counter keeps its value.  The dropout
+ * salt takes no part. */
+#define TIMHIP_SAMPLER_WRAP 0
+#define TIMHIP_SAMPLER_DROP 1
+#define TIMHIP_SAMPLER_MAX_AUG (1 << 24)
+int timhip_sampler_draw(uint64_t seed, uint64_t* counter, int num_windows, int world, int rank, int B, int shuffle, int last,
+                        int num_feats, int v_num_aug, int a_num_aug, int32_t* window, uint8_t* valid, int32_t* v_aug,
+                        int32_t* a_aug, int64_t* epoch, int64_t* iteration, void* stream);
+
+/* Batch assembly from DEVICE words, one launch: what timhip_window_gather (per modality), timhip_window_times and the label
+ * gathers of a batch produce, written to caller-owned outputs.  Tables as above (feats, feat_times with leading dimension ld >=
+ * 2, row0, feat_indices [W, num_feats], queries [W, max, 2], start_sec [W]) plus v_labels / a_labels int64 [W, max, 4] (verb,
+ * noun, action, class id; -1 padded) and v_ids / a_ids int64 [W, max] (-1 padded).  v_feats / a_feats NULL: that modality is
+ * absent (its feat_times must be NULL too) and its outputs are not touched.
+ *   window int32 [B], valid uint8 [B], v_aug / a_aug int32 [B, num_feats] (NULL: index 0): device words, read by the kernel.  A
+ *   window outside [0, num_windows) or an index outside [0, num_aug) is read as 0: nothing is read out of bounds.
+ *   visual [B, num_feats, Cv], audio [B, num_feats, Ca] fp32: the rows timhip_window_gather copies; 16-byte accesses for
+ *   a row whose source and destination are 16-byte aligned and whose width is a multiple of 4, element by element otherwise.
+ *   times [B, T, 2]: timhip_window_times to the bit (one IEEE subtraction, one IEEE division, max with 0).
+ *   verb, noun, action, v_action_ids int64 [B, max_v]; class_id, a_action_ids int64 [B, max_a]: the window's entries where
+ *   valid[b] != 0, -1 ("no query") in a row with valid[b] == 0; features and times of such a row are the wrapped window's.
+ * A flat work index over (section, row, item; a feature item is up to four 16-byte chunks), at most 2048 blocks of 256 threads.  TIMHIP_EINVAL on a null pointer that
+ * the shape needs, B / num_windows / num_feats < 1, window_size <= 0; TIMHIP_EALIGN on a float pointer off 4 bytes. */
+typedef struct TimWindowBatch {
+  const float* v_feats; const float* a_feats;
+  const float* v_feat_times; const float* a_feat_times;
+  const int64_t* v_row0; const int64_t* a_row0;
+  const int32_t* feat_indices;
+  const float* v_queries; const float* a_queries; const float* start_sec;
+  const int64_t* v_labels; const int64_t* a_labels; const int64_t* v_ids; const int64_t* a_ids;
+  const int32_t* window; const uint8_t* valid; const int32_t* v_aug; const int32_t* a_aug;
+  float* visual; float* audio; float* times;
+  int64_t* verb; int64_t* noun; int64_t* action; int64_t* class_id; int64_t* v_action_ids; int64_t* a_action_ids;
+  int32_t Cv, Ca, v_num_aug, a_num_aug, v_ld, a_ld, num_feats, max_v, max_a, B, num_windows;
+  float window_size;
+} TimWindowBatch;
+int timhip_window_batch(const TimWindowBatch* desc, void* stream);
+
+/* DRLoc sample positions (reference helpers/losses/drloc.py:4-7) from a device counter of their own: one block reads the counter
+ * (c), stores c + 1 and writes draw c.  pos_1, pos_2 int64 [n, m] in [0, l): (uint64(word) * l) >> 32, element i = row * m + col
+ * reading words (x, y) of the Philox block with key = seed, site = SITE_DRLOC (10), counter ((c mod 2^40) << 24) | (i >> 1) when
+ * i is even and words (z, w) when it is odd.  deltax fp32 [n, m] = float(|pos_1 - pos_2|) * (1.0f / float(l)): the conversion is
+ * exact, the reciprocal is one IEEE division and the product one IEEE multiplication - the bits torch gives on the device for
+ * abs((pos_1 - pos_2).float()) followed by `/= l` (a tensor divided by a host scalar is multiplied by the scalar's reciprocal
+ * there; for l = 6, 7, 50 some quotients differ from x / l in the last place).  1 <= l <= 2^24, n, m >= 1, n * m <= TIMHIP_DRLOC_MAX_SAMPLES and no null pointer, else
+ * TIMHIP_EINVAL (nothing launched, the counter keeps its value). */
+#define TIMHIP_DRLOC_MAX_SAMPLES (1 << 25)
+int timhip_drloc_draw(uint64_t seed, uint64_t* counter, int n, int m, int l, int64_t* pos_1, int64_t* pos_2, float* deltax,
+                      void* stream);
 
 /* ---------------------------------------------------------------- AVGA pooling of the AVE recipe (additive to ABI 6) */
 /* Audio-guided visual attention pooling (reference helpers/pool.py:6-43, models/tim.py:137-144): per pooled row r (one time step

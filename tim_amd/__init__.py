@@ -40,6 +40,12 @@ def __getattr__(name):  # lazy: importing the package must not require torch on 
     if name in ("Mixup", "mixup_data"):
         from . import mixup as _mixup
         return getattr(_mixup, name)
+    if name == "WindowSampler":
+        from .data import WindowSampler
+        return WindowSampler
+    if name == "DrlocPositions":
+        from .losses import DrlocPositions
+        return DrlocPositions
     if name in ("optim", "mixup"):
         import importlib
         return importlib.import_module("." + name, __name__)

@@ -22,6 +22,9 @@ H16 = (PREC_BF16, PREC_F16)   # 16-bit operand storage (the MFMA GEMM / attentio
 SITE_FEAT_V, SITE_FEAT_A, SITE_SEQ = 1, 2, 3
 SITE_MIXUP = 8   # mixup.hip: lam and the permutation (its own device counter, no dropout salt)
 MIXUP_ALPHA_MIN, MIXUP_ALPHA_MAX, MIXUP_MAX_TENSORS = 0.05, 16.0, 4   # include/timhip.h: TIMHIP_MIXUP_*
+SITE_SAMPLER, SITE_DRLOC = 9, 10   # sampler.hip: the batch order with its augmentation indices, the DRLoc positions (as SITE_MIXUP)
+SAMPLER_WRAP, SAMPLER_DROP, SAMPLER_MAX_AUG, DRLOC_MAX_SAMPLES = 0, 1, 1 << 24, 1 << 25   # include/timhip.h: TIMHIP_SAMPLER_*, TIMHIP_DRLOC_*
+SAMPLER_EPOCH_BITS = 23            # the epoch enters the permutation's Philox counter modulo 2^23
 SITE_L_ATTN, SITE_L_DROP1, SITE_L_FFN, SITE_L_DROP2 = 0, 1, 2, 3
 
 
@@ -108,6 +111,15 @@ class TimAvga(C.Structure):
 
 class TimAvgaGrads(C.Structure):
     _fields_ = [(n, vp) for n in ("w_video", "b_video", "w_audio", "b_audio", "w_v", "w_g", "w_h")]
+
+
+class TimWindowBatch(C.Structure):
+    """one timhip_window_batch call (include/timhip.h): the dataset's tables, the sampler's device words, the outputs, the shape"""
+    _fields_ = [(n, vp) for n in ("v_feats", "a_feats", "v_feat_times", "a_feat_times", "v_row0", "a_row0", "feat_indices", "v_queries",
+                                  "a_queries", "start_sec", "v_labels", "a_labels", "v_ids", "a_ids", "window", "valid", "v_aug", "a_aug",
+                                  "visual", "audio", "times", "verb", "noun", "action", "class_id", "v_action_ids", "a_action_ids")] + \
+               [(n, i32) for n in ("Cv", "Ca", "v_num_aug", "a_num_aug", "v_ld", "a_ld", "num_feats", "max_v", "max_a", "B",
+                                   "num_windows")] + [("window_size", f32)]
 
 
 _SIGS = {
@@ -203,6 +215,9 @@ _SIGS = {
     "timhip_rec_counts": (C.c_int, [vp, vp, vp, i32, vp, vp]),
     "timhip_window_gather": (C.c_int, [vp, i32, i32, vp, vp, i32, vp, i32, vp, vp, vp]),
     "timhip_window_times": (C.c_int, [vp, i32, vp, vp, i32, vp, vp, i32, vp, i32, vp, i32, vp, i32, vp, f32, vp, vp]),
+    "timhip_sampler_draw": (C.c_int, [u64, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "timhip_window_batch": (C.c_int, [C.POINTER(TimWindowBatch), vp]),
+    "timhip_drloc_draw": (C.c_int, [u64, vp, i32, i32, i32, vp, vp, vp, vp]),
     "timhip_gemm_timing_start": (C.c_int, [i32, C.c_double]),
     "timhip_gemm_timing_stop": (C.c_int, [vp, vp, vp]),
     "timhip_timing_stop_families": (C.c_int, [vp, vp, vp]),

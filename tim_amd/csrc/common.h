@@ -239,6 +239,7 @@ struct PerDeviceOnce {
 enum {
   SITE_FEAT_V = 1, SITE_FEAT_A = 2, SITE_SEQ = 3,
   SITE_MIXUP = 8,   // mixup.hip: lam and the permutation (not a dropout site: no salt, its own device counter)
+  SITE_SAMPLER = 9, SITE_DRLOC = 10,   // sampler.hip: the batch order with its augmentation indices, the DRLoc positions (as SITE_MIXUP)
   SITE_L_BASE = 16, SITE_L_ATTN = 0, SITE_L_DROP1 = 1, SITE_L_FFN = 2, SITE_L_DROP2 = 3, SITE_L_STRIDE = 8
 };
 static inline uint32_t layer_site(int layer, int which) {

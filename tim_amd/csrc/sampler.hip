@@ -1,0 +1,314 @@
+// Device-side batch sampler (include/timhip.h has the contract): what a captured training iteration needs from the data side
+// without the host taking part
+//   * sampler_draw_kernel: iteration t of a seeded, epoch-shuffled, rank-sharded order - window numbers, valid flags and the
+//     augmentation indices of a batch, from philox4x32_7 keyed by the seed and numbered by a device counter the kernel advances
+//   * window_batch_kernel: the batch of data.py's DeviceWindowDataset.batch() from those device words into caller-owned outputs,
+//     one byte-bound launch (the eager form: two gathers, the times kernel and four torch index ops)
+//   * drloc_draw_kernel: the DRLoc sample positions and their normalised distance, a device counter of its own
+#include "common.h"
+
+namespace {
+
+constexpr int SMP_ROUNDS = 6;                        // Feistel rounds of the permutation
+constexpr uint64_t SMP_EPOCH_MASK = (1ull << 23) - 1;  // the epoch enters the Philox counter modulo 2^23
+constexpr uint64_t SMP_AUG_FLAG = 1ull << 63;        // counter bit 63: an augmentation word
+constexpr int DRLOC_DRAW_BITS = 24;                  // Philox counter = (draw number << 24) | block
+
+struct SamplerGeom {
+  unsigned long long iters;   // iterations per epoch
+  unsigned int N, world, rank, B, per_rank, h;   // h: half the bits of the Feistel domain
+  int shuffle, nf, v_num_aug, a_num_aug;
+};
+
+// the keyed bijection of [0, N) at epoch bits `ebits`: a balanced Feistel network over 2h bits, walked until the value is back
+// inside [0, N) (a bijection of the domain returns there: no cap)
+__device__ uint32_t smp_perm(uint64_t seed, uint64_t ebits, uint32_t v, uint32_t N, uint32_t h) {
+  const uint32_t mask = (1u << h) - 1u;
+  do {
+    uint32_t L = v >> h, R = v & mask;
+#pragma unroll 1
+    for (int rnd = 0; rnd < SMP_ROUNDS; ++rnd) {
+      const uint32_t f = philox4x32_7(seed, SITE_SAMPLER, ebits | ((uint64_t)rnd << 32) | (uint64_t)R).x & mask;
+      const uint32_t nr = L ^ f;
+      L = R;
+      R = nr;
+    }
+    v = (L << h) | R;
+  } while (v >= N);
+  return v;
+}
+
+__device__ __forceinline__ void smp_aug(uint64_t seed, uint64_t base, int count, uint32_t num_aug, int* __restrict__ out) {
+  for (int blk = threadIdx.x; blk < ((count + 3) >> 2); blk += blockDim.x) {
+    const Philox4 r = philox4x32_7(seed, SITE_SAMPLER, base | (uint64_t)blk);
+    const int i = blk * 4;
+    out[i] = (int)mulhi32(r.x, num_aug);
+    if (i + 1 < count) out[i + 1] = (int)mulhi32(r.y, num_aug);
+    if (i + 2 < count) out[i + 2] = (int)mulhi32(r.z, num_aug);
+    if (i + 3 < count) out[i + 3] = (int)mulhi32(r.w, num_aug);
+  }
+}
+
+// ONE block: every thread reads the counter, the barrier, then thread 0 stores its new value
+__global__ __launch_bounds__(256) void sampler_draw_kernel(uint64_t seed, unsigned long long* __restrict__ counter, const SamplerGeom g,
+                                                           int* __restrict__ window, unsigned char* __restrict__ valid,
+                                                           int* __restrict__ v_aug, int* __restrict__ a_aug,
+                                                           long long* __restrict__ epoch, long long* __restrict__ iteration) {
+  const unsigned long long t = *counter;
+  __syncthreads();
+  const unsigned long long e = t / g.iters, k = t - e * g.iters;
+  if (threadIdx.x == 0) {
+    *counter = t + 1ull;
+    if (epoch) *epoch = (long long)e;
+    if (iteration) *iteration = (long long)k;
+  }
+  const uint64_t ebits = ((uint64_t)e & SMP_EPOCH_MASK) << 40;
+  for (unsigned int b = threadIdx.x; b < g.B; b += blockDim.x) {
+    const unsigned long long p = k * g.B + b;
+    const unsigned long long gi = (p % g.per_rank) * g.world + g.rank;
+    const uint32_t i = (uint32_t)(gi % g.N);
+    window[b] = (int)(g.shuffle ? smp_perm(seed, ebits, i, g.N, g.h) : i);
+    valid[b] = p < g.per_rank ? 1 : 0;
+  }
+  const uint64_t abase = SMP_AUG_FLAG | (((uint64_t)t << 23) & (SMP_AUG_FLAG - 1ull));
+  const int count = (int)g.B * g.nf;
+  if (v_aug) smp_aug(seed, abase, count, (uint32_t)g.v_num_aug, v_aug);
+  if (a_aug) smp_aug(seed, abase | (1ull << 22), count, (uint32_t)g.a_num_aug, a_aug);
+}
+
+// ---- batch assembly ---------------------------------------------------------------------------------------------------
+enum { WB_VISUAL = 0, WB_AUDIO, WB_TIMES, WB_VLABELS, WB_ALABELS, WB_SECTIONS };
+
+struct WbArgs {
+  TimWindowBatch d;
+  long long first[WB_SECTIONS + 1];   // flat work index of a section's first item; first[WB_SECTIONS] = all of them
+  int groups_v, groups_a, T;          // items of a feature row (64 per WB_SPAN chunks, the last span possibly short); time rows of a window
+};
+
+__device__ __forceinline__ void wb_divmod(long long r, int d, long long& q, int& rem) {
+  if (((unsigned long long)r >> 32) == 0) {   // (a 32-bit divide wherever it is enough: every product shape)
+    const uint32_t qq = (uint32_t)r / (uint32_t)d;
+    q = (long long)qq;
+    rem = (int)((uint32_t)r - qq * (uint32_t)d);
+  } else {
+    q = r / d;
+    rem = (int)(r - q * d);
+  }
+}
+
+// the window of batch row b (a word outside the table reads window 0: nothing is read out of bounds)
+__device__ __forceinline__ int wb_window(const TimWindowBatch& d, long long b) {
+  const int w = d.window[b];
+  return (unsigned)w < (unsigned)d.num_windows ? w : 0;
+}
+
+// One item = up to four 16-byte chunks of one gathered row: the lanes of a wave take 64 consecutive chunks, four times, so the
+// index chain (window -> row0, feat_indices, aug) is walked once per four loads and the four loads are in flight together
+constexpr int WB_UNROLL = 4, WB_SPAN = 64 * WB_UNROLL;   // chunks a wave covers (the four loads are written out below)
+
+__device__ __forceinline__ void wb_feature_item(const TimWindowBatch& d, const float* __restrict__ feats, const long long* __restrict__ row0,
+                                                const int* __restrict__ aug, int num_aug, int C, float* __restrict__ out, long long row,
+                                                int group) {
+  long long b;
+  int j;
+  wb_divmod(row, d.num_feats, b, j);
+  const int w = wb_window(d, b);
+  int a = aug ? aug[row] : 0;
+  a = (unsigned)a < (unsigned)num_aug ? a : 0;
+  const long long srow = (row0[w] + d.feat_indices[(size_t)w * d.num_feats + j]) * num_aug + a;
+  const float* x = feats + (size_t)srow * C;
+  float* o = out + (size_t)row * C;
+  const int chunks = (C + 3) >> 2, c0 = (group >> 6) * WB_SPAN + (group & 63);
+  if ((C & 3) == 0 && ((((uintptr_t)x) | ((uintptr_t)o)) & 15) == 0) {
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    const f32x4* xv = reinterpret_cast<const f32x4*>(x) + c0;
+    f32x4* ov = reinterpret_cast<f32x4*>(o) + c0;
+    const bool p0 = c0 < chunks, p1 = c0 + 64 < chunks, p2 = c0 + 128 < chunks, p3 = c0 + 192 < chunks;
+    f32x4 v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f;
+    if (p0) v0 = xv[0];
+    if (p1) v1 = xv[64];
+    if (p2) v2 = xv[128];
+    if (p3) v3 = xv[192];
+    if (p0) ov[0] = v0;
+    if (p1) ov[64] = v1;
+    if (p2) ov[128] = v2;
+    if (p3) ov[192] = v3;
+  } else {   // a width that is no multiple of 4, or a row off 16-byte alignment
+    for (int k = 0; k < WB_UNROLL; ++k) {
+      const int e0 = 4 * (c0 + 64 * k);
+      for (int e = e0; e < e0 + 4 && e < C; ++e) o[e] = x[e];
+    }
+  }
+}
+
+// flat work index over (section, row, item), grid-stride (a row's items are a multiple of 64 and the feature sections come
+// first: a wave never straddles two rows)
+__global__ __launch_bounds__(256) void window_batch_kernel(const WbArgs a) {
+  const TimWindowBatch& d = a.d;
+  const long long total = a.first[WB_SECTIONS], stride = (long long)gridDim.x * blockDim.x;
+  for (long long wi = (long long)blockIdx.x * blockDim.x + threadIdx.x; wi < total; wi += stride) {
+    if (wi < a.first[WB_AUDIO]) {
+      long long row;
+      int chunk;
+      wb_divmod(wi, a.groups_v, row, chunk);
+      wb_feature_item(d, d.v_feats, (const long long*)d.v_row0, d.v_aug, d.v_num_aug, d.Cv, d.visual, row, chunk);
+    } else if (wi < a.first[WB_TIMES]) {
+      long long row;
+      int chunk;
+      wb_divmod(wi - a.first[WB_AUDIO], a.groups_a, row, chunk);
+      wb_feature_item(d, d.a_feats, (const long long*)d.a_row0, d.a_aug, d.a_num_aug, d.Ca, d.audio, row, chunk);
+    } else if (wi < a.first[WB_VLABELS]) {   // window_times_kernel (batch.hip), one (start, end) row per item
+      long long b;
+      int t;
+      wb_divmod(wi - a.first[WB_TIMES], a.T, b, t);
+      const int w = wb_window(d, b), nf = d.num_feats;
+      const int nfv = d.v_feat_times ? nf : 0, nfa = d.a_feat_times ? nf : 0;
+      const float st = d.start_sec[w];
+      const float* p;
+      if (t < nfv) p = d.v_feat_times + (size_t)(((const long long*)d.v_row0)[w] + d.feat_indices[(size_t)w * nf + t]) * d.v_ld;
+      else if (t < nfv + nfa) p = d.a_feat_times + (size_t)(((const long long*)d.a_row0)[w] + d.feat_indices[(size_t)w * nf + (t - nfv)]) * d.a_ld;
+      else if (t < nfv + nfa + d.max_v) p = d.v_queries + ((size_t)w * d.max_v + (t - nfv - nfa)) * 2;
+      else p = d.a_queries + ((size_t)w * d.max_a + (t - nfv - nfa - d.max_v)) * 2;
+      const float s = p[0], e = p[1];
+      float* o = d.times + ((size_t)b * a.T + t) * 2;
+      o[0] = fmaxf((s - st) / d.window_size, 0.f);
+      o[1] = fmaxf((e - st) / d.window_size, 0.f);
+    } else if (wi < a.first[WB_ALABELS]) {
+      long long b;
+      int q;
+      wb_divmod(wi - a.first[WB_VLABELS], d.max_v, b, q);
+      const int w = wb_window(d, b);
+      const bool ok = d.valid[b] != 0;
+      const size_t src = (size_t)w * d.max_v + q, dst = (size_t)b * d.max_v + q;
+      const long long* lab = (const long long*)d.v_labels + src * 4;
+      ((long long*)d.verb)[dst] = ok ? lab[0] : -1ll;
+      ((long long*)d.noun)[dst] = ok ? lab[1] : -1ll;
+      ((long long*)d.action)[dst] = ok ? lab[2] : -1ll;
+      ((long long*)d.v_action_ids)[dst] = ok ? ((const long long*)d.v_ids)[src] : -1ll;
+    } else {
+      long long b;
+      int q;
+      wb_divmod(wi - a.first[WB_ALABELS], d.max_a, b, q);
+      const int w = wb_window(d, b);
+      const bool ok = d.valid[b] != 0;
+      const size_t src = (size_t)w * d.max_a + q, dst = (size_t)b * d.max_a + q;
+      ((long long*)d.class_id)[dst] = ok ? ((const long long*)d.a_labels)[src * 4 + 3] : -1ll;
+      ((long long*)d.a_action_ids)[dst] = ok ? ((const long long*)d.a_ids)[src] : -1ll;
+    }
+  }
+}
+
+// ---- DRLoc positions --------------------------------------------------------------------------------------------------
+// ONE block, the counter as in sampler_draw_kernel; a Philox block serves two elements: words (x, y) and (z, w)
+__global__ __launch_bounds__(256) void drloc_draw_kernel(uint64_t seed, unsigned long long* __restrict__ counter, int count, uint32_t l,
+                                                         long long* __restrict__ pos_1, long long* __restrict__ pos_2,
+                                                         float* __restrict__ deltax) {
+  const unsigned long long c = *counter;
+  __syncthreads();
+  if (threadIdx.x == 0) *counter = c + 1ull;
+  const uint64_t base = (uint64_t)c << DRLOC_DRAW_BITS;
+  // |pos_1 - pos_2| times the rounded reciprocal of l: what torch's `deltax /= l` computes on the device (a tensor divided by a
+  // host scalar is multiplied by 1 / scalar there), so the loss of losses._drloc keeps its bits
+  const float inv = __fdiv_rn(1.0f, (float)l);
+  for (int blk = threadIdx.x; blk < ((count + 1) >> 1); blk += blockDim.x) {
+    const Philox4 r = philox4x32_7(seed, SITE_DRLOC, base | (uint64_t)blk);
+    const int i = blk * 2;
+    const uint32_t a0 = mulhi32(r.x, l), b0 = mulhi32(r.y, l);
+    pos_1[i] = (long long)a0;
+    pos_2[i] = (long long)b0;
+    deltax[i] = __fmul_rn((float)(a0 > b0 ? a0 - b0 : b0 - a0), inv);   // (exact conversion: l <= 2^24)
+    if (i + 1 < count) {
+      const uint32_t a1 = mulhi32(r.z, l), b1 = mulhi32(r.w, l);
+      pos_1[i + 1] = (long long)a1;
+      pos_2[i + 1] = (long long)b1;
+      deltax[i + 1] = __fmul_rn((float)(a1 > b1 ? a1 - b1 : b1 - a1), inv);
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int timhip_sampler_draw(uint64_t seed, uint64_t* counter, int num_windows, int world, int rank, int B, int shuffle, int last,
+                        int num_feats, int v_num_aug, int a_num_aug, int32_t* window, uint8_t* valid, int32_t* v_aug,
+                        int32_t* a_aug, int64_t* epoch, int64_t* iteration, void* stream) {
+  if (!counter || !window || !valid || num_windows < 1 || world < 1 || rank < 0 || rank >= world || B < 1 || B > (1 << 20))
+    return TIMHIP_EINVAL;
+  if (last != TIMHIP_SAMPLER_WRAP && last != TIMHIP_SAMPLER_DROP) return TIMHIP_EINVAL;
+  if ((v_aug && v_num_aug < 1) || (a_aug && a_num_aug < 1)) return TIMHIP_EINVAL;
+  if ((v_aug || a_aug) && (num_feats < 1 || (long long)B * num_feats > TIMHIP_SAMPLER_MAX_AUG)) return TIMHIP_EINVAL;
+  SamplerGeom g;
+  g.N = (unsigned)num_windows;
+  g.world = (unsigned)world;
+  g.rank = (unsigned)rank;
+  g.B = (unsigned)B;
+  g.per_rank = (unsigned)(((long long)num_windows + world - 1) / world);
+  g.iters = last == TIMHIP_SAMPLER_WRAP ? (g.per_rank + g.B - 1) / g.B : g.per_rank / g.B;
+  if (g.iters < 1) return TIMHIP_EINVAL;   // "drop" with fewer windows per rank than one batch
+  unsigned bits = 0;
+  while (bits < 32 && ((unsigned long long)(g.N - 1) >> bits) != 0) ++bits;   // bit_length(N - 1)
+  if (bits < 2) bits = 2;
+  g.h = (bits + 1) / 2;
+  g.shuffle = shuffle ? 1 : 0;
+  g.nf = (v_aug || a_aug) ? num_feats : 0;
+  g.v_num_aug = v_num_aug;
+  g.a_num_aug = a_num_aug;
+  hipLaunchKernelGGL(sampler_draw_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, seed, (unsigned long long*)counter, g,
+                     (int*)window, (unsigned char*)valid, (int*)v_aug, (int*)a_aug, (long long*)epoch, (long long*)iteration);
+  TIM_CHECK_LAUNCH();
+  return TIMHIP_OK;
+}
+
+int timhip_window_batch(const TimWindowBatch* desc, void* stream) {
+  if (!desc) return TIMHIP_EINVAL;
+  WbArgs a;
+  a.d = *desc;
+  const TimWindowBatch& d = a.d;
+  if (d.B < 1 || d.num_windows < 1 || d.num_feats < 1 || d.max_v < 0 || d.max_a < 0 || !(d.window_size > 0.f)) return TIMHIP_EINVAL;
+  if (!d.window || !d.valid || !d.feat_indices || !d.start_sec || !d.times) return TIMHIP_EINVAL;
+  const bool has_v = d.v_feats != nullptr, has_a = d.a_feats != nullptr;
+  if (has_v && (!d.v_row0 || !d.v_feat_times || !d.visual || d.Cv < 1 || d.v_num_aug < 1 || d.v_ld < 2)) return TIMHIP_EINVAL;
+  if (has_a && (!d.a_row0 || !d.a_feat_times || !d.audio || d.Ca < 1 || d.a_num_aug < 1 || d.a_ld < 2)) return TIMHIP_EINVAL;
+  if ((!has_v && d.v_feat_times) || (!has_a && d.a_feat_times)) return TIMHIP_EINVAL;
+  if (d.max_v > 0 && (!d.v_queries || !d.v_labels || !d.v_ids || !d.verb || !d.noun || !d.action || !d.v_action_ids)) return TIMHIP_EINVAL;
+  if (d.max_a > 0 && (!d.a_queries || !d.a_labels || !d.a_ids || !d.class_id || !d.a_action_ids)) return TIMHIP_EINVAL;
+  if ((((uintptr_t)d.visual) | ((uintptr_t)d.audio) | ((uintptr_t)d.times) | ((uintptr_t)d.v_feats) | ((uintptr_t)d.a_feats)) & 3) return TIMHIP_EALIGN;
+  a.groups_v = has_v ? ((d.Cv + 3) / 4 + 255) / 256 * 64 : 64;   // (wb_feature_item: 256 chunks per wave)
+  a.groups_a = has_a ? ((d.Ca + 3) / 4 + 255) / 256 * 64 : 64;
+  a.T = (has_v ? d.num_feats : 0) + (has_a ? d.num_feats : 0) + d.max_v + d.max_a;
+  const long long rows = (long long)d.B * d.num_feats;
+  if (rows > (1ll << 40) / (a.groups_v > a.groups_a ? a.groups_v : a.groups_a)) return TIMHIP_EUNSUPPORTED;   // (the flat index stays far inside 63 bits)
+  long long total = 0;
+  a.first[WB_VISUAL] = total;
+  total += has_v ? rows * a.groups_v : 0;
+  a.first[WB_AUDIO] = total;
+  total += has_a ? rows * a.groups_a : 0;
+  a.first[WB_TIMES] = total;
+  total += (long long)d.B * a.T;
+  a.first[WB_VLABELS] = total;
+  total += (long long)d.B * d.max_v;
+  a.first[WB_ALABELS] = total;
+  total += (long long)d.B * d.max_a;
+  a.first[WB_SECTIONS] = total;
+  if (a.T < 1) a.T = 1;
+  if (total == 0) return TIMHIP_OK;
+  // byte-bound: 256 CUs x 8 blocks of 256 threads and a grid-stride loop over the rest
+  const long long want = (total + 255) / 256;
+  const int blocks = (int)(want > 2048 ? 2048 : want);
+  hipLaunchKernelGGL(window_batch_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
+  TIM_CHECK_LAUNCH();
+  return TIMHIP_OK;
+}
+
+int timhip_drloc_draw(uint64_t seed, uint64_t* counter, int n, int m, int l, int64_t* pos_1, int64_t* pos_2, float* deltax,
+                      void* stream) {
+  if (!counter || !pos_1 || !pos_2 || !deltax || n < 1 || m < 1 || l < 1 || l > (1 << 24)) return TIMHIP_EINVAL;
+  if ((long long)n * m > TIMHIP_DRLOC_MAX_SAMPLES) return TIMHIP_EINVAL;
+  hipLaunchKernelGGL(drloc_draw_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, seed, (unsigned long long*)counter, n * m,
+                     (uint32_t)l, (long long*)pos_1, (long long*)pos_2, deltax);
+  TIM_CHECK_LAUNCH();
+  return TIMHIP_OK;
+}
+
+}  // extern "C"

@@ -8,7 +8,13 @@ gather + host-to-device copy per GPU.  `DeviceWindowDataset` holds the same tabl
 the MI355X's 288 GB many times over) and produces whole batches with two HIP kernels (`timhip_window_gather`,
 `timhip_window_times`): `batch(indices)` returns what `default_collate([dataset[i] for i in indices])` returns in the
 reference, already on the device.  No CPU path: the kernels run or the call raises.
+
+`batch()` takes host indices and allocates its outputs, so it cannot sit inside a captured step.  `ds.sampler(batch_size, ...)`
+returns a `WindowSampler` whose order lives on the device: `next_batch()` is two launches (`timhip_sampler_draw`,
+`timhip_window_batch`) into tensors of fixed address, eager or replayed with the same bits.
 """
+import ctypes as C
+
 import torch
 
 from . import _lib as L
@@ -128,3 +134,144 @@ class DeviceWindowDataset:
             "num_v_queries": torch.full((B,), mv, dtype=torch.int64), "num_a_queries": torch.full((B,), ma, dtype=torch.int64),
         }
         return v_data, a_data, times, label, metadata
+
+    def narration_ids(self, windows):
+        """The narration-id strings (host data) of a list or CPU tensor of window numbers, in `batch()`'s transposed layout:
+        {"v_narration_ids": one list (of len(windows) strings) per query slot, "a_narration_ids": likewise}."""
+        idx = [int(i) for i in torch.as_tensor(windows).reshape(-1).tolist()]
+        for i in idx:
+            if not 0 <= i < self.num_windows:
+                raise ValueError("window %d outside [0, %d)" % (i, self.num_windows))
+        return {"v_narration_ids": [[self.v_narration_ids[i][q] for i in idx] for q in range(self.max_visual_actions)],
+                "a_narration_ids": [[self.a_narration_ids[i][q] for i in idx] for q in range(self.max_audio_actions)]}
+
+    def sampler(self, batch_size, seed=0, shuffle=True, rank=0, world=1, last="wrap"):
+        """A `WindowSampler` over this dataset: batches drawn and assembled on the device, capturable."""
+        return WindowSampler(self, batch_size, seed=seed, shuffle=shuffle, rank=rank, world=world, last=last)
+
+
+class WindowSampler:
+    """The batches of a seeded, epoch-shuffled, rank-sharded order over a `DeviceWindowDataset`, with all state on the device.
+
+        smp = ds.sampler(batch_size, seed=0, shuffle=True, rank=rank, world=world)
+        def step():                                   # eager, or the `fn` of a GraphedStep: the same sequence of batches
+            visual, audio, times, label, metadata = smp.next_batch()       # two launches, no host input
+            ...
+
+    `next_batch()` returns what `ds.batch(indices)` returns (shapes, dtypes, dict keys; narration-id strings aside - they are
+    host data, `ds.narration_ids(metadata["window"].cpu())` looks them up), in tensors the sampler owns: the SAME objects on
+    every call, refilled by `timhip_sampler_draw` + `timhip_window_batch`.  The k-th call of a seed (counted by a 64-bit word
+    in device memory that the draw kernel advances) returns iteration k: epoch k // iterations_per_epoch of an order that is
+    `DistributedSampler`'s in structure - the epoch's permutation, padded with its own head to a multiple of `world`, dealt
+    round-robin to the ranks - with its own keyed permutation (include/timhip.h), not torch's randperm stream.  With
+    `last="wrap"` a short last batch keeps its full shape: the rows beyond the rank's share have `metadata["valid"] == 0`, the
+    features and times of a real window and -1 ("no query") in every label and id; `last="drop"` drops that batch.
+
+    No CPU path: the kernels run or the call raises."""
+
+    def __init__(self, dataset, batch_size, seed=0, shuffle=True, rank=0, world=1, last="wrap"):
+        ds = self.dataset = dataset
+        B, world, rank = int(batch_size), int(world), int(rank)
+        if B < 1 or B > (1 << 20):
+            raise ValueError("batch_size must lie in [1, 2^20], got %d" % B)
+        if world < 1 or not 0 <= rank < world:
+            raise ValueError("rank %d outside [0, world = %d)" % (rank, world))
+        if last not in ("wrap", "drop"):
+            raise ValueError('last must be "wrap" or "drop", got %r' % (last,))
+        if ds.num_windows < 1:
+            raise ValueError("the dataset has no windows")
+        if B * ds.num_feats > L.SAMPLER_MAX_AUG:
+            raise ValueError("batch_size * num_feats = %d: the augmentation draw addresses at most %d indices per modality"
+                             % (B * ds.num_feats, L.SAMPLER_MAX_AUG))
+        self.batch_size, self.seed, self.shuffle = B, int(seed) & (2 ** 64 - 1), bool(shuffle)
+        self.rank, self.world, self.last = rank, world, last
+        self.per_rank = -(-ds.num_windows // world)
+        self.iterations_per_epoch = -(-self.per_rank // B) if last == "wrap" else self.per_rank // B
+        if self.iterations_per_epoch < 1:
+            raise ValueError('last="drop": %d windows per rank do not fill one batch of %d' % (self.per_rank, B))
+        dev, nf, mv, ma = ds.device, ds.num_feats, ds.max_visual_actions, ds.max_audio_actions
+        self.device = dev
+        self.counter = torch.zeros(1, dtype=torch.int64, device=dev)       # the number of the NEXT iteration
+        self.epoch = torch.zeros(1, dtype=torch.int64, device=dev)         # of the batch drawn last
+        self.iteration = torch.zeros(1, dtype=torch.int64, device=dev)     # its number inside that epoch
+        self.window = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.valid = torch.zeros(B, dtype=torch.uint8, device=dev)
+        self.v_aug = torch.zeros((B, nf), dtype=torch.int32, device=dev) if ds.has_v else None
+        self.a_aug = torch.zeros((B, nf), dtype=torch.int32, device=dev) if ds.has_a else None
+        f32 = lambda *s: torch.zeros(s, dtype=torch.float32, device=dev)   # noqa: E731
+        i64 = lambda *s: torch.full(s, -1, dtype=torch.int64, device=dev)   # noqa: E731
+        self.visual = f32(B, nf, ds.v["C"]) if ds.has_v else torch.empty((B, 0), device=dev)
+        self.audio = f32(B, nf, ds.a["C"]) if ds.has_a else torch.empty((B, 0), device=dev)
+        T = (nf if ds.has_v else 0) + (nf if ds.has_a else 0) + mv + ma
+        self.times = f32(B, T, 2)
+        self.label = {"verb": i64(B, mv), "noun": i64(B, mv), "action": i64(B, mv), "class_id": i64(B, ma)}
+        self.metadata = {"v_action_ids": i64(B, mv), "a_action_ids": i64(B, ma),
+                         "num_v_queries": torch.full((B,), mv, dtype=torch.int64), "num_a_queries": torch.full((B,), ma, dtype=torch.int64),
+                         "window": self.window, "valid": self.valid}
+        self._desc = None
+
+    def _descriptor(self):
+        ds, lb, md = self.dataset, self.label, self.metadata
+        d = L.TimWindowBatch()
+        if ds.has_v:
+            d.v_feats, d.v_feat_times, d.v_row0, d.v_aug, d.visual = ptr(ds.v["feats"]), ptr(ds.v["times"]), ptr(ds.v_row0), ptr(self.v_aug), ptr(self.visual)
+            d.Cv, d.v_num_aug, d.v_ld = ds.v["C"], ds.v["num_aug"], 2
+        if ds.has_a:
+            d.a_feats, d.a_feat_times, d.a_row0, d.a_aug, d.audio = ptr(ds.a["feats"]), ptr(ds.a["times"]), ptr(ds.a_row0), ptr(self.a_aug), ptr(self.audio)
+            d.Ca, d.a_num_aug, d.a_ld = ds.a["C"], ds.a["num_aug"], 2
+        d.feat_indices, d.start_sec, d.window, d.valid, d.times = ptr(ds.feat_indices), ptr(ds.start_sec), ptr(self.window), ptr(self.valid), ptr(self.times)
+        if ds.max_visual_actions:
+            d.v_queries, d.v_labels, d.v_ids = ptr(ds.v_queries), ptr(ds.v_labels), ptr(ds.v_action_ids)
+            d.verb, d.noun, d.action, d.v_action_ids = ptr(lb["verb"]), ptr(lb["noun"]), ptr(lb["action"]), ptr(md["v_action_ids"])
+        if ds.max_audio_actions:
+            d.a_queries, d.a_labels, d.a_ids = ptr(ds.a_queries), ptr(ds.a_labels), ptr(ds.a_action_ids)
+            d.class_id, d.a_action_ids = ptr(lb["class_id"]), ptr(md["a_action_ids"])
+        d.num_feats, d.max_v, d.max_a, d.B, d.num_windows = ds.num_feats, ds.max_visual_actions, ds.max_audio_actions, self.batch_size, ds.num_windows
+        d.window_size = ds.window_size
+        return d
+
+    def next_batch(self):
+        """Two launches on the current stream: the draw of the next iteration and the assembly of its batch into the sampler's
+        own tensors -> (visual, audio, times, label, metadata), the same objects every time.  Capturable; never synchronises."""
+        ds = self.dataset
+        if self._desc is None:
+            self._desc = self._descriptor()
+        with torch.cuda.device(self.device):
+            st = _stream()
+            call("timhip_sampler_draw", self.seed, ptr(self.counter), ds.num_windows, self.world, self.rank, self.batch_size,
+                 int(self.shuffle), L.SAMPLER_WRAP if self.last == "wrap" else L.SAMPLER_DROP, ds.num_feats,
+                 ds.v["num_aug"] if ds.has_v else 0, ds.a["num_aug"] if ds.has_a else 0, ptr(self.window), ptr(self.valid),
+                 ptr(self.v_aug), ptr(self.a_aug), ptr(self.epoch), ptr(self.iteration), st)
+            call("timhip_window_batch", C.byref(self._desc), st)
+        return self.visual, self.audio, self.times, self.label, self.metadata
+
+    # ---- position ---------------------------------------------------------------------------------------------------
+    def _check_iteration(self, k):
+        k = int(k)
+        if k < 0 or k // self.iterations_per_epoch >= (1 << L.SAMPLER_EPOCH_BITS):
+            raise ValueError("iteration %d: the order is defined for epochs [0, 2^%d) of %d iterations"
+                             % (k, L.SAMPLER_EPOCH_BITS, self.iterations_per_epoch))
+        return k
+
+    def set_iteration(self, k):
+        """The next `next_batch()` returns iteration k's batch (k counts from 0 across epochs)."""
+        self.counter.copy_(torch.tensor([self._check_iteration(k)], dtype=torch.int64))
+
+    # ---- checkpoint -------------------------------------------------------------------------------------------------
+    def _arguments(self):
+        return {"seed": self.seed, "num_windows": self.dataset.num_windows, "batch_size": self.batch_size, "shuffle": self.shuffle,
+                "rank": self.rank, "world": self.world, "last": self.last}
+
+    def state_dict(self):
+        """The arguments and the counter (a host read: synchronises).  The NEXT batch of a loaded state is the one this state
+        would have returned next."""
+        return dict(self._arguments(), counter=int(self.counter.item()))
+
+    def load_state_dict(self, sd):
+        mine = self._arguments()
+        for k, v in mine.items():
+            if k != "seed" and sd.get(k, v) != v:
+                raise ValueError("sampler state with %s = %r loaded into a sampler with %s = %r" % (k, sd.get(k), k, v))
+        k = self._check_iteration(sd["counter"])
+        self.seed = int(sd["seed"]) & (2 ** 64 - 1)
+        self.counter.copy_(torch.tensor([k], dtype=torch.int64))

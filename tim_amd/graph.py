@@ -16,6 +16,9 @@ What makes the HIP path capturable:
   * mixup's lam and permutation are host draws in the reference, which a graph would freeze as well - a step that calls
     `tim_amd.mixup.Mixup.draw()` inside `fn` redraws both on EVERY replay (the draw kernel numbers its sets with a counter it
     advances in device memory; `Mixup.mix`, `Mixup.targets` and the cross entropy read the state from device memory);
+  * the batch and the DRLoc sample positions are host work in the reference too - `tim_amd.data.WindowSampler.next_batch()` and
+    `tim_amd.losses.DrlocPositions.draw()` inside `fn` draw and assemble both on the device on every replay (counters in device
+    memory, as mixup): such a step needs no copy into static inputs before a replay;
   * the operand-dtype weight copies are rebuilt by a cast kernel at the head of the captured step, so an optimizer update
     between (or inside) replays is always picked up; with `optimizer=` a `tim_amd.optim.FusedAdamW` the captured update
     writes them itself and that cast is dropped.

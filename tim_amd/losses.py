@@ -255,9 +255,69 @@ def collect_samples(x, pos, n):
     return (x[:, pos]).view(D, n, -1).permute(1, 0, 2)
 
 
+class DrlocPositions:
+    """The DRLoc sample positions of a captured step: `pos_1`, `pos_2` int64 [n, m] in [0, l) and `deltax` fp32 [n, m] =
+    |pos_1 - pos_2| / l in device memory, redrawn by `draw()` (one launch of timhip_drloc_draw, capturable, never synchronises).
+
+        pos = DrlocPositions(batch, m, num_feats, device, seed=rank)
+        def step():                                   # eager, or the `fn` of a GraphedStep: the same sequence of draws
+            pos.draw()
+            ... dense_relative_localization_loss_crossmodal(x1, x2, model, m, positions=pos) ...
+
+    The k-th draw of a seed is a function of (seed, k) alone (Philox at SITE_DRLOC, numbered by a 64-bit device counter the
+    kernel advances), as `tim_amd.mixup.Mixup.draw()`.  The loss reads the tensors when its kernels run: compute the loss (and
+    its backward) of one draw before the next `draw()`.  There is no CPU path."""
+
+    def __init__(self, n, m, l, device=None, seed=0):
+        device = torch.device("cuda" if device is None else device)
+        if device.type != "cuda":
+            raise L.TimHipError("DrlocPositions: the TIM hot path runs on the MI355X HIP kernels only; got device %s (there is no "
+                                "CPU fallback)" % device)
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        n, m, l = int(n), int(m), int(l)
+        if n < 1 or m < 1 or not 1 <= l <= (1 << 24) or n * m > L.DRLOC_MAX_SAMPLES:
+            raise ValueError("DrlocPositions: n, m >= 1, n * m <= %d and 1 <= l <= 2^24, got (%d, %d, %d)" % (L.DRLOC_MAX_SAMPLES, n, m, l))
+        L.load()
+        self.n, self.m, self.l, self.device, self.seed = n, m, l, device, int(seed) & (2 ** 64 - 1)
+        self.pos_1 = torch.zeros((n, m), dtype=torch.int64, device=device)
+        self.pos_2 = torch.zeros((n, m), dtype=torch.int64, device=device)
+        self.deltax = torch.zeros((n, m), dtype=torch.float32, device=device)
+        self.counter = torch.zeros(1, dtype=torch.int64, device=device)
+
+    def draw(self):
+        with torch.cuda.device(self.device):
+            call("timhip_drloc_draw", self.seed, ptr(self.counter), self.n, self.m, self.l, ptr(self.pos_1), ptr(self.pos_2),
+                 ptr(self.deltax), _stream())
+        return self
+
+    def state_dict(self):
+        """seed, shape and the counter (a host read: synchronises); the NEXT draw of a loaded state is the one this state would
+        have made next"""
+        return {"seed": self.seed, "counter": int(self.counter.item()), "n": self.n, "m": self.m, "l": self.l}
+
+    def load_state_dict(self, sd):
+        for k in ("n", "m", "l"):
+            if int(sd.get(k, getattr(self, k))) != getattr(self, k):
+                raise ValueError("DRLoc positions of %s = %s loaded into an object of %s = %d" % (k, sd.get(k), k, getattr(self, k)))
+        if int(sd["counter"]) < 0:
+            raise ValueError("counter must be >= 0")
+        self.seed = int(sd["seed"]) & (2 ** 64 - 1)
+        self.counter.copy_(torch.tensor([int(sd["counter"])], dtype=torch.int64))
+
+
 def _drloc(x1, x2, model, m, positions):
     core = getattr(model, "module", model)
     n, l, D = x1.size()
+    if isinstance(positions, DrlocPositions):   # device words a captured step redraws: deltax comes with them
+        if (positions.n, positions.m, positions.l) != (n, int(m), l) or positions.device != x1.device:
+            raise ValueError("positions drawn for (n, m, l) = (%d, %d, %d) on %s, the loss needs (%d, %d, %d) on %s"
+                             % (positions.n, positions.m, positions.l, positions.device, n, int(m), l, x1.device))
+        deltax, p1, p2 = positions.deltax, positions.pos_1, positions.pos_2
+        mlp = core.drloc_mlp
+        y = DrlocFn.apply(core.rt, x1, x2, p1, p2, m, mlp[0].weight, mlp[0].bias, mlp[2].weight, mlp[2].bias, mlp[4].weight,
+                          mlp[4].bias)
+        return torch.nn.functional.l1_loss(deltax, y.view(n, m))
     pos_1, pos_2 = position_sampling(l, m, n) if positions is None else positions
     deltax = torch.abs((pos_1 - pos_2).float()).to(x1.device)
     deltax /= l
@@ -270,7 +330,8 @@ def _drloc(x1, x2, model, m, positions):
 
 
 def dense_relative_localization_loss(x, model, m, positions=None):
-    """drloc.py:17-27.  `positions=(pos_1, pos_2)` pins the sampled pairs (tests); default: drawn as the reference does."""
+    """drloc.py:17-27.  `positions=(pos_1, pos_2)` pins the sampled pairs (tests); a `DrlocPositions` supplies pairs and deltax
+    from device memory (a captured step that redraws them); default: drawn as the reference does."""
     return _drloc(x, x, model, m, positions)
 
 
