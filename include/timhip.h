@@ -827,6 +827,19 @@ int timhip_det_side_loss_fwd(const float* const* logits, const float* const* tar
                              const float* iou, const float* offsets, const float* reg_pred, float iou_threshold, float alpha,
                              float gamma, float eps, float lambda_reg, float momentum, float* normaliser, float* block,
                              void* stream);
+/* The same forward with sums that do not depend on the order in which blocks finish (additive to ABI 6).  timhip_det_side_loss_fwd
+ * adds the partial sums of its blocks and waves onto block[1..3] with float atomics: the loss of one input differs in its last place
+ * from run to run.  Here every block (focal launches) and every wave (rows launch) stores its sum in a slot of `partials` (device
+ * float[TIMHIP_DET_SIDE_PARTIALS], caller-owned scratch, contents undefined afterwards) and ONE finishing block adds the slots in a
+ * fixed order (thread t: slots t, t + 256, ... of head 0, 1, ..., then a fixed tree over the 256 threads) into block[1..3]; the
+ * finishing kernel of the atomic form follows (one launch more): the same input gives the same bits in every run, eager or as a replayed graph node.  Same arguments, checks,
+ * grids and block layout; the value differs from the atomic form's by rounding only; timhip_det_side_loss_bwd reads either block.
+ * partials NULL: TIMHIP_EINVAL. */
+#define TIMHIP_DET_SIDE_PARTIALS 4096
+int timhip_det_side_loss_fwd_ordered(const float* const* logits, const float* const* targets, const int* C, int nheads, int rows,
+                                     const float* iou, const float* offsets, const float* reg_pred, float iou_threshold, float alpha,
+                                     float gamma, float eps, float lambda_reg, float momentum, float* normaliser, float* block,
+                                     float* partials, void* stream);
 int timhip_det_side_loss_bwd(const float* const* logits, const float* const* targets, const int* C, int nheads, int rows,
                              const float* iou, const float* offsets, const float* reg_pred, float iou_threshold, float alpha,
                              float gamma, float eps, float lambda_reg, const float* block, const float* grad_out,
@@ -1068,6 +1081,47 @@ typedef struct TimWindowBatch {
   float window_size;
 } TimWindowBatch;
 int timhip_window_batch(const TimWindowBatch* desc, void* stream);
+
+/* Batch assembly of the DETECTION dataset (reference detection/.../datasets/sliding_window.py:324-399 plus default_collate) from
+ * the device words timhip_sampler_draw writes, one launch into caller-owned outputs.  Tables: feats, feat_times (leading
+ * dimension ld >= 2), row0, feat_indices [W, num_feats] and start_sec fp32 [W] as in timhip_window_batch; v_segments /
+ * a_segments fp32 [W, max, 2], the stored ground-truth segments in seconds (0 padded); v_labels / a_labels int64 [W, max, 4]
+ * (verb, noun, action, class id; -1 padded: a slot whose four words are all -1 holds no action); window_start_sec float64 [W] and
+ * video_of int32 [W] (the window's index in the dataset's sorted video list).  v_feats / a_feats NULL: that modality is absent (its
+ * feat_times must be NULL too) and its outputs are not touched; at least one is present.
+ *   window, valid, v_aug / a_aug: device words as in timhip_window_batch, with the same reading of a word outside its table as 0.
+ *   visual [B, num_feats, Cv], audio [B, num_feats, Ca] fp32: the rows timhip_window_batch copies, by the same code.
+ *   times fp32 [B, T, 2], T = num_feats per present modality (visual rows first; the model builds its own queries): per element
+ *       d = t - start_sec[w]                 one IEEE fp32 subtraction
+ *       r = rintf(d * 1000.0f) / 1000.0f     a correctly rounded fp32 product, round half to even, a correctly rounded fp32
+ *                                            division: torch.round(d, decimals=3) on fp32 (not a product with 0.001f, not double)
+ *       out = fmaxf(r / window_size, 0)      one IEEE fp32 division
+ *   v_gt_segments fp32 [B, max_v, 2], a_gt_segments fp32 [B, max_a, 2]: the same three steps on the stored segment; exactly 0.0
+ *   in a padded slot and in every slot of a row with valid[b] == 0.
+ *   verb, noun, action int64 [B, max_v], class_id int64 [B, max_a]: the window's entries (action reads label column action_col
+ *   in 0..2), -1 in a padded slot and in a row with valid[b] == 0.
+ *   window_start float64 [B] = window_start_sec[w], video_index int32 [B] = video_of[w]: the wrapped window's, also where
+ *   valid[b] == 0, as features and times are.
+ * A flat work index over (section, row, item), feature sections first, at most 2048 blocks of 256 threads.  TIMHIP_EINVAL on a
+ * null pointer that the shape needs, B / num_windows / num_feats < 1, window_size <= 0, action_col outside 0..2, a modality's
+ * times without its features, no modality; TIMHIP_EALIGN on a float pointer off 4 bytes or a double pointer off 8.  A refused
+ * call launches nothing. */
+typedef struct TimDetWindowBatch {
+  const float* v_feats; const float* a_feats;
+  const float* v_feat_times; const float* a_feat_times;
+  const int64_t* v_row0; const int64_t* a_row0;
+  const int32_t* feat_indices;
+  const float* v_segments; const float* a_segments; const float* start_sec;
+  const double* window_start_sec; const int32_t* video_of;
+  const int64_t* v_labels; const int64_t* a_labels;
+  const int32_t* window; const uint8_t* valid; const int32_t* v_aug; const int32_t* a_aug;
+  float* visual; float* audio; float* times; float* v_gt_segments; float* a_gt_segments;
+  int64_t* verb; int64_t* noun; int64_t* action; int64_t* class_id;
+  double* window_start; int32_t* video_index;
+  int32_t Cv, Ca, v_num_aug, a_num_aug, v_ld, a_ld, num_feats, max_v, max_a, B, num_windows, action_col;
+  float window_size;
+} TimDetWindowBatch;
+int timhip_det_window_batch(const TimDetWindowBatch* desc, void* stream);
 
 /* DRLoc sample positions (reference helpers/losses/drloc.py:4-7) from a device counter of their own: one block reads the counter
  * (c), stores c + 1 and writes draw c.  pos_1, pos_2 int64 [n, m] in [0, l): (uint64(word) * l) >> 32, element i = row * m + col

@@ -43,6 +43,9 @@ def __getattr__(name):  # lazy: importing the package must not require torch on 
     if name == "WindowSampler":
         from .data import WindowSampler
         return WindowSampler
+    if name in ("DeviceDetectionDataset", "DetectionWindowSampler"):
+        from . import det_data as _det_data
+        return getattr(_det_data, name)
     if name == "DrlocPositions":
         from .losses import DrlocPositions
         return DrlocPositions

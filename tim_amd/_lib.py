@@ -76,6 +76,7 @@ class TimOptItem(C.Structure):
 # words of an optimizer state block (include/timhip.h: TIMHIP_OPT_*)
 OPT_STEP, OPT_LR, OPT_NORM, OPT_COEF, OPT_FOUND_INF, OPT_SKIPPED, OPT_BC1, OPT_BC2_SQRT = range(8)
 OPT_STATE_WORDS, OPT_MAX_FLAGS, OPT_MAX_STATES = 8, 32, 8
+DET_SIDE_PARTIALS = 4096   # include/timhip.h: TIMHIP_DET_SIDE_PARTIALS (floats of scratch of timhip_det_side_loss_fwd_ordered)
 
 
 class TimWgradItem(C.Structure):
@@ -120,6 +121,16 @@ class TimWindowBatch(C.Structure):
                                   "visual", "audio", "times", "verb", "noun", "action", "class_id", "v_action_ids", "a_action_ids")] + \
                [(n, i32) for n in ("Cv", "Ca", "v_num_aug", "a_num_aug", "v_ld", "a_ld", "num_feats", "max_v", "max_a", "B",
                                    "num_windows")] + [("window_size", f32)]
+
+
+class TimDetWindowBatch(C.Structure):
+    """one timhip_det_window_batch call (include/timhip.h): the detection dataset's tables, the sampler's device words, the outputs"""
+    _fields_ = [(n, vp) for n in ("v_feats", "a_feats", "v_feat_times", "a_feat_times", "v_row0", "a_row0", "feat_indices", "v_segments",
+                                  "a_segments", "start_sec", "window_start_sec", "video_of", "v_labels", "a_labels", "window", "valid",
+                                  "v_aug", "a_aug", "visual", "audio", "times", "v_gt_segments", "a_gt_segments", "verb", "noun", "action",
+                                  "class_id", "window_start", "video_index")] + \
+               [(n, i32) for n in ("Cv", "Ca", "v_num_aug", "a_num_aug", "v_ld", "a_ld", "num_feats", "max_v", "max_a", "B",
+                                   "num_windows", "action_col")] + [("window_size", f32)]
 
 
 _SIGS = {
@@ -199,6 +210,7 @@ _SIGS = {
     "timhip_focal_loss_bwd": (C.c_int, [vp, vp, i32, i32, vp, vp, f32, f32, vp, vp, vp]),
     "timhip_diou_1d": (C.c_int, [vp, vp, i32, vp, f32, vp, vp, vp, vp]),
     "timhip_det_side_loss_fwd": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp, f32, f32, f32, f32, f32, f32, vp, vp, vp]),
+    "timhip_det_side_loss_fwd_ordered": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp, f32, f32, f32, f32, f32, f32, vp, vp, vp, vp]),
     "timhip_det_side_loss_bwd": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp, f32, f32, f32, f32, f32, vp, vp, vp, vp, vp]),
     "timhip_softnms_1d_workspace_bytes": (C.c_size_t, [C.c_int64, i32]),
     "timhip_softnms_1d": (C.c_int, [vp, vp, vp, vp, i32, f32, f32, f32, i32, vp, vp, vp, vp, C.c_size_t, vp]),
@@ -217,6 +229,7 @@ _SIGS = {
     "timhip_window_times": (C.c_int, [vp, i32, vp, vp, i32, vp, vp, i32, vp, i32, vp, i32, vp, i32, vp, f32, vp, vp]),
     "timhip_sampler_draw": (C.c_int, [u64, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
     "timhip_window_batch": (C.c_int, [C.POINTER(TimWindowBatch), vp]),
+    "timhip_det_window_batch": (C.c_int, [C.POINTER(TimDetWindowBatch), vp]),
     "timhip_drloc_draw": (C.c_int, [u64, vp, i32, i32, i32, vp, vp, vp, vp]),
     "timhip_gemm_timing_start": (C.c_int, [i32, C.c_double]),
     "timhip_gemm_timing_stop": (C.c_int, [vp, vp, vp]),

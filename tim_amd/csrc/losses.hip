@@ -243,6 +243,12 @@ __global__ void det_zero_kernel(float* block) { if (threadIdx.x < 8) block[threa
 
 __device__ __forceinline__ bool det_positive(const float* __restrict__ off, int r) { return off[2 * r] != INFINITY; }
 
+// ORDERED (timhip_det_side_loss_fwd_ordered): a block stores its sum in a slot of its own instead of adding it onto block[1] in
+// the order the blocks arrive; det_finish_ordered_kernel adds the slots in one fixed order
+constexpr int DET_PART_FOCAL = 512, DET_PART_ROWS = 256;   // most blocks of one focal launch / of the rows launch
+constexpr int DET_PART_ROWS0 = 4 * DET_PART_FOCAL;         // the rows launch's slots follow those of the four heads: (sum, count) per wave
+
+template <bool ORDERED>
 __global__ __launch_bounds__(256) void det_focal_fwd_kernel(const float* __restrict__ x, const float* __restrict__ t, long long n, int C,
                                                             const float* __restrict__ iou, float thr, float alpha, float gamma,
                                                             float* __restrict__ block) {
@@ -255,10 +261,15 @@ __global__ __launch_bounds__(256) void det_focal_fwd_kernel(const float* __restr
   __shared__ float part[4];
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
   __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(block + 1, (part[0] + part[1]) + (part[2] + part[3]));
+  if (threadIdx.x == 0) {
+    const float sum = (part[0] + part[1]) + (part[2] + part[3]);
+    if (ORDERED) block[blockIdx.x] = sum;   // (block: the head's slots)
+    else atomicAdd(block + 1, sum);
+  }
 }
 
 // positives counted, DIoU loss of the positive rows summed (forward: dpred == NULL), or its gradient written (backward)
+template <bool ORDERED>
 __global__ __launch_bounds__(256) void det_rows_kernel(const float* __restrict__ pred, const float* __restrict__ off, int n, float eps,
                                                        float* __restrict__ block, const float* __restrict__ gout, float lambda_reg,
                                                        float* __restrict__ dpred) {
@@ -290,7 +301,16 @@ __global__ __launch_bounds__(256) void det_rows_kernel(const float* __restrict__
   }
   if (!dpred) {
     acc = wave_sum(acc); cnt = wave_sum(cnt);
-    if ((threadIdx.x & 63) == 0) { atomicAdd(block + 2, acc); atomicAdd(block + 3, cnt); }
+    if ((threadIdx.x & 63) == 0) {
+      if (ORDERED) {   // (block: the rows launch's slots)
+        float* slot = block + 2 * (blockIdx.x * 4 + (threadIdx.x >> 6));
+        slot[0] = acc;
+        slot[1] = cnt;
+      } else {
+        atomicAdd(block + 2, acc);
+        atomicAdd(block + 3, cnt);
+      }
+    }
   }
 }
 
@@ -302,6 +322,47 @@ __global__ void det_finish_kernel(float* __restrict__ block, float* __restrict__
   normaliser[0] = nm;
   block[4] = nm;
   block[0] = block[1] / ((float)nheads * nm) + (npos > 0.f ? lambda_reg * block[2] / nm : 0.f);
+}
+
+struct DetParts {
+  int focal[4];   // blocks of each head's focal launch
+  int rows;       // blocks of the rows launch
+};
+
+// the sum of one value per thread of a 256-thread block, by a tree whose shape does not depend on anything that runs
+__device__ __forceinline__ float det_tree_sum(float v, float* sh) {
+  sh[threadIdx.x] = v;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+    __syncthreads();
+  }
+  const float r = sh[0];
+  __syncthreads();
+  return r;
+}
+
+// ONE block of 256 threads: thread t adds the slots t, t + 256, ... of every launch in ascending order, then the tree; the sums
+// go where the atomics would have left them and det_finish_kernel follows (the SAME kernel as in the atomic form: normaliser and
+// loss are then the same instructions on the sums)
+__global__ __launch_bounds__(256) void det_sum_ordered_kernel(float* __restrict__ block, const float* __restrict__ partials, const DetParts p,
+                                                              int nheads) {
+  __shared__ float sh[256];
+  float focal = 0.f, diou = 0.f, cnt = 0.f;
+  for (int k = 0; k < nheads; ++k)
+    for (int j = threadIdx.x; j < p.focal[k]; j += 256) focal += partials[k * DET_PART_FOCAL + j];
+  for (int j = threadIdx.x; j < p.rows * 4; j += 256) {
+    diou += partials[DET_PART_ROWS0 + 2 * j];
+    cnt += partials[DET_PART_ROWS0 + 2 * j + 1];
+  }
+  focal = det_tree_sum(focal, sh);
+  diou = det_tree_sum(diou, sh);
+  cnt = det_tree_sum(cnt, sh);
+  if (threadIdx.x == 0) {
+    block[1] = focal;
+    block[2] = diou;
+    block[3] = cnt;
+  }
 }
 
 __global__ __launch_bounds__(256) void det_focal_bwd_kernel(const float* __restrict__ x, const float* __restrict__ t, long long n, int C,
@@ -365,29 +426,58 @@ int timhip_diou_1d(const float* pred_offsets, const float* target_offsets, int n
   return TIMHIP_OK;
 }
 
-int timhip_det_side_loss_fwd(const float* const* logits, const float* const* targets, const int* C, int nheads, int rows,
-                             const float* iou, const float* offsets, const float* reg_pred, float iou_threshold, float alpha,
-                             float gamma, float eps, float lambda_reg, float momentum, float* normaliser, float* block,
-                             void* stream) {
+// partials == NULL: the sums are added with atomics (timhip_det_side_loss_fwd); else into slots, added in a fixed order
+static int det_side_loss_fwd(const float* const* logits, const float* const* targets, const int* C, int nheads, int rows, const float* iou,
+                             const float* offsets, const float* reg_pred, float iou_threshold, float alpha, float gamma, float eps,
+                             float lambda_reg, float momentum, float* normaliser, float* block, float* partials, void* stream) {
   if (!logits || !targets || !C || nheads < 1 || nheads > 4 || rows < 0 || !iou || !offsets || !reg_pred || !normaliser || !block)
     return TIMHIP_EINVAL;
   for (int k = 0; k < nheads && rows > 0; ++k)     // every head is checked before the first launch: a refused call writes nothing
     if (!logits[k] || !targets[k] || C[k] <= 0) return TIMHIP_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(det_zero_kernel, dim3(1), dim3(64), 0, s, block);
+  DetParts parts = {{0, 0, 0, 0}, 0};
   if (rows > 0) {
     for (int k = 0; k < nheads; ++k) {
       const long long n = (long long)rows * C[k];
-      const int blocks = (int)((n + 255) / 256 > 512 ? 512 : (n + 255) / 256);   // one atomic per block on a single address
-      hipLaunchKernelGGL(det_focal_fwd_kernel, dim3(blocks), dim3(256), 0, s, logits[k], targets[k], n, C[k], iou, iou_threshold,
-                         alpha, gamma, block);
+      const int blocks = (int)((n + 255) / 256 > DET_PART_FOCAL ? DET_PART_FOCAL : (n + 255) / 256);   // one atomic per block on a single address
+      parts.focal[k] = blocks;
+      if (partials)
+        hipLaunchKernelGGL(det_focal_fwd_kernel<true>, dim3(blocks), dim3(256), 0, s, logits[k], targets[k], n, C[k], iou, iou_threshold,
+                           alpha, gamma, partials + k * DET_PART_FOCAL);
+      else
+        hipLaunchKernelGGL(det_focal_fwd_kernel<false>, dim3(blocks), dim3(256), 0, s, logits[k], targets[k], n, C[k], iou, iou_threshold,
+                           alpha, gamma, block);
     }
-    hipLaunchKernelGGL(det_rows_kernel, dim3((rows + 255) / 256 > 256 ? 256 : (rows + 255) / 256), dim3(256), 0, s, reg_pred, offsets,
-                       rows, eps, block, (const float*)nullptr, lambda_reg, (float*)nullptr);
+    parts.rows = (rows + 255) / 256 > DET_PART_ROWS ? DET_PART_ROWS : (rows + 255) / 256;
+    if (partials)
+      hipLaunchKernelGGL(det_rows_kernel<true>, dim3(parts.rows), dim3(256), 0, s, reg_pred, offsets, rows, eps, partials + DET_PART_ROWS0,
+                         (const float*)nullptr, lambda_reg, (float*)nullptr);
+    else
+      hipLaunchKernelGGL(det_rows_kernel<false>, dim3(parts.rows), dim3(256), 0, s, reg_pred, offsets, rows, eps, block,
+                         (const float*)nullptr, lambda_reg, (float*)nullptr);
   }
+  if (partials) hipLaunchKernelGGL(det_sum_ordered_kernel, dim3(1), dim3(256), 0, s, block, (const float*)partials, parts, nheads);
   hipLaunchKernelGGL(det_finish_kernel, dim3(1), dim3(1), 0, s, block, normaliser, momentum, lambda_reg, nheads);
   TIM_CHECK_LAUNCH();
   return TIMHIP_OK;
+}
+
+int timhip_det_side_loss_fwd(const float* const* logits, const float* const* targets, const int* C, int nheads, int rows,
+                             const float* iou, const float* offsets, const float* reg_pred, float iou_threshold, float alpha,
+                             float gamma, float eps, float lambda_reg, float momentum, float* normaliser, float* block,
+                             void* stream) {
+  return det_side_loss_fwd(logits, targets, C, nheads, rows, iou, offsets, reg_pred, iou_threshold, alpha, gamma, eps, lambda_reg, momentum,
+                           normaliser, block, nullptr, stream);
+}
+
+int timhip_det_side_loss_fwd_ordered(const float* const* logits, const float* const* targets, const int* C, int nheads, int rows,
+                                     const float* iou, const float* offsets, const float* reg_pred, float iou_threshold, float alpha,
+                                     float gamma, float eps, float lambda_reg, float momentum, float* normaliser, float* block,
+                                     float* partials, void* stream) {
+  if (!partials) return TIMHIP_EINVAL;
+  return det_side_loss_fwd(logits, targets, C, nheads, rows, iou, offsets, reg_pred, iou_threshold, alpha, gamma, eps, lambda_reg, momentum,
+                           normaliser, block, partials, stream);
 }
 
 int timhip_det_side_loss_bwd(const float* const* logits, const float* const* targets, const int* C, int nheads, int rows,
@@ -408,7 +498,7 @@ int timhip_det_side_loss_bwd(const float* const* logits, const float* const* tar
                        alpha, gamma, block, grad_out, nheads, dlogits[k]);
   }
   if (dreg)
-    hipLaunchKernelGGL(det_rows_kernel, dim3((rows + 255) / 256 > 256 ? 256 : (rows + 255) / 256), dim3(256), 0, s, reg_pred, offsets,
+    hipLaunchKernelGGL(det_rows_kernel<false>, dim3((rows + 255) / 256 > 256 ? 256 : (rows + 255) / 256), dim3(256), 0, s, reg_pred, offsets,
                        rows, eps, const_cast<float*>(block), grad_out, lambda_reg, dreg);
   TIM_CHECK_LAUNCH();
   return TIMHIP_OK;

@@ -4,6 +4,8 @@
 //     augmentation indices of a batch, from philox4x32_7 keyed by the seed and numbered by a device counter the kernel advances
 //   * window_batch_kernel: the batch of data.py's DeviceWindowDataset.batch() from those device words into caller-owned outputs,
 //     one byte-bound launch (the eager form: two gathers, the times kernel and four torch index ops)
+//   * det_window_batch_kernel: the same for the detection dataset (tim_amd/det_data.py): feature rows through the same mover,
+//     times and ground-truth segments rounded to 1e-3 s in fp32 as torch.round does, labels, window start and video index
 //   * drloc_draw_kernel: the DRLoc sample positions and their normalised distance, a device counter of its own
 #include "common.h"
 
@@ -96,8 +98,10 @@ __device__ __forceinline__ void wb_divmod(long long r, int d, long long& q, int&
   }
 }
 
-// the window of batch row b (a word outside the table reads window 0: nothing is read out of bounds)
-__device__ __forceinline__ int wb_window(const TimWindowBatch& d, long long b) {
+// the window of batch row b (a word outside the table reads window 0: nothing is read out of bounds); D: TimWindowBatch or
+// TimDetWindowBatch - the fields read here and in wb_feature_item carry the same names in both
+template <class D>
+__device__ __forceinline__ int wb_window(const D& d, long long b) {
   const int w = d.window[b];
   return (unsigned)w < (unsigned)d.num_windows ? w : 0;
 }
@@ -106,7 +110,8 @@ __device__ __forceinline__ int wb_window(const TimWindowBatch& d, long long b) {
 // index chain (window -> row0, feat_indices, aug) is walked once per four loads and the four loads are in flight together
 constexpr int WB_UNROLL = 4, WB_SPAN = 64 * WB_UNROLL;   // chunks a wave covers (the four loads are written out below)
 
-__device__ __forceinline__ void wb_feature_item(const TimWindowBatch& d, const float* __restrict__ feats, const long long* __restrict__ row0,
+template <class D>
+__device__ __forceinline__ void wb_feature_item(const D& d, const float* __restrict__ feats, const long long* __restrict__ row0,
                                                 const int* __restrict__ aug, int num_aug, int C, float* __restrict__ out, long long row,
                                                 int group) {
   long long b;
@@ -194,6 +199,91 @@ __global__ __launch_bounds__(256) void window_batch_kernel(const WbArgs a) {
       const size_t src = (size_t)w * d.max_a + q, dst = (size_t)b * d.max_a + q;
       ((long long*)d.class_id)[dst] = ok ? ((const long long*)d.a_labels)[src * 4 + 3] : -1ll;
       ((long long*)d.a_action_ids)[dst] = ok ? ((const long long*)d.a_ids)[src] : -1ll;
+    }
+  }
+}
+
+// ---- detection batch assembly -----------------------------------------------------------------------------------------
+enum { DB_VISUAL = 0, DB_AUDIO, DB_TIMES, DB_VSEG, DB_ASEG, DB_META, DB_SECTIONS };
+
+struct DbArgs {
+  TimDetWindowBatch d;
+  long long first[DB_SECTIONS + 1];   // as WbArgs
+  int groups_v, groups_a, T;
+};
+
+// torch.round(t - start, decimals=3) / window_size clamped at 0, in fp32 steps that are each correctly rounded: the subtraction,
+// nearbyint(d * 1000) (round half to even), the division by 1000 (NOT a product with 0.001f) and the division by the window size
+__device__ __forceinline__ float db_norm(float t, float st, float ws) {
+  const float d = __fsub_rn(t, st);
+  const float r = __fdiv_rn(rintf(__fmul_rn(d, 1000.0f)), 1000.0f);
+  return fmaxf(__fdiv_rn(r, ws), 0.f);
+}
+
+// a slot of a label table [W, max, 4] that holds no action: all four words are -1 (a real row carries a class in at least one)
+__device__ __forceinline__ bool db_padded(const long long* lab) { return (lab[0] & lab[1] & lab[2] & lab[3]) == -1ll; }
+
+// the feature sections are window_batch_kernel's (wb_feature_item); then one (start, end) row, one ground-truth slot or one
+// batch row per item
+__global__ __launch_bounds__(256) void det_window_batch_kernel(const DbArgs a) {
+  const TimDetWindowBatch& d = a.d;
+  const long long total = a.first[DB_SECTIONS], stride = (long long)gridDim.x * blockDim.x;
+  for (long long wi = (long long)blockIdx.x * blockDim.x + threadIdx.x; wi < total; wi += stride) {
+    if (wi < a.first[DB_AUDIO]) {
+      long long row;
+      int chunk;
+      wb_divmod(wi, a.groups_v, row, chunk);
+      wb_feature_item(d, d.v_feats, (const long long*)d.v_row0, d.v_aug, d.v_num_aug, d.Cv, d.visual, row, chunk);
+    } else if (wi < a.first[DB_TIMES]) {
+      long long row;
+      int chunk;
+      wb_divmod(wi - a.first[DB_AUDIO], a.groups_a, row, chunk);
+      wb_feature_item(d, d.a_feats, (const long long*)d.a_row0, d.a_aug, d.a_num_aug, d.Ca, d.audio, row, chunk);
+    } else if (wi < a.first[DB_VSEG]) {
+      long long b;
+      int t;
+      wb_divmod(wi - a.first[DB_TIMES], a.T, b, t);
+      const int w = wb_window(d, b), nf = d.num_feats;
+      const int nfv = d.v_feat_times ? nf : 0;
+      const float st = d.start_sec[w];
+      const float* p;
+      if (t < nfv) p = d.v_feat_times + (size_t)(((const long long*)d.v_row0)[w] + d.feat_indices[(size_t)w * nf + t]) * d.v_ld;
+      else p = d.a_feat_times + (size_t)(((const long long*)d.a_row0)[w] + d.feat_indices[(size_t)w * nf + (t - nfv)]) * d.a_ld;
+      const float s = p[0], e = p[1];
+      float* o = d.times + ((size_t)b * a.T + t) * 2;
+      o[0] = db_norm(s, st, d.window_size);
+      o[1] = db_norm(e, st, d.window_size);
+    } else if (wi < a.first[DB_ASEG]) {
+      long long b;
+      int q;
+      wb_divmod(wi - a.first[DB_VSEG], d.max_v, b, q);
+      const int w = wb_window(d, b);
+      const size_t src = (size_t)w * d.max_v + q, dst = (size_t)b * d.max_v + q;
+      const long long* lab = (const long long*)d.v_labels + src * 4;
+      const bool ok = d.valid[b] != 0, real = ok && !db_padded(lab);
+      const float st = d.start_sec[w];
+      d.v_gt_segments[dst * 2] = real ? db_norm(d.v_segments[src * 2], st, d.window_size) : 0.f;
+      d.v_gt_segments[dst * 2 + 1] = real ? db_norm(d.v_segments[src * 2 + 1], st, d.window_size) : 0.f;
+      ((long long*)d.verb)[dst] = ok ? lab[0] : -1ll;
+      ((long long*)d.noun)[dst] = ok ? lab[1] : -1ll;
+      ((long long*)d.action)[dst] = ok ? lab[d.action_col] : -1ll;
+    } else if (wi < a.first[DB_META]) {
+      long long b;
+      int q;
+      wb_divmod(wi - a.first[DB_ASEG], d.max_a, b, q);
+      const int w = wb_window(d, b);
+      const size_t src = (size_t)w * d.max_a + q, dst = (size_t)b * d.max_a + q;
+      const long long* lab = (const long long*)d.a_labels + src * 4;
+      const bool ok = d.valid[b] != 0, real = ok && !db_padded(lab);
+      const float st = d.start_sec[w];
+      d.a_gt_segments[dst * 2] = real ? db_norm(d.a_segments[src * 2], st, d.window_size) : 0.f;
+      d.a_gt_segments[dst * 2 + 1] = real ? db_norm(d.a_segments[src * 2 + 1], st, d.window_size) : 0.f;
+      ((long long*)d.class_id)[dst] = ok ? lab[3] : -1ll;
+    } else {   // the wrapped window's values, whatever valid[b] says
+      const long long b = wi - a.first[DB_META];
+      const int w = wb_window(d, b);
+      d.window_start[b] = d.window_start_sec[w];
+      d.video_index[b] = d.video_of[w];
     }
   }
 }
@@ -297,6 +387,54 @@ int timhip_window_batch(const TimWindowBatch* desc, void* stream) {
   const long long want = (total + 255) / 256;
   const int blocks = (int)(want > 2048 ? 2048 : want);
   hipLaunchKernelGGL(window_batch_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
+  TIM_CHECK_LAUNCH();
+  return TIMHIP_OK;
+}
+
+int timhip_det_window_batch(const TimDetWindowBatch* desc, void* stream) {
+  if (!desc) return TIMHIP_EINVAL;
+  DbArgs a;
+  a.d = *desc;
+  const TimDetWindowBatch& d = a.d;
+  if (d.B < 1 || d.num_windows < 1 || d.num_feats < 1 || d.max_v < 0 || d.max_a < 0 || !(d.window_size > 0.f)) return TIMHIP_EINVAL;
+  if (d.action_col < 0 || d.action_col > 2) return TIMHIP_EINVAL;
+  if (!d.window || !d.valid || !d.feat_indices || !d.start_sec || !d.window_start_sec || !d.video_of || !d.times || !d.window_start ||
+      !d.video_index)
+    return TIMHIP_EINVAL;
+  const bool has_v = d.v_feats != nullptr, has_a = d.a_feats != nullptr;
+  if (!has_v && !has_a) return TIMHIP_EINVAL;
+  if (has_v && (!d.v_row0 || !d.v_feat_times || !d.visual || d.Cv < 1 || d.v_num_aug < 1 || d.v_ld < 2)) return TIMHIP_EINVAL;
+  if (has_a && (!d.a_row0 || !d.a_feat_times || !d.audio || d.Ca < 1 || d.a_num_aug < 1 || d.a_ld < 2)) return TIMHIP_EINVAL;
+  if ((!has_v && d.v_feat_times) || (!has_a && d.a_feat_times)) return TIMHIP_EINVAL;
+  if (d.max_v > 0 && (!d.v_segments || !d.v_labels || !d.v_gt_segments || !d.verb || !d.noun || !d.action)) return TIMHIP_EINVAL;
+  if (d.max_a > 0 && (!d.a_segments || !d.a_labels || !d.a_gt_segments || !d.class_id)) return TIMHIP_EINVAL;
+  if ((((uintptr_t)d.visual) | ((uintptr_t)d.audio) | ((uintptr_t)d.times) | ((uintptr_t)d.v_feats) | ((uintptr_t)d.a_feats) |
+       ((uintptr_t)d.v_feat_times) | ((uintptr_t)d.a_feat_times) | ((uintptr_t)d.start_sec) | ((uintptr_t)d.v_segments) |
+       ((uintptr_t)d.a_segments) | ((uintptr_t)d.v_gt_segments) | ((uintptr_t)d.a_gt_segments)) & 3)
+    return TIMHIP_EALIGN;
+  if ((((uintptr_t)d.window_start_sec) | ((uintptr_t)d.window_start)) & 7) return TIMHIP_EALIGN;
+  a.groups_v = has_v ? ((d.Cv + 3) / 4 + 255) / 256 * 64 : 64;   // (wb_feature_item: 256 chunks per wave)
+  a.groups_a = has_a ? ((d.Ca + 3) / 4 + 255) / 256 * 64 : 64;
+  a.T = (has_v ? d.num_feats : 0) + (has_a ? d.num_feats : 0);
+  const long long rows = (long long)d.B * d.num_feats;
+  if (rows > (1ll << 40) / (a.groups_v > a.groups_a ? a.groups_v : a.groups_a)) return TIMHIP_EUNSUPPORTED;   // (as timhip_window_batch)
+  long long total = 0;
+  a.first[DB_VISUAL] = total;
+  total += has_v ? rows * a.groups_v : 0;
+  a.first[DB_AUDIO] = total;
+  total += has_a ? rows * a.groups_a : 0;
+  a.first[DB_TIMES] = total;
+  total += (long long)d.B * a.T;
+  a.first[DB_VSEG] = total;
+  total += (long long)d.B * d.max_v;
+  a.first[DB_ASEG] = total;
+  total += (long long)d.B * d.max_a;
+  a.first[DB_META] = total;
+  total += d.B;
+  a.first[DB_SECTIONS] = total;
+  const long long want = (total + 255) / 256;
+  const int blocks = (int)(want > 2048 ? 2048 : want);
+  hipLaunchKernelGGL(det_window_batch_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
   TIM_CHECK_LAUNCH();
   return TIMHIP_OK;
 }

@@ -150,24 +150,9 @@ class DeviceWindowDataset:
         return WindowSampler(self, batch_size, seed=seed, shuffle=shuffle, rank=rank, world=world, last=last)
 
 
-class WindowSampler:
-    """The batches of a seeded, epoch-shuffled, rank-sharded order over a `DeviceWindowDataset`, with all state on the device.
-
-        smp = ds.sampler(batch_size, seed=0, shuffle=True, rank=rank, world=world)
-        def step():                                   # eager, or the `fn` of a GraphedStep: the same sequence of batches
-            visual, audio, times, label, metadata = smp.next_batch()       # two launches, no host input
-            ...
-
-    `next_batch()` returns what `ds.batch(indices)` returns (shapes, dtypes, dict keys; narration-id strings aside - they are
-    host data, `ds.narration_ids(metadata["window"].cpu())` looks them up), in tensors the sampler owns: the SAME objects on
-    every call, refilled by `timhip_sampler_draw` + `timhip_window_batch`.  The k-th call of a seed (counted by a 64-bit word
-    in device memory that the draw kernel advances) returns iteration k: epoch k // iterations_per_epoch of an order that is
-    `DistributedSampler`'s in structure - the epoch's permutation, padded with its own head to a multiple of `world`, dealt
-    round-robin to the ranks - with its own keyed permutation (include/timhip.h), not torch's randperm stream.  With
-    `last="wrap"` a short last batch keeps its full shape: the rows beyond the rank's share have `metadata["valid"] == 0`, the
-    features and times of a real window and -1 ("no query") in every label and id; `last="drop"` drops that batch.
-
-    No CPU path: the kernels run or the call raises."""
+class _DeviceOrder:
+    """What `WindowSampler` and `det_data.DetectionWindowSampler` share: the arguments of a seeded, epoch-shuffled, rank-sharded
+    order over a dataset's windows, the device words `timhip_sampler_draw` writes, position and checkpoint."""
 
     def __init__(self, dataset, batch_size, seed=0, shuffle=True, rank=0, world=1, last="wrap"):
         ds = self.dataset = dataset
@@ -189,7 +174,7 @@ class WindowSampler:
         self.iterations_per_epoch = -(-self.per_rank // B) if last == "wrap" else self.per_rank // B
         if self.iterations_per_epoch < 1:
             raise ValueError('last="drop": %d windows per rank do not fill one batch of %d' % (self.per_rank, B))
-        dev, nf, mv, ma = ds.device, ds.num_feats, ds.max_visual_actions, ds.max_audio_actions
+        dev, nf = ds.device, ds.num_feats
         self.device = dev
         self.counter = torch.zeros(1, dtype=torch.int64, device=dev)       # the number of the NEXT iteration
         self.epoch = torch.zeros(1, dtype=torch.int64, device=dev)         # of the batch drawn last
@@ -198,6 +183,69 @@ class WindowSampler:
         self.valid = torch.zeros(B, dtype=torch.uint8, device=dev)
         self.v_aug = torch.zeros((B, nf), dtype=torch.int32, device=dev) if ds.has_v else None
         self.a_aug = torch.zeros((B, nf), dtype=torch.int32, device=dev) if ds.has_a else None
+
+    def _draw(self, st):
+        ds = self.dataset
+        call("timhip_sampler_draw", self.seed, ptr(self.counter), ds.num_windows, self.world, self.rank, self.batch_size,
+             int(self.shuffle), L.SAMPLER_WRAP if self.last == "wrap" else L.SAMPLER_DROP, ds.num_feats,
+             ds.v["num_aug"] if ds.has_v else 0, ds.a["num_aug"] if ds.has_a else 0, ptr(self.window), ptr(self.valid),
+             ptr(self.v_aug), ptr(self.a_aug), ptr(self.epoch), ptr(self.iteration), st)
+
+    # ---- position ---------------------------------------------------------------------------------------------------
+    def _check_iteration(self, k):
+        k = int(k)
+        if k < 0 or k // self.iterations_per_epoch >= (1 << L.SAMPLER_EPOCH_BITS):
+            raise ValueError("iteration %d: the order is defined for epochs [0, 2^%d) of %d iterations"
+                             % (k, L.SAMPLER_EPOCH_BITS, self.iterations_per_epoch))
+        return k
+
+    def set_iteration(self, k):
+        """The next `next_batch()` returns iteration k's batch (k counts from 0 across epochs)."""
+        self.counter.copy_(torch.tensor([self._check_iteration(k)], dtype=torch.int64))
+
+    # ---- checkpoint -------------------------------------------------------------------------------------------------
+    def _arguments(self):
+        return {"seed": self.seed, "num_windows": self.dataset.num_windows, "batch_size": self.batch_size, "shuffle": self.shuffle,
+                "rank": self.rank, "world": self.world, "last": self.last}
+
+    def state_dict(self):
+        """The arguments and the counter (a host read: synchronises).  The NEXT batch of a loaded state is the one this state
+        would have returned next."""
+        return dict(self._arguments(), counter=int(self.counter.item()))
+
+    def load_state_dict(self, sd):
+        mine = self._arguments()
+        for k, v in mine.items():
+            if k != "seed" and sd.get(k, v) != v:
+                raise ValueError("sampler state with %s = %r loaded into a sampler with %s = %r" % (k, sd.get(k), k, v))
+        k = self._check_iteration(sd["counter"])
+        self.seed = int(sd["seed"]) & (2 ** 64 - 1)
+        self.counter.copy_(torch.tensor([k], dtype=torch.int64))
+
+
+class WindowSampler(_DeviceOrder):
+    """The batches of a seeded, epoch-shuffled, rank-sharded order over a `DeviceWindowDataset`, with all state on the device.
+
+        smp = ds.sampler(batch_size, seed=0, shuffle=True, rank=rank, world=world)
+        def step():                                   # eager, or the `fn` of a GraphedStep: the same sequence of batches
+            visual, audio, times, label, metadata = smp.next_batch()       # two launches, no host input
+            ...
+
+    `next_batch()` returns what `ds.batch(indices)` returns (shapes, dtypes, dict keys; narration-id strings aside - they are
+    host data, `ds.narration_ids(metadata["window"].cpu())` looks them up), in tensors the sampler owns: the SAME objects on
+    every call, refilled by `timhip_sampler_draw` + `timhip_window_batch`.  The k-th call of a seed (counted by a 64-bit word
+    in device memory that the draw kernel advances) returns iteration k: epoch k // iterations_per_epoch of an order that is
+    `DistributedSampler`'s in structure - the epoch's permutation, padded with its own head to a multiple of `world`, dealt
+    round-robin to the ranks - with its own keyed permutation (include/timhip.h), not torch's randperm stream.  With
+    `last="wrap"` a short last batch keeps its full shape: the rows beyond the rank's share have `metadata["valid"] == 0`, the
+    features and times of a real window and -1 ("no query") in every label and id; `last="drop"` drops that batch.
+
+    No CPU path: the kernels run or the call raises."""
+
+    def __init__(self, dataset, batch_size, seed=0, shuffle=True, rank=0, world=1, last="wrap"):
+        super().__init__(dataset, batch_size, seed=seed, shuffle=shuffle, rank=rank, world=world, last=last)
+        ds, B = dataset, self.batch_size
+        dev, nf, mv, ma = ds.device, ds.num_feats, ds.max_visual_actions, ds.max_audio_actions
         f32 = lambda *s: torch.zeros(s, dtype=torch.float32, device=dev)   # noqa: E731
         i64 = lambda *s: torch.full(s, -1, dtype=torch.int64, device=dev)   # noqa: E731
         self.visual = f32(B, nf, ds.v["C"]) if ds.has_v else torch.empty((B, 0), device=dev)
@@ -233,45 +281,10 @@ class WindowSampler:
     def next_batch(self):
         """Two launches on the current stream: the draw of the next iteration and the assembly of its batch into the sampler's
         own tensors -> (visual, audio, times, label, metadata), the same objects every time.  Capturable; never synchronises."""
-        ds = self.dataset
         if self._desc is None:
             self._desc = self._descriptor()
         with torch.cuda.device(self.device):
             st = _stream()
-            call("timhip_sampler_draw", self.seed, ptr(self.counter), ds.num_windows, self.world, self.rank, self.batch_size,
-                 int(self.shuffle), L.SAMPLER_WRAP if self.last == "wrap" else L.SAMPLER_DROP, ds.num_feats,
-                 ds.v["num_aug"] if ds.has_v else 0, ds.a["num_aug"] if ds.has_a else 0, ptr(self.window), ptr(self.valid),
-                 ptr(self.v_aug), ptr(self.a_aug), ptr(self.epoch), ptr(self.iteration), st)
+            self._draw(st)
             call("timhip_window_batch", C.byref(self._desc), st)
         return self.visual, self.audio, self.times, self.label, self.metadata
-
-    # ---- position ---------------------------------------------------------------------------------------------------
-    def _check_iteration(self, k):
-        k = int(k)
-        if k < 0 or k // self.iterations_per_epoch >= (1 << L.SAMPLER_EPOCH_BITS):
-            raise ValueError("iteration %d: the order is defined for epochs [0, 2^%d) of %d iterations"
-                             % (k, L.SAMPLER_EPOCH_BITS, self.iterations_per_epoch))
-        return k
-
-    def set_iteration(self, k):
-        """The next `next_batch()` returns iteration k's batch (k counts from 0 across epochs)."""
-        self.counter.copy_(torch.tensor([self._check_iteration(k)], dtype=torch.int64))
-
-    # ---- checkpoint -------------------------------------------------------------------------------------------------
-    def _arguments(self):
-        return {"seed": self.seed, "num_windows": self.dataset.num_windows, "batch_size": self.batch_size, "shuffle": self.shuffle,
-                "rank": self.rank, "world": self.world, "last": self.last}
-
-    def state_dict(self):
-        """The arguments and the counter (a host read: synchronises).  The NEXT batch of a loaded state is the one this state
-        would have returned next."""
-        return dict(self._arguments(), counter=int(self.counter.item()))
-
-    def load_state_dict(self, sd):
-        mine = self._arguments()
-        for k, v in mine.items():
-            if k != "seed" and sd.get(k, v) != v:
-                raise ValueError("sampler state with %s = %r loaded into a sampler with %s = %r" % (k, sd.get(k), k, v))
-        k = self._check_iteration(sd["counter"])
-        self.seed = int(sd["seed"]) & (2 ** 64 - 1)
-        self.counter.copy_(torch.tensor([k], dtype=torch.int64))

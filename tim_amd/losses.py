@@ -449,7 +449,7 @@ def ctr_diou_loss_1d(input_offsets, target_offsets, reduction: str = "none", eps
 class _DetSideLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, aux, iou, offsets, reg_pred, *logits):
-        targets, normaliser, thr, alpha, gamma, eps, lam, mom = aux
+        targets, normaliser, thr, alpha, gamma, eps, lam, mom, ordered = aux
         _require_gpu(reg_pred, "detection side loss")
         dev = reg_pred.device
         xs = [_f32c(x) for x in logits]
@@ -467,8 +467,13 @@ class _DetSideLossFn(torch.autograd.Function):
         block = torch.empty(8, dtype=torch.float32, device=dev)
         Cs = (C.c_int * len(xs))(*[x.shape[1] for x in xs])
         pa = lambda ts_: (C.c_void_p * len(ts_))(*[ptr(t) for t in ts_])   # noqa: E731
-        call("timhip_det_side_loss_fwd", pa(xs), pa(ts), Cs, len(xs), rows, ptr(u), ptr(off), ptr(rp), float(thr), float(alpha),
-             float(gamma), float(eps), float(lam), float(mom), ptr(normaliser), ptr(block), _stream())
+        args = (pa(xs), pa(ts), Cs, len(xs), rows, ptr(u), ptr(off), ptr(rp), float(thr), float(alpha), float(gamma), float(eps), float(lam),
+                float(mom), ptr(normaliser), ptr(block))
+        if ordered:
+            partials = torch.empty(L.DET_SIDE_PARTIALS, dtype=torch.float32, device=dev)
+            call("timhip_det_side_loss_fwd_ordered", *args, ptr(partials), _stream())
+        else:
+            call("timhip_det_side_loss_fwd", *args, _stream())
         ctx.consts = (float(thr), float(alpha), float(gamma), float(eps), float(lam), rows, tuple(reg_pred.shape))
         ctx.n = len(xs)
         ctx.save_for_backward(block, u, off, rp, *xs, *ts)
@@ -491,7 +496,7 @@ class _DetSideLossFn(torch.autograd.Function):
 
 
 def detection_side_loss(cls_logits, cls_targets, reg_pred, offsets, iou, normaliser, iou_threshold, lambda_reg=0.5, momentum=0.9,
-                        alpha=0.25, gamma=2.0, eps=1e-8):
+                        alpha=0.25, gamma=2.0, eps=1e-8, ordered=False):
     """One modality side of the detection training loss, det scripts/train.py:222-349, as a handful of launches:
 
         valid_cls = iou >= 0;  w = where(iou < iou_threshold, 1, iou);  positive = offsets[:, 0] != inf
@@ -502,12 +507,15 @@ def detection_side_loss(cls_logits, cls_targets, reg_pred, offsets, iou, normali
 
     cls_logits / cls_targets: lists of the side's K heads ([rows, C_k] each; verb / noun / action, or the audio head).  The loop's
     eager form derives the flags and weights with ~25 small torch launches per side; here the kernels derive them in place
-    (timhip_det_side_loss_fwd / _bwd).  Gradients flow to the logits and to reg_pred."""
+    (timhip_det_side_loss_fwd / _bwd).  Gradients flow to the logits and to reg_pred.
+
+    ordered=True: the sums are added in a fixed order (timhip_det_side_loss_fwd_ordered) instead of with float atomics - one input
+    gives the same loss bits in every run, eager or replayed; the value differs from the default form's by rounding only."""
     if not isinstance(cls_logits, (list, tuple)):
         cls_logits, cls_targets = [cls_logits], [cls_targets]
     if normaliser.dtype != torch.float32 or normaliser.numel() != 1 or not normaliser.is_cuda:
         raise ValueError("normaliser: a float32 scalar tensor on the GPU (it is advanced in place)")
-    aux = (list(cls_targets), normaliser, iou_threshold, alpha, gamma, eps, lambda_reg, momentum)
+    aux = (list(cls_targets), normaliser, iou_threshold, alpha, gamma, eps, lambda_reg, momentum, bool(ordered))
     return _DetSideLossFn.apply(aux, iou, offsets, reg_pred, *cls_logits)
 
 

@@ -47,7 +47,7 @@ BUDGET = {
     "rowops.hip": [(r"ln_fwd8", 0), (r"ln_bwd_kernel", 0)],
     "optim.hip": [(r"optim_norm_kernel", 0), (r"optim_update_kernel", 0)],   # streaming kernels: scratch traffic would share their HBM budget
     "mixup.hip": [(r"mixup_apply_kernel", 0)],   # streaming: two reads and one write per element, nothing else may touch memory
-    "sampler.hip": [(r"window_batch_kernel", 0)],   # streaming: one read and one write per gathered element
+    "sampler.hip": [(r"det_window_batch_kernel", 0), (r"window_batch_kernel", 0)],  # streaming: one read and one write per gathered element
     "detect.hip": [(r"det_count_kernel", 0), (r"det_scan_kernel", 0), (r"det_emit_kernel", 0)],   # streaming: one read of the logits each
     "twostream.hip": [(r"ts_select_kernel", 0), (r"det_scan_kernel", 0), (r"ts_emit_kernel", 0)],   # streaming: both rows of logits once
     "detmap.hip": [(r"det_match_kernel", 0), (r"det_ap_kernel", 0)],   # a wave's segments and lock words live in registers
