@@ -968,6 +968,68 @@ int timhip_rec_finalize(const float* sum, int pitch, int C, const float* seen, c
 int timhip_rec_counts(const int32_t* rank_a, const int32_t* rank_b, const uint8_t* touched, int num_actions, int32_t* counts,
                       void* stream);
 
+/* rec_combined: the AVE-only "combined" accuracy of the reference's meters (meters.py:283-285, :563-565).  prob_v /
+ * prob_a: the probabilities rec_finalize wrote for the action head and the audio head ([num_actions, pitch_*], the same C).
+ * The reference adds the two POSITIONALLY over the labelled actions of each modality: the k-th touched visual id a (ascending)
+ * is paired with the k-th touched audio id b.  rank[a] = the rank of l = labels_state[a, label_col] over
+ * (prob_v[a, c] + prob_a[b, c]) * 0.5f (fp32, the sum rounded, then the product) with rec_finalize's tie rule; 0x7fffffff for
+ * an untouched visual id, a visual id without a partner or a label outside [0, C).  rec_counts over touched_v then gives the
+ * counts.  One launch; a wavefront finds its pair with two scans of the touched bytes (num_actions / 64 steps each). */
+int timhip_rec_combined(const float* prob_v, int pitch_v, const float* prob_a, int pitch_a, int C, const int32_t* labels_state,
+                        int n_labels, int label_col, const uint8_t* touched_v, const uint8_t* touched_a, int num_actions,
+                        int32_t* rank, void* stream);
+
+/* ---------------------------------------------------------------- training meter (additive to ABI 6) */
+/* The loss averages and batch accuracies of a recognition training run, kept in device memory: what the reference's TrainMeter
+ * (recognition/time_interval_machine/utils/meters.py:30-167) keeps on the host after copying every head's logits there.
+ *
+ * STATE BLOCK: TIMHIP_METER_STATE_WORDS 32-bit words, 8-byte aligned, zero before the first update (and to reset).  The enum
+ * gives WORD offsets; 64-bit fields (marked) start on even words:
+ *   TIMHIP_METER_UPDATES             int64   updates so far
+ *   TIMHIP_METER_SUM   + 4 * slot    double  sum of val * n          slot = TIMHIP_METER_TOTAL .. _AUDIO
+ *   TIMHIP_METER_COUNT + 4 * slot    int64   sum of n                (avg = sum / count is the reader's division; 0 -> 0.0)
+ *   TIMHIP_METER_RUN + 6 * head + 2 * k   int64   k = 0 rows, 1 top-1 hits, 2 top-5 hits since the reset, head = TIMHIP_METER_HEAD_*
+ *   TIMHIP_METER_VAL   + slot        float   the loss of the last update that touched the slot
+ *   TIMHIP_METER_LAST + 3 * head + k int32   the same three counts of the last update alone
+ *   TIMHIP_METER_NV, TIMHIP_METER_NA int32   valid visual / audio rows of the last update
+ *
+ * meter_update: one batch.  v_heads / a_heads: HOST arrays of up to TIMHIP_METER_MAX_HEADS heads per modality over the
+ *   UNFILTERED fp32 logits [R, C] with row stride ld (elements, >= C).  v_labels [Rv, >= 3] int64 (verb, noun, action; row
+ *   stride ld_v_labels), a_labels [Ra, >= 1]; under mixup these are target_a.  A visual row is valid iff its action label
+ *   (column 2) is not -1, an audio row iff column 0 is not -1; nv and na are those counts, taken on the device.
+ *   losses: HOST array of TIMHIP_METER_SLOTS DEVICE pointers to one fp32 each (NULL: that loss counts as 0).  One thread does,
+ *   in this order and in double / int64, sum = sum + (double)val * n (the product rounded on its own), count += n:
+ *     TOTAL, DRLOC with n = nv + na, always;  VISUAL, then VERB and NOUN (only with TIMHIP_METER_VERB_NOUN), then ACTION
+ *     with n = nv, only when nv > 0;  AUDIO with n = na, only when na > 0   (the conditions of meters.py:140-167).
+ *   With TIMHIP_METER_BATCH_ACCURACY every valid row of every head is ranked over its raw logits x:
+ *     rank = #{c : x_c > x_y} + #{c < y : x_c == x_y}, y = labels[r, head.label_col]; no rank (counted as a row, never a hit)
+ *     when y is outside [0, C) or x_y is NaN.  head.slot names the counters it feeds; with a VERB and a NOUN head the MT
+ *     counters take the larger of the two ranks (multitask accuracy).  work: timhip_meter_work_words(...) int32 of scratch.
+ *   At most two launches on `stream`, no floating-point atomics, no allocation, no host read: replayable in a HIP graph, and
+ *   every word is the same in every run.  Rv == 0 and Ra == 0 launches nothing.  Refused before any launch: NULL state /
+ *   losses / heads / labels (logits with rows), more than TIMHIP_METER_MAX_HEADS heads in a group, C < 1, ld < C, a label
+ *   column or slot out of range, unknown flags - TIMHIP_EINVAL; a state block off 8 bytes - TIMHIP_EALIGN. */
+enum { TIMHIP_METER_TOTAL = 0, TIMHIP_METER_DRLOC = 1, TIMHIP_METER_VISUAL = 2, TIMHIP_METER_VERB = 3, TIMHIP_METER_NOUN = 4,
+       TIMHIP_METER_ACTION = 5, TIMHIP_METER_AUDIO = 6 };
+#define TIMHIP_METER_SLOTS 7
+enum { TIMHIP_METER_HEAD_VERB = 0, TIMHIP_METER_HEAD_NOUN = 1, TIMHIP_METER_HEAD_ACTION = 2, TIMHIP_METER_HEAD_MT = 3,
+       TIMHIP_METER_HEAD_AUDIO = 4 };
+#define TIMHIP_METER_HEADS 5
+enum { TIMHIP_METER_UPDATES = 0, TIMHIP_METER_SUM = 2, TIMHIP_METER_COUNT = 4, TIMHIP_METER_RUN = 30, TIMHIP_METER_VAL = 60,
+       TIMHIP_METER_LAST = 67, TIMHIP_METER_NV = 82, TIMHIP_METER_NA = 83 };
+#define TIMHIP_METER_STATE_WORDS 84
+#define TIMHIP_METER_MAX_HEADS 3
+enum { TIMHIP_METER_VERB_NOUN = 1, TIMHIP_METER_BATCH_ACCURACY = 2 };   /* flags */
+typedef struct TimMeterHead {
+  const float* logits;
+  int64_t ld;
+  int32_t C, label_col, slot, reserved;
+} TimMeterHead;
+size_t timhip_meter_work_words(const TimMeterHead* v_heads, int n_v, int Rv, const TimMeterHead* a_heads, int n_a, int Ra);
+int timhip_meter_update(const TimMeterHead* v_heads, int n_v, const int64_t* v_labels, int64_t ld_v_labels, int Rv,
+                        const TimMeterHead* a_heads, int n_a, const int64_t* a_labels, int64_t ld_a_labels, int Ra,
+                        const float* const* losses, int flags, void* state, int32_t* work, void* stream);
+
 /* ---------------------------------------------------------------- detection scoring: detections to AP */
 /* The ActivityNet-style interpolated average precision of the reference's scoring script (detection/eval_detection/
  * evaluate_detection_json.py: compute_average_precision_detection, segment_iou, interpolated_prec_rec), on tables the caller

@@ -31,6 +31,9 @@ def __getattr__(name):  # lazy: importing the package must not require torch on 
     if name == "RecognitionCollector":
         from .recog import RecognitionCollector
         return RecognitionCollector
+    if name == "TrainMeter":
+        from .meters import TrainMeter
+        return TrainMeter
     if name == "AttentionMaps":
         from .attn_maps import AttentionMaps
         return AttentionMaps

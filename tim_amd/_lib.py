@@ -102,6 +102,18 @@ class TimRecHead(C.Structure):
 REC_MAX_HEADS = 3   # include/timhip.h: TIMHIP_REC_MAX_HEADS
 
 
+class TimMeterHead(C.Structure):
+    _fields_ = [("logits", vp), ("ld", C.c_int64), ("C", i32), ("label_col", i32), ("slot", i32), ("reserved", i32)]
+
+
+# a training meter's state block (include/timhip.h: TIMHIP_METER_*): loss slots, counter rows, WORD offsets (64-bit fields on even words)
+METER_TOTAL, METER_DRLOC, METER_VISUAL, METER_VERB, METER_NOUN, METER_ACTION, METER_AUDIO = range(7)
+METER_HEAD_VERB, METER_HEAD_NOUN, METER_HEAD_ACTION, METER_HEAD_MT, METER_HEAD_AUDIO = range(5)
+METER_SLOTS, METER_HEADS, METER_MAX_HEADS, METER_STATE_WORDS = 7, 5, 3, 84
+METER_UPDATES, METER_SUM, METER_COUNT, METER_RUN, METER_VAL, METER_LAST, METER_NV, METER_NA = 0, 2, 4, 30, 60, 67, 82, 83
+METER_VERB_NOUN, METER_BATCH_ACCURACY = 1, 2   # flags
+
+
 class TimAvga(C.Structure):
     """one AVGA pooling call (include/timhip.h): inputs, operand copies of the weights, shape"""
     _fields_ = [(n, vp) for n in ("video", "audio", "w_video", "w_audio", "w_v", "w_g", "w_v_t", "w_g_t", "w_video_s", "w_audio_s", "b_video",
@@ -225,6 +237,9 @@ _SIGS = {
     "timhip_rec_accumulate": (C.c_int, [vp, i32, vp, vp, vp, C.c_int64, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     "timhip_rec_finalize": (C.c_int, [vp, i32, i32, vp, vp, i32, i32, vp, i32, vp, vp, vp]),
     "timhip_rec_counts": (C.c_int, [vp, vp, vp, i32, vp, vp]),
+    "timhip_rec_combined": (C.c_int, [vp, i32, vp, i32, i32, vp, i32, i32, vp, vp, i32, vp, vp]),
+    "timhip_meter_work_words": (sz, [vp, i32, i32, vp, i32, i32]),
+    "timhip_meter_update": (C.c_int, [vp, i32, vp, C.c_int64, i32, vp, i32, vp, C.c_int64, i32, vp, i32, vp, vp, vp]),
     "timhip_window_gather": (C.c_int, [vp, i32, i32, vp, vp, i32, vp, i32, vp, vp, vp]),
     "timhip_window_times": (C.c_int, [vp, i32, vp, vp, i32, vp, vp, i32, vp, i32, vp, i32, vp, i32, vp, f32, vp, vp]),
     "timhip_sampler_draw": (C.c_int, [u64, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),

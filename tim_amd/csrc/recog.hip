@@ -28,6 +28,8 @@
 //            double exp, like the sigmoid of detect.hip.
 // rec_counts_kernel      one block: #(rank < 1), #(rank < 5) and the number of touched actions; with a second rank vector
 //                        the rank is the larger of the two (verb + noun multitask accuracy).
+// rec_combined_kernel    the AVE-only "combined" accuracy: the action and the audio probabilities of the labelled
+//                        actions paired by position, averaged in fp32 and ranked; described at the kernel.
 //
 // The unit is compiled with contraction off (no product here feeds an add, and none may start to).  Loads are one dword per
 // lane, 256 contiguous bytes per wave instruction, four chunks in flight, as in detect.hip: rows of 97 or 3,806 floats are
@@ -271,6 +273,70 @@ __global__ __launch_bounds__(1024) void rec_counts_kernel(const int* __restrict_
   }
 }
 
+// The AVE-only "combined" accuracy (meters.py:283-285): the reference adds the visual and the audio probabilities of the
+// labelled actions POSITIONALLY, the k-th labelled visual action with the k-th labelled audio action in ascending id order.
+// One wavefront per touched visual action a: k = #touched visual ids below a, b = the k-th touched audio id (two ballot
+// scans over the touched bytes: num_actions / 64 steps each, a few thousand ids on AVE), then the rank of a's label over
+// (p_action[a] + p_audio[b]) * 0.5f in fp32, with rec_finalize_kernel's tie rule.  No partner: kNoRank.
+__global__ __launch_bounds__(64 * kWavesPerBlock) void rec_combined_kernel(
+    const float* __restrict__ prob_v, int pitch_v, const float* __restrict__ prob_a, int pitch_a, int C,
+    const int* __restrict__ labels_state, int n_labels, int label_col, const uint8_t* __restrict__ touched_v,
+    const uint8_t* __restrict__ touched_a, int num_actions, int* __restrict__ rank) {
+  const int lane = threadIdx.x & 63;
+  const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+  const int nwaves = gridDim.x * kWavesPerBlock;
+  for (int a = wave; a < num_actions; a += nwaves) {
+    if (!touched_v[a]) {
+      if (lane == 0) rank[a] = kNoRank;
+      continue;
+    }
+    int k = 0;
+    for (int base = 0; base < a; base += 64) {
+      const int j = base + lane;
+      k += __popcll(__ballot(j < a && touched_v[j] != 0));
+    }
+    int b = -1, seen = 0;
+    for (int base = 0; base < num_actions && b < 0; base += 64) {
+      const int j = base + lane;
+      unsigned long long m = __ballot(j < num_actions && touched_a[j] != 0);
+      const int pc = __popcll(m);
+      if (seen + pc > k) {
+        for (int i = seen; i < k; ++i) m &= m - 1;              // drop the set bits in front of the k-th
+        b = base + (int)__ffsll((long long)m) - 1;
+      }
+      seen += pc;
+    }
+    const int lab = labels_state[(size_t)a * n_labels + label_col];
+    const bool has = b >= 0 && lab >= 0 && lab < C;
+    if (!has) {
+      if (lane == 0) rank[a] = kNoRank;
+      continue;
+    }
+    const float* pv = prob_v + (size_t)a * (size_t)pitch_v;
+    const float* pa = prob_a + (size_t)b * (size_t)pitch_a;
+    const float sl = __fmul_rn(__fadd_rn(pv[lab], pa[lab]), 0.5f);
+    int above = 0;
+    for (int cb = 0; cb < C; cb += kChunk) {
+      float x[4], y[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int c = cb + 64 * q + lane;
+        x[q] = c < C ? pv[c] : 0.0f;
+        y[q] = c < C ? pa[c] : 0.0f;
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int c = cb + 64 * q + lane;
+        const float s = __fmul_rn(__fadd_rn(x[q], y[q]), 0.5f);
+        above += c < C && (s > sl || (s == sl && c < lab));
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) above += __shfl_xor(above, o, 64);
+    if (lane == 0) rank[a] = above;
+  }
+}
+
 int rec_grid(long long waves) {
   const long long blocks = (waves + kWavesPerBlock - 1) / kWavesPerBlock;
   return blocks < 1 ? 1 : (blocks > kMaxBlocks ? kMaxBlocks : (int)blocks);
@@ -318,6 +384,18 @@ int timhip_rec_finalize(const float* sum, int pitch, int C, const float* seen, c
   if (labels_state && (n_labels < 1 || label_col < 0 || label_col >= n_labels)) return TIMHIP_EINVAL;
   hipLaunchKernelGGL(rec_finalize_kernel, dim3(rec_grid(num_actions)), dim3(64 * kWavesPerBlock), 0, (hipStream_t)stream, sum,
                      pitch, C, seen, labels_state, n_labels, label_col, touched, num_actions, prob, rank);
+  TIM_CHECK_LAUNCH();
+  return TIMHIP_OK;
+}
+
+int timhip_rec_combined(const float* prob_v, int pitch_v, const float* prob_a, int pitch_a, int C, const int32_t* labels_state,
+                        int n_labels, int label_col, const uint8_t* touched_v, const uint8_t* touched_a, int num_actions,
+                        int32_t* rank, void* stream) {
+  if (!prob_v || !prob_a || !labels_state || !touched_v || !touched_a || !rank) return TIMHIP_EINVAL;
+  if (C < 1 || pitch_v < C || pitch_a < C || num_actions < 1 || n_labels < 1 || label_col < 0 || label_col >= n_labels)
+    return TIMHIP_EINVAL;
+  hipLaunchKernelGGL(rec_combined_kernel, dim3(rec_grid(num_actions)), dim3(64 * kWavesPerBlock), 0, (hipStream_t)stream, prob_v,
+                     pitch_v, prob_a, pitch_a, C, labels_state, n_labels, label_col, touched_v, touched_a, num_actions, rank);
   TIM_CHECK_LAUNCH();
   return TIMHIP_OK;
 }

@@ -95,6 +95,7 @@ class RecognitionCollector:
         self.err = torch.zeros((1,), dtype=torch.int32, device=self.device)
         self._counts = torch.zeros((8, 3), dtype=torch.int32, device=self.device)
         self._work = None
+        self._combined = None            # (action probabilities, audio probabilities, rank) of accuracies(combined=True)
 
     def reset(self):
         for g in self.groups.values():
@@ -207,16 +208,49 @@ class RecognitionCollector:
                 rows.append("mt_action")
         return rows
 
-    def accuracies(self):
+    def _launch_combined(self, row):
+        """the AVE-only "combined" accuracy (the reference's meters.py:283-285): the action and the audio probabilities of
+        the labelled actions, paired by position, averaged and ranked -> self._counts[row]"""
+        v, a = self.groups.get("visual"), self.groups.get("audio")
+        if v is None or a is None:
+            raise ValueError("the combined accuracy needs both modalities")
+        i = v.heads.index("action")
+        if v.classes[i] != a.classes[0]:
+            raise ValueError("the combined accuracy adds the action and the audio probabilities: %d and %d classes do not "
+                             "broadcast" % (v.classes[i], a.classes[0]))
+        if self._combined is None:
+            self._combined = (torch.zeros_like(v.sum[i]), torch.zeros_like(a.sum[0]),
+                              torch.empty((self.num_actions,), dtype=torch.int32, device=self.device))
+        pv, pa, rank = self._combined
+        self._finalize(v, i, pv)
+        self._finalize(a, 0, pa)
+        st = _stream()
+        call("timhip_rec_combined", ptr(pv), v.pitch[i], ptr(pa), a.pitch[0], v.classes[i], ptr(v.labels), v.n_labels,
+             HEADS["action"][0], ptr(v.touched), ptr(a.touched), self.num_actions, ptr(rank), st)
+        call("timhip_rec_counts", ptr(rank), None, ptr(v.touched), self.num_actions, ptr(self._counts[row]), st)
+
+    def accuracies(self, combined=False):
         """{"verb" / "noun" / "action" / "audio": (top1, top5), "mt_action": (top1, top5)} in per cent, the floats the
-        reference's accuracy() / multitask_accuracy() return.  One read of a few integers; raises if an id was out of range."""
+        reference's accuracy() / multitask_accuracy() return.  One read of a few integers; raises if an id was out of range.
+        combined=True (AVE, both modalities) adds "combined": the k-th labelled visual action's probabilities and the k-th
+        labelled audio action's, in ascending id order, averaged in fp32 and ranked against the visual action label - the
+        reference's positional add; unequal numbers of labelled actions or of classes raise ValueError (the reference fails
+        to broadcast there)."""
         rows = self._launch_accuracies()
+        if combined:
+            self._launch_combined(len(rows))
+            rows.append("combined")
         back = torch.cat([self._counts[:len(rows)].reshape(-1), self.err]).cpu().numpy()
         self._check(int(back[-1]))
         out = {}
         for k, h in enumerate(rows):
             c1, c5, n = (int(v) for v in back[3 * k:3 * k + 3])
             out[h] = multitask_floats(c1, c5, n) if h == "mt_action" else accuracy_floats(c1, c5, n)
+        if combined:
+            n_v, n_a = (int(back[3 * rows.index(h) + 2]) for h in ("action", "audio"))
+            if n_v != n_a:
+                raise ValueError("the combined accuracy pairs the labelled actions by position: %d visual and %d audio "
+                                 "actions do not broadcast" % (n_v, n_a))
         return out
 
     def ranks(self):

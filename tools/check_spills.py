@@ -52,7 +52,8 @@ BUDGET = {
     "twostream.hip": [(r"ts_select_kernel", 0), (r"det_scan_kernel", 0), (r"ts_emit_kernel", 0)],   # streaming: both rows of logits once
     "detmap.hip": [(r"det_match_kernel", 0), (r"det_ap_kernel", 0)],   # a wave's segments and lock words live in registers
     "recog.hip": [(r"rec_eid_kernel", 0), (r"rec_link_kernel", 0), (r"rec_accumulate_kernel", 0), (r"rec_finalize_kernel", 0),
-                  (r"rec_counts_kernel", 0)],   # streaming: the logits once, the accumulator chunk once in and once out
+                  (r"rec_counts_kernel", 0), (r"rec_combined_kernel", 0)],   # streaming: the logits once, the accumulator chunk once in and once out
+    "meter.hip": [(r"meter_rank_kernel", 0), (r"meter_finish_kernel", 0)],   # streaming: a segment's 16 dwords per lane and 17 counters live in registers
     # one block per CU-sized LDS image (128 KiB of staged cells at Cv = 1024): 86 (forward) / 132-176 (backward) VGPRs of the 512 a
     # wave may have at that occupancy - nothing forces a spill, and scratch traffic would sit inside the MFMA loops
     "avga.hip": [(r"avga_kernel", 0), (r"avga_zero_kernel", 0), (r"avga_audio_kernel", 0)],   # (the last two: a fill and a cast)
