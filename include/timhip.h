@@ -840,6 +840,32 @@ int timhip_det_side_loss_fwd_ordered(const float* const* logits, const float* co
                                      const float* iou, const float* offsets, const float* reg_pred, float iou_threshold, float alpha,
                                      float gamma, float eps, float lambda_reg, float momentum, float* normaliser, float* block,
                                      float* partials, void* stream);
+/* The ordered forward with the SIDE STATISTICS a detection meter needs (additive to ABI 6): what the reference's loop
+ * gets from a second focal pass with reduction="none" over the action head (det scripts/train.py:262-273, :315-326) comes out of the
+ * pass that is made anyway.  Arguments of _fwd_ordered plus `stats` (device float[TIMHIP_DET_SIDE_STATS_WORDS], every word written):
+ *   TIMHIP_DET_STAT_HEAD_SUM + k   focal sum of head k < nheads (0 for the other k < 4)
+ *   TIMHIP_DET_STAT_POS_SUM        the LAST head's focal sum over the rows with iou >= 0 and offsets[r, 0] != inf
+ *   TIMHIP_DET_STAT_NEG_SUM        the LAST head's focal sum over the rows with iou >= 0 and offsets[r, 0] == inf
+ *   TIMHIP_DET_STAT_VALID          rows with iou >= 0              _POSITIVES   = block[3]      _DIOU_SUM = block[2]
+ *   TIMHIP_DET_STAT_NORMALISER     = block[4]                      _LOSS        = block[0]
+ *   TIMHIP_DET_STAT_CLS            focal / (nheads * nm)           _REG         positives > 0 ? lambda_reg * DIoU / nm : 0
+ *   TIMHIP_DET_STAT_HEAD + k       HEAD_SUM[k] / nm                _POS, _NEG   POS_SUM / nm, NEG_SUM / nm      (nm = block[4])
+ * all fp32; counts are exact floats.  partials: float[TIMHIP_DET_SIDE_STATS_PARTIALS] (the ordered form's slots, then the last head's
+ * (positive, negative) per block and the valid rows per wave).  No float atomics.  The last head's launch keeps two more accumulators
+ * and reads offsets[r, 0] beside iou[r]; the accumulators behind block[1..3] are the ordered form's: for one input block[0..7] and
+ * normaliser are bit for bit those of _fwd_ordered, and timhip_det_side_loss_bwd reads the block as before.  Same launches as the
+ * ordered form (its kernels' stats arms).  Refused before any launch, nothing written: what _fwd_ordered refuses, stats or partials
+ * NULL - TIMHIP_EINVAL; rows > 2^24 - TIMHIP_EUNSUPPORTED.  rows == 0: zeros, with NORMALISER = block[4] advanced as by _fwd_ordered. */
+enum { TIMHIP_DET_STAT_HEAD_SUM = 0, TIMHIP_DET_STAT_POS_SUM = 4, TIMHIP_DET_STAT_NEG_SUM = 5, TIMHIP_DET_STAT_VALID = 6,
+       TIMHIP_DET_STAT_POSITIVES = 7, TIMHIP_DET_STAT_DIOU_SUM = 8, TIMHIP_DET_STAT_NORMALISER = 9, TIMHIP_DET_STAT_LOSS = 10,
+       TIMHIP_DET_STAT_CLS = 11, TIMHIP_DET_STAT_REG = 12, TIMHIP_DET_STAT_HEAD = 13, TIMHIP_DET_STAT_POS = 17, TIMHIP_DET_STAT_NEG = 18,
+       TIMHIP_DET_STAT_RESERVED = 19 };
+#define TIMHIP_DET_SIDE_STATS_WORDS 20
+#define TIMHIP_DET_SIDE_STATS_PARTIALS 6144
+int timhip_det_side_loss_fwd_stats(const float* const* logits, const float* const* targets, const int* C, int nheads, int rows,
+                                   const float* iou, const float* offsets, const float* reg_pred, float iou_threshold, float alpha,
+                                   float gamma, float eps, float lambda_reg, float momentum, float* normaliser, float* block,
+                                   float* partials, float* stats, void* stream);
 int timhip_det_side_loss_bwd(const float* const* logits, const float* const* targets, const int* C, int nheads, int rows,
                              const float* iou, const float* offsets, const float* reg_pred, float iou_threshold, float alpha,
                              float gamma, float eps, float lambda_reg, const float* block, const float* grad_out,
@@ -1029,6 +1055,43 @@ size_t timhip_meter_work_words(const TimMeterHead* v_heads, int n_v, int Rv, con
 int timhip_meter_update(const TimMeterHead* v_heads, int n_v, const int64_t* v_labels, int64_t ld_v_labels, int Rv,
                         const TimMeterHead* a_heads, int n_a, const int64_t* a_labels, int64_t ld_a_labels, int Ra,
                         const float* const* losses, int flags, void* state, int32_t* work, void* stream);
+
+/* ---------------------------------------------------------------- detection meter (additive to ABI 6) */
+/* The eleven loss averages of the reference's detection TrainMeter and InferenceMeter (detection/time_interval_machine/utils/
+ * meters.py:29-315, :317-572), kept in device memory and fed by the side statistics of timhip_det_side_loss_fwd_stats: what
+ * det scripts/train.py:413-430 hands over after thirteen .cpu().item() / .cpu() reads.
+ *
+ * STATE BLOCK: TIMHIP_DET_METER_STATE_WORDS 32-bit words, 8-byte aligned, zero before the first update (and to reset).  WORD
+ * offsets; 64-bit fields (marked) start on even words:
+ *   TIMHIP_DET_METER_UPDATES                    int64   updates so far
+ *   TIMHIP_DET_METER_SUM   + 4 * slot           double  sum of val * n        slot = TIMHIP_DET_METER_TOTAL .. _NEGATIVE
+ *   TIMHIP_DET_METER_COUNT + 4 * slot           int64   sum of n              (avg = sum / count is the reader's division; 0 -> 0.0)
+ *   TIMHIP_DET_METER_RUN  + 4 * side + 2 * k    int64   k = 0 valid rows (iou >= 0), 1 positives since the reset; side 0 visual, 1 audio
+ *   TIMHIP_DET_METER_VAL   + slot               float   the value of the last update that touched the slot
+ *   TIMHIP_DET_METER_LAST + 2 * side + k        int32   the same two counts of the last update alone
+ *   TIMHIP_DET_METER_NORM + side                float   the normaliser the side's last update used
+ *
+ * det_meter_update: sides: HOST array of two DEVICE pointers to stats blocks (visual, audio; NULL: the side is absent and counts as
+ *   zero rows).  nheads: the visual side's heads, 3 (verb, noun, action) or 1.  total_loss / drloc_loss: device scalars, NULL
+ *   counts as 0.  One launch of one block; one thread does, in this order and in double / int64, sum = sum + (double)val * n
+ *   (the product rounded on its own), count += n   (meters.py:94-137), with v_cls / v_pos / a_cls / a_pos the sides' VALID /
+ *   POSITIVES words and every value its own side's, divided by that side's normaliser:
+ *     v_cls > 0:  VISUAL = CLS, then VERB = HEAD[0] and NOUN = HEAD[1] (nheads == 3), then ACTION = HEAD[nheads - 1], n = v_cls;
+ *                 VISUAL_REG = REG and POSITIVE = POS with n = v_pos;  NEGATIVE = NEG with n = v_cls - v_pos
+ *     a_cls > 0:  AUDIO = CLS with n = a_cls;  AUDIO_REG = REG and POSITIVE = POS with n = a_pos;  NEGATIVE = NEG, n = a_cls - a_pos
+ *     always:     TOTAL, DRLOC with n = v_cls + a_cls
+ *   No synchronisation, no host read, no atomics: every word has the same bits eagerly and as a replayed graph node.  Refused
+ *   before the launch: NULL state / sides, both sides NULL, nheads not 1 or 3 - TIMHIP_EINVAL; a state block off 8 bytes -
+ *   TIMHIP_EALIGN. */
+enum { TIMHIP_DET_METER_TOTAL = 0, TIMHIP_DET_METER_DRLOC = 1, TIMHIP_DET_METER_VISUAL = 2, TIMHIP_DET_METER_VERB = 3,
+       TIMHIP_DET_METER_NOUN = 4, TIMHIP_DET_METER_ACTION = 5, TIMHIP_DET_METER_VISUAL_REG = 6, TIMHIP_DET_METER_AUDIO = 7,
+       TIMHIP_DET_METER_AUDIO_REG = 8, TIMHIP_DET_METER_POSITIVE = 9, TIMHIP_DET_METER_NEGATIVE = 10 };
+#define TIMHIP_DET_METER_SLOTS 11
+enum { TIMHIP_DET_METER_UPDATES = 0, TIMHIP_DET_METER_SUM = 2, TIMHIP_DET_METER_COUNT = 4, TIMHIP_DET_METER_RUN = 46,
+       TIMHIP_DET_METER_VAL = 54, TIMHIP_DET_METER_LAST = 65, TIMHIP_DET_METER_NORM = 69 };
+#define TIMHIP_DET_METER_STATE_WORDS 72
+int timhip_det_meter_update(void* state, const float* const* sides, int nheads, const float* total_loss, const float* drloc_loss,
+                            void* stream);
 
 /* ---------------------------------------------------------------- detection scoring: detections to AP */
 /* The ActivityNet-style interpolated average precision of the reference's scoring script (detection/eval_detection/

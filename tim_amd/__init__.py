@@ -34,6 +34,9 @@ def __getattr__(name):  # lazy: importing the package must not require torch on 
     if name == "TrainMeter":
         from .meters import TrainMeter
         return TrainMeter
+    if name == "DetectionMeter":
+        from .meters import DetectionMeter
+        return DetectionMeter
     if name == "AttentionMaps":
         from .attn_maps import AttentionMaps
         return AttentionMaps

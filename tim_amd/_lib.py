@@ -77,6 +77,10 @@ class TimOptItem(C.Structure):
 OPT_STEP, OPT_LR, OPT_NORM, OPT_COEF, OPT_FOUND_INF, OPT_SKIPPED, OPT_BC1, OPT_BC2_SQRT = range(8)
 OPT_STATE_WORDS, OPT_MAX_FLAGS, OPT_MAX_STATES = 8, 32, 8
 DET_SIDE_PARTIALS = 4096   # include/timhip.h: TIMHIP_DET_SIDE_PARTIALS (floats of scratch of timhip_det_side_loss_fwd_ordered)
+# timhip_det_side_loss_fwd_stats: its scratch and the words of a side stats block (include/timhip.h: TIMHIP_DET_STAT_*)
+DET_SIDE_STATS_PARTIALS, DET_SIDE_STATS_WORDS = 6144, 20
+(DET_STAT_HEAD_SUM, DET_STAT_POS_SUM, DET_STAT_NEG_SUM, DET_STAT_VALID, DET_STAT_POSITIVES, DET_STAT_DIOU_SUM, DET_STAT_NORMALISER,
+ DET_STAT_LOSS, DET_STAT_CLS, DET_STAT_REG, DET_STAT_HEAD, DET_STAT_POS, DET_STAT_NEG, DET_STAT_RESERVED) = 0, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 17, 18, 19
 
 
 class TimWgradItem(C.Structure):
@@ -112,6 +116,12 @@ METER_HEAD_VERB, METER_HEAD_NOUN, METER_HEAD_ACTION, METER_HEAD_MT, METER_HEAD_A
 METER_SLOTS, METER_HEADS, METER_MAX_HEADS, METER_STATE_WORDS = 7, 5, 3, 84
 METER_UPDATES, METER_SUM, METER_COUNT, METER_RUN, METER_VAL, METER_LAST, METER_NV, METER_NA = 0, 2, 4, 30, 60, 67, 82, 83
 METER_VERB_NOUN, METER_BATCH_ACCURACY = 1, 2   # flags
+
+# a detection meter's state block (include/timhip.h: TIMHIP_DET_METER_*): slots, then WORD offsets (64-bit fields on even words)
+(DET_METER_TOTAL, DET_METER_DRLOC, DET_METER_VISUAL, DET_METER_VERB, DET_METER_NOUN, DET_METER_ACTION, DET_METER_VISUAL_REG,
+ DET_METER_AUDIO, DET_METER_AUDIO_REG, DET_METER_POSITIVE, DET_METER_NEGATIVE) = range(11)
+DET_METER_SLOTS, DET_METER_STATE_WORDS = 11, 72
+DET_METER_UPDATES, DET_METER_SUM, DET_METER_COUNT, DET_METER_RUN, DET_METER_VAL, DET_METER_LAST, DET_METER_NORM = 0, 2, 4, 46, 54, 65, 69
 
 
 class TimAvga(C.Structure):
@@ -223,7 +233,9 @@ _SIGS = {
     "timhip_diou_1d": (C.c_int, [vp, vp, i32, vp, f32, vp, vp, vp, vp]),
     "timhip_det_side_loss_fwd": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp, f32, f32, f32, f32, f32, f32, vp, vp, vp]),
     "timhip_det_side_loss_fwd_ordered": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp, f32, f32, f32, f32, f32, f32, vp, vp, vp, vp]),
+    "timhip_det_side_loss_fwd_stats": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp, f32, f32, f32, f32, f32, f32, vp, vp, vp, vp, vp]),
     "timhip_det_side_loss_bwd": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp, f32, f32, f32, f32, f32, vp, vp, vp, vp, vp]),
+    "timhip_det_meter_update": (C.c_int, [vp, vp, i32, vp, vp, vp]),
     "timhip_softnms_1d_workspace_bytes": (C.c_size_t, [C.c_int64, i32]),
     "timhip_softnms_1d": (C.c_int, [vp, vp, vp, vp, i32, f32, f32, f32, i32, vp, vp, vp, vp, C.c_size_t, vp]),
     "timhip_nms_1d": (C.c_int, [vp, vp, vp, i32, f32, vp, vp, vp, vp]),

@@ -247,36 +247,77 @@ __device__ __forceinline__ bool det_positive(const float* __restrict__ off, int 
 // the order the blocks arrive; det_finish_ordered_kernel adds the slots in one fixed order
 constexpr int DET_PART_FOCAL = 512, DET_PART_ROWS = 256;   // most blocks of one focal launch / of the rows launch
 constexpr int DET_PART_ROWS0 = 4 * DET_PART_FOCAL;         // the rows launch's slots follow those of the four heads: (sum, count) per wave
+// the stats form's own slots follow the ordered form's: (positive, negative) per block of the last head's launch, valid rows per wave
+constexpr int DET_PART_SPLIT0 = TIMHIP_DET_SIDE_PARTIALS, DET_PART_VALID0 = DET_PART_SPLIT0 + 2 * DET_PART_FOCAL;
+static_assert(DET_PART_ROWS0 + 8 * DET_PART_ROWS == TIMHIP_DET_SIDE_PARTIALS, "the ordered form's slots");
+static_assert(DET_PART_VALID0 + 4 * DET_PART_ROWS == TIMHIP_DET_SIDE_STATS_PARTIALS, "the stats form's slots");
 
-template <bool ORDERED>
-__global__ __launch_bounds__(256) void det_focal_fwd_kernel(const float* __restrict__ x, const float* __restrict__ t, long long n, int C,
-                                                            const float* __restrict__ iou, float thr, float alpha, float gamma,
-                                                            float* __restrict__ block) {
-  float acc = 0.f;
+// STATS (timhip_det_side_loss_fwd_stats, the LAST head's launch): the same elements also go to two more accumulators, the rows with
+// a positive offset target and the others, through products of their own (the row weight or 0, times the term): `acc` and what
+// feeds it are the instructions of the ordered form.  parts: (positive, negative) per block
+template <bool ORDERED, bool STATS>
+__device__ __forceinline__ void det_focal_fwd_body(const float* __restrict__ x, const float* __restrict__ t, long long n, int C,
+                                                   const float* __restrict__ iou, float thr, float alpha, float gamma,
+                                                   float* __restrict__ block, const float* __restrict__ off, float* __restrict__ parts) {
+  float acc = 0.f, accp = 0.f, accn = 0.f;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const float u = iou[i / C];
-    if (u >= 0.f) acc += (u < thr ? 1.f : u) * focal_term(x[i], t[i], alpha, gamma).loss;
+    const long long r = i / C;
+    const float u = iou[r];
+    const float o = STATS ? off[2 * r] : 0.f;   // (asked for beside iou[r], not behind its test: one round trip, not two)
+    if (u >= 0.f) {
+      const float w = u < thr ? 1.f : u, l = focal_term(x[i], t[i], alpha, gamma).loss;
+      acc += w * l;
+      if (STATS) {
+        const bool pos = o != INFINITY;
+        accp += (pos ? w : 0.f) * l;
+        accn += (pos ? 0.f : w) * l;
+      }
+    }
   }
   acc = wave_sum(acc);
-  __shared__ float part[4];
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+  __shared__ float part[STATS ? 12 : 4];
+  if (STATS) { accp = wave_sum(accp); accn = wave_sum(accn); }
+  if ((threadIdx.x & 63) == 0) {
+    part[threadIdx.x >> 6] = acc;
+    if (STATS) { part[4 + (threadIdx.x >> 6)] = accp; part[8 + (threadIdx.x >> 6)] = accn; }
+  }
   __syncthreads();
   if (threadIdx.x == 0) {
     const float sum = (part[0] + part[1]) + (part[2] + part[3]);
     if (ORDERED) block[blockIdx.x] = sum;   // (block: the head's slots)
     else atomicAdd(block + 1, sum);
+    if (STATS) {
+      parts[2 * blockIdx.x] = (part[4] + part[5]) + (part[6] + part[7]);
+      parts[2 * blockIdx.x + 1] = (part[8] + part[9]) + (part[10] + part[11]);
+    }
   }
 }
 
-// positives counted, DIoU loss of the positive rows summed (forward: dpred == NULL), or its gradient written (backward)
 template <bool ORDERED>
-__global__ __launch_bounds__(256) void det_rows_kernel(const float* __restrict__ pred, const float* __restrict__ off, int n, float eps,
-                                                       float* __restrict__ block, const float* __restrict__ gout, float lambda_reg,
-                                                       float* __restrict__ dpred) {
-  float acc = 0.f, cnt = 0.f;
+__global__ __launch_bounds__(256) void det_focal_fwd_kernel(const float* __restrict__ x, const float* __restrict__ t, long long n, int C,
+                                                            const float* __restrict__ iou, float thr, float alpha, float gamma,
+                                                            float* __restrict__ block) {
+  det_focal_fwd_body<ORDERED, false>(x, t, n, C, iou, thr, alpha, gamma, block, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(256) void det_focal_fwd_stats_kernel(const float* __restrict__ x, const float* __restrict__ t, long long n, int C,
+                                                                  const float* __restrict__ iou, float thr, float alpha, float gamma,
+                                                                  float* __restrict__ block, const float* __restrict__ off,
+                                                                  float* __restrict__ parts) {
+  det_focal_fwd_body<true, true>(x, t, n, C, iou, thr, alpha, gamma, block, off, parts);
+}
+
+// positives counted, DIoU loss of the positive rows summed (forward: dpred == NULL), or its gradient written (backward)
+// STATS: the rows with iou >= 0 are counted beside the positives; nvalid: one count per wave
+template <bool ORDERED, bool STATS>
+__device__ __forceinline__ void det_rows_body(const float* __restrict__ pred, const float* __restrict__ off, int n, float eps,
+                                              float* __restrict__ block, const float* __restrict__ gout, float lambda_reg,
+                                              float* __restrict__ dpred, const float* __restrict__ iou, float* __restrict__ nvalid) {
+  float acc = 0.f, cnt = 0.f, val = 0.f;
   const float g = dpred ? (gout ? gout[0] : 1.f) * lambda_reg / block[4] : 0.f;
   for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < n; r += gridDim.x * blockDim.x) {
     float dl = 0.f, dr = 0.f;
+    if (STATS) val += iou[r] >= 0.f ? 1.f : 0.f;
     if (det_positive(off, r)) {
       cnt += 1.f;
       const float lp = pred[2 * r], rp = pred[2 * r + 1], lg = off[2 * r], rg = off[2 * r + 1];
@@ -311,17 +352,57 @@ __global__ __launch_bounds__(256) void det_rows_kernel(const float* __restrict__
         atomicAdd(block + 3, cnt);
       }
     }
+    if (STATS) {
+      val = wave_sum(val);
+      if ((threadIdx.x & 63) == 0) nvalid[blockIdx.x * 4 + (threadIdx.x >> 6)] = val;
+    }
   }
+}
+
+template <bool ORDERED>
+__global__ __launch_bounds__(256) void det_rows_kernel(const float* __restrict__ pred, const float* __restrict__ off, int n, float eps,
+                                                       float* __restrict__ block, const float* __restrict__ gout, float lambda_reg,
+                                                       float* __restrict__ dpred) {
+  det_rows_body<ORDERED, false>(pred, off, n, eps, block, gout, lambda_reg, dpred, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(256) void det_rows_stats_kernel(const float* __restrict__ pred, const float* __restrict__ off, int n, float eps,
+                                                             float* __restrict__ slots, const float* __restrict__ iou,
+                                                             float* __restrict__ nvalid) {
+  det_rows_body<true, true>(pred, off, n, eps, slots, nullptr, 0.f, nullptr, iou, nvalid);
 }
 
 // normaliser <- momentum * normaliser + (1 - momentum) * max(positives, 1)   (train.py:230: a running value across steps and sides);
 // loss = focal / (heads * normaliser) + lambda_reg * DIoU / normaliser   (no regression term without positives, train.py:277)
-__global__ void det_finish_kernel(float* __restrict__ block, float* __restrict__ normaliser, float momentum, float lambda_reg, int nheads) {
+__device__ __forceinline__ void det_finish_body(float* __restrict__ block, float* __restrict__ normaliser, float momentum, float lambda_reg,
+                                                int nheads) {
   const float npos = block[3];
   const float nm = momentum * normaliser[0] + (1.f - momentum) * fmaxf(npos, 1.f);
   normaliser[0] = nm;
   block[4] = nm;
   block[0] = block[1] / ((float)nheads * nm) + (npos > 0.f ? lambda_reg * block[2] / nm : 0.f);
+}
+
+__global__ void det_finish_kernel(float* __restrict__ block, float* __restrict__ normaliser, float momentum, float lambda_reg, int nheads) {
+  det_finish_body(block, normaliser, momentum, lambda_reg, nheads);
+}
+
+// the stats form's finish: det_finish_kernel's body, then the words a meter reads (TIMHIP_DET_STAT_*): the sums the finishing
+// block left in stats[0 .. VALID] divided as the loss divides them
+__global__ void det_finish_stats_kernel(float* __restrict__ block, float* __restrict__ normaliser, float momentum, float lambda_reg,
+                                        int nheads, float* __restrict__ stats) {
+  det_finish_body(block, normaliser, momentum, lambda_reg, nheads);
+  const float npos = block[3], nm = block[4];
+  stats[TIMHIP_DET_STAT_POSITIVES] = npos;
+  stats[TIMHIP_DET_STAT_DIOU_SUM] = block[2];
+  stats[TIMHIP_DET_STAT_NORMALISER] = nm;
+  stats[TIMHIP_DET_STAT_LOSS] = block[0];
+  stats[TIMHIP_DET_STAT_CLS] = block[1] / ((float)nheads * nm);
+  stats[TIMHIP_DET_STAT_REG] = npos > 0.f ? lambda_reg * block[2] / nm : 0.f;
+  for (int k = 0; k < 4; ++k) stats[TIMHIP_DET_STAT_HEAD + k] = stats[TIMHIP_DET_STAT_HEAD_SUM + k] / nm;
+  stats[TIMHIP_DET_STAT_POS] = stats[TIMHIP_DET_STAT_POS_SUM] / nm;
+  stats[TIMHIP_DET_STAT_NEG] = stats[TIMHIP_DET_STAT_NEG_SUM] / nm;
+  stats[TIMHIP_DET_STAT_RESERVED] = 0.f;
 }
 
 struct DetParts {
@@ -345,24 +426,61 @@ __device__ __forceinline__ float det_tree_sum(float v, float* sh) {
 // ONE block of 256 threads: thread t adds the slots t, t + 256, ... of every launch in ascending order, then the tree; the sums
 // go where the atomics would have left them and det_finish_kernel follows (the SAME kernel as in the atomic form: normaliser and
 // loss are then the same instructions on the sums)
-__global__ __launch_bounds__(256) void det_sum_ordered_kernel(float* __restrict__ block, const float* __restrict__ partials, const DetParts p,
-                                                              int nheads) {
+// STATS: the same slots also feed one accumulator per head, and the stats form's own slots (the last head's positive / negative
+// parts, the valid rows per wave) three more; these go through the wave sum and one LDS exchange - a fixed order too - and land in
+// stats[0 .. TIMHIP_DET_STAT_VALID], the words of absent heads as 0.  focal / diou / cnt are the ordered form's instructions
+template <bool STATS>
+__device__ __forceinline__ void det_sum_ordered_body(float* __restrict__ block, const float* __restrict__ partials, const DetParts& p,
+                                                     int nheads, float* __restrict__ stats) {
   __shared__ float sh[256];
+  __shared__ float ex[STATS ? 7 * 4 : 1];
   float focal = 0.f, diou = 0.f, cnt = 0.f;
+  float e[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // heads 0 .. 3, positive part, negative part, valid rows
   for (int k = 0; k < nheads; ++k)
     for (int j = threadIdx.x; j < p.focal[k]; j += 256) focal += partials[k * DET_PART_FOCAL + j];
   for (int j = threadIdx.x; j < p.rows * 4; j += 256) {
     diou += partials[DET_PART_ROWS0 + 2 * j];
     cnt += partials[DET_PART_ROWS0 + 2 * j + 1];
   }
+  if (STATS) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (k < nheads)
+        for (int j = threadIdx.x; j < p.focal[k]; j += 256) e[k] += partials[k * DET_PART_FOCAL + j];
+    if (nheads > 0)
+      for (int j = threadIdx.x; j < p.focal[nheads - 1]; j += 256) {
+        e[4] += partials[DET_PART_SPLIT0 + 2 * j];
+        e[5] += partials[DET_PART_SPLIT0 + 2 * j + 1];
+      }
+    for (int j = threadIdx.x; j < p.rows * 4; j += 256) e[6] += partials[DET_PART_VALID0 + j];
+  }
   focal = det_tree_sum(focal, sh);
   diou = det_tree_sum(diou, sh);
   cnt = det_tree_sum(cnt, sh);
+  if (STATS) {
+#pragma unroll
+    for (int q = 0; q < 7; ++q) {
+      e[q] = wave_sum(e[q]);
+      if ((threadIdx.x & 63) == 0) ex[q * 4 + (threadIdx.x >> 6)] = e[q];
+    }
+    __syncthreads();
+    if (threadIdx.x < 7) stats[threadIdx.x] = (ex[threadIdx.x * 4] + ex[threadIdx.x * 4 + 1]) + (ex[threadIdx.x * 4 + 2] + ex[threadIdx.x * 4 + 3]);
+  }
   if (threadIdx.x == 0) {
     block[1] = focal;
     block[2] = diou;
     block[3] = cnt;
   }
+}
+
+__global__ __launch_bounds__(256) void det_sum_ordered_kernel(float* __restrict__ block, const float* __restrict__ partials, const DetParts p,
+                                                              int nheads) {
+  det_sum_ordered_body<false>(block, partials, p, nheads, nullptr);
+}
+
+__global__ __launch_bounds__(256) void det_sum_stats_kernel(float* __restrict__ block, const float* __restrict__ partials, const DetParts p,
+                                                            int nheads, float* __restrict__ stats) {
+  det_sum_ordered_body<true>(block, partials, p, nheads, stats);
 }
 
 __global__ __launch_bounds__(256) void det_focal_bwd_kernel(const float* __restrict__ x, const float* __restrict__ t, long long n, int C,
@@ -426,12 +544,15 @@ int timhip_diou_1d(const float* pred_offsets, const float* target_offsets, int n
   return TIMHIP_OK;
 }
 
-// partials == NULL: the sums are added with atomics (timhip_det_side_loss_fwd); else into slots, added in a fixed order
+// partials == NULL: the sums are added with atomics (timhip_det_side_loss_fwd); else into slots, added in a fixed order;
+// stats != NULL (with partials): the stats arms of the ordered form's kernels (timhip_det_side_loss_fwd_stats)
 static int det_side_loss_fwd(const float* const* logits, const float* const* targets, const int* C, int nheads, int rows, const float* iou,
                              const float* offsets, const float* reg_pred, float iou_threshold, float alpha, float gamma, float eps,
-                             float lambda_reg, float momentum, float* normaliser, float* block, float* partials, void* stream) {
+                             float lambda_reg, float momentum, float* normaliser, float* block, float* partials, float* stats,
+                             void* stream) {
   if (!logits || !targets || !C || nheads < 1 || nheads > 4 || rows < 0 || !iou || !offsets || !reg_pred || !normaliser || !block)
     return TIMHIP_EINVAL;
+  if (stats && rows > (1 << 24)) return TIMHIP_EUNSUPPORTED;   // (the counts are carried as floats)
   for (int k = 0; k < nheads && rows > 0; ++k)     // every head is checked before the first launch: a refused call writes nothing
     if (!logits[k] || !targets[k] || C[k] <= 0) return TIMHIP_EINVAL;
   hipStream_t s = (hipStream_t)stream;
@@ -442,7 +563,10 @@ static int det_side_loss_fwd(const float* const* logits, const float* const* tar
       const long long n = (long long)rows * C[k];
       const int blocks = (int)((n + 255) / 256 > DET_PART_FOCAL ? DET_PART_FOCAL : (n + 255) / 256);   // one atomic per block on a single address
       parts.focal[k] = blocks;
-      if (partials)
+      if (stats && k == nheads - 1)
+        hipLaunchKernelGGL(det_focal_fwd_stats_kernel, dim3(blocks), dim3(256), 0, s, logits[k], targets[k], n, C[k], iou, iou_threshold,
+                           alpha, gamma, partials + k * DET_PART_FOCAL, offsets, partials + DET_PART_SPLIT0);
+      else if (partials)
         hipLaunchKernelGGL(det_focal_fwd_kernel<true>, dim3(blocks), dim3(256), 0, s, logits[k], targets[k], n, C[k], iou, iou_threshold,
                            alpha, gamma, partials + k * DET_PART_FOCAL);
       else
@@ -450,12 +574,21 @@ static int det_side_loss_fwd(const float* const* logits, const float* const* tar
                            alpha, gamma, block);
     }
     parts.rows = (rows + 255) / 256 > DET_PART_ROWS ? DET_PART_ROWS : (rows + 255) / 256;
-    if (partials)
+    if (stats)
+      hipLaunchKernelGGL(det_rows_stats_kernel, dim3(parts.rows), dim3(256), 0, s, reg_pred, offsets, rows, eps, partials + DET_PART_ROWS0, iou,
+                         partials + DET_PART_VALID0);
+    else if (partials)
       hipLaunchKernelGGL(det_rows_kernel<true>, dim3(parts.rows), dim3(256), 0, s, reg_pred, offsets, rows, eps, partials + DET_PART_ROWS0,
                          (const float*)nullptr, lambda_reg, (float*)nullptr);
     else
       hipLaunchKernelGGL(det_rows_kernel<false>, dim3(parts.rows), dim3(256), 0, s, reg_pred, offsets, rows, eps, block,
                          (const float*)nullptr, lambda_reg, (float*)nullptr);
+  }
+  if (stats) {
+    hipLaunchKernelGGL(det_sum_stats_kernel, dim3(1), dim3(256), 0, s, block, (const float*)partials, parts, nheads, stats);
+    hipLaunchKernelGGL(det_finish_stats_kernel, dim3(1), dim3(1), 0, s, block, normaliser, momentum, lambda_reg, nheads, stats);
+    TIM_CHECK_LAUNCH();
+    return TIMHIP_OK;
   }
   if (partials) hipLaunchKernelGGL(det_sum_ordered_kernel, dim3(1), dim3(256), 0, s, block, (const float*)partials, parts, nheads);
   hipLaunchKernelGGL(det_finish_kernel, dim3(1), dim3(1), 0, s, block, normaliser, momentum, lambda_reg, nheads);
@@ -468,7 +601,7 @@ int timhip_det_side_loss_fwd(const float* const* logits, const float* const* tar
                              float gamma, float eps, float lambda_reg, float momentum, float* normaliser, float* block,
                              void* stream) {
   return det_side_loss_fwd(logits, targets, C, nheads, rows, iou, offsets, reg_pred, iou_threshold, alpha, gamma, eps, lambda_reg, momentum,
-                           normaliser, block, nullptr, stream);
+                           normaliser, block, nullptr, nullptr, stream);
 }
 
 int timhip_det_side_loss_fwd_ordered(const float* const* logits, const float* const* targets, const int* C, int nheads, int rows,
@@ -477,7 +610,16 @@ int timhip_det_side_loss_fwd_ordered(const float* const* logits, const float* co
                                      float* partials, void* stream) {
   if (!partials) return TIMHIP_EINVAL;
   return det_side_loss_fwd(logits, targets, C, nheads, rows, iou, offsets, reg_pred, iou_threshold, alpha, gamma, eps, lambda_reg, momentum,
-                           normaliser, block, partials, stream);
+                           normaliser, block, partials, nullptr, stream);
+}
+
+int timhip_det_side_loss_fwd_stats(const float* const* logits, const float* const* targets, const int* C, int nheads, int rows,
+                                   const float* iou, const float* offsets, const float* reg_pred, float iou_threshold, float alpha,
+                                   float gamma, float eps, float lambda_reg, float momentum, float* normaliser, float* block,
+                                   float* partials, float* stats, void* stream) {
+  if (!partials || !stats) return TIMHIP_EINVAL;
+  return det_side_loss_fwd(logits, targets, C, nheads, rows, iou, offsets, reg_pred, iou_threshold, alpha, gamma, eps, lambda_reg, momentum,
+                           normaliser, block, partials, stats, stream);
 }
 
 int timhip_det_side_loss_bwd(const float* const* logits, const float* const* targets, const int* C, int nheads, int rows,

@@ -449,7 +449,7 @@ def ctr_diou_loss_1d(input_offsets, target_offsets, reduction: str = "none", eps
 class _DetSideLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, aux, iou, offsets, reg_pred, *logits):
-        targets, normaliser, thr, alpha, gamma, eps, lam, mom, ordered = aux
+        targets, normaliser, thr, alpha, gamma, eps, lam, mom, ordered, stats = aux
         _require_gpu(reg_pred, "detection side loss")
         dev = reg_pred.device
         xs = [_f32c(x) for x in logits]
@@ -469,7 +469,10 @@ class _DetSideLossFn(torch.autograd.Function):
         pa = lambda ts_: (C.c_void_p * len(ts_))(*[ptr(t) for t in ts_])   # noqa: E731
         args = (pa(xs), pa(ts), Cs, len(xs), rows, ptr(u), ptr(off), ptr(rp), float(thr), float(alpha), float(gamma), float(eps), float(lam),
                 float(mom), ptr(normaliser), ptr(block))
-        if ordered:
+        if stats is not None:
+            partials = torch.empty(L.DET_SIDE_STATS_PARTIALS, dtype=torch.float32, device=dev)
+            call("timhip_det_side_loss_fwd_stats", *args, ptr(partials), ptr(stats), _stream())
+        elif ordered:
             partials = torch.empty(L.DET_SIDE_PARTIALS, dtype=torch.float32, device=dev)
             call("timhip_det_side_loss_fwd_ordered", *args, ptr(partials), _stream())
         else:
@@ -496,7 +499,7 @@ class _DetSideLossFn(torch.autograd.Function):
 
 
 def detection_side_loss(cls_logits, cls_targets, reg_pred, offsets, iou, normaliser, iou_threshold, lambda_reg=0.5, momentum=0.9,
-                        alpha=0.25, gamma=2.0, eps=1e-8, ordered=False):
+                        alpha=0.25, gamma=2.0, eps=1e-8, ordered=False, stats=None):
     """One modality side of the detection training loss, det scripts/train.py:222-349, as a handful of launches:
 
         valid_cls = iou >= 0;  w = where(iou < iou_threshold, 1, iou);  positive = offsets[:, 0] != inf
@@ -510,12 +513,20 @@ def detection_side_loss(cls_logits, cls_targets, reg_pred, offsets, iou, normali
     (timhip_det_side_loss_fwd / _bwd).  Gradients flow to the logits and to reg_pred.
 
     ordered=True: the sums are added in a fixed order (timhip_det_side_loss_fwd_ordered) instead of with float atomics - one input
-    gives the same loss bits in every run, eager or replayed; the value differs from the default form's by rounding only."""
+    gives the same loss bits in every run, eager or replayed; the value differs from the default form's by rounding only.
+
+    stats: a float32 GPU tensor of `_lib.DET_SIDE_STATS_WORDS` elements (`DetectionMeter.side_stats()`): the side statistics a
+    detection meter reads are written into it (timhip_det_side_loss_fwd_stats: per-head sums, the last head's positive / negative
+    parts, the counts, each divided as the loss divides).  It implies the ordered sums; the loss and the gradients are those of
+    ordered=True to the bit."""
     if not isinstance(cls_logits, (list, tuple)):
         cls_logits, cls_targets = [cls_logits], [cls_targets]
     if normaliser.dtype != torch.float32 or normaliser.numel() != 1 or not normaliser.is_cuda:
         raise ValueError("normaliser: a float32 scalar tensor on the GPU (it is advanced in place)")
-    aux = (list(cls_targets), normaliser, iou_threshold, alpha, gamma, eps, lambda_reg, momentum, bool(ordered))
+    if stats is not None and (not torch.is_tensor(stats) or stats.dtype != torch.float32 or not stats.is_cuda
+                              or stats.numel() != L.DET_SIDE_STATS_WORDS or not stats.is_contiguous()):
+        raise ValueError("stats: a contiguous float32 tensor of %d elements on the GPU" % L.DET_SIDE_STATS_WORDS)
+    aux = (list(cls_targets), normaliser, iou_threshold, alpha, gamma, eps, lambda_reg, momentum, bool(ordered), stats)
     return _DetSideLossFn.apply(aux, iou, offsets, reg_pred, *cls_logits)
 
 

@@ -19,7 +19,10 @@ Two recorded deviations:
      tensors.  Here the sums are doubles and the counts int64: what the class computes from the Python numbers its signature
      suggests.
 
-Out of scope: the detection meters, the timers, the RAM / GPU probes and a cross-rank reduction of the state.
+Out of scope: the timers, the RAM / GPU probes and a cross-rank reduction of the state.
+
+`DetectionMeter` is the detection counterpart: the eleven loss averages of the reference's detection `TrainMeter`
+and `InferenceMeter`, fed by the side statistics `detection_side_loss(..., stats=)` leaves on the device.
 """
 import ctypes
 
@@ -271,3 +274,180 @@ class TrainMeter:
                     dst.copy_(src)
                 g.labels.copy_(sd[name]["labels"])
                 g.touched.copy_(sd[name]["touched"])
+
+
+# ================================================================================================ detection
+DET_SLOTS = ("total", "drloc", "visual", "verb", "noun", "action", "visual_reg", "audio", "audio_reg", "positive", "negative")
+DET_SIDES = ("visual", "audio")
+# the reference's get_train_stats() / get_val_epoch_stats() names (detection utils/meters.py:139-179, :492-524); "Train/loss" and
+# "Val/loss" are ours: the reference prints the total only in its message lines.  The positive / negative averages are ONE pair of
+# meters that both modalities feed; the reference reports it under both modalities' names
+_DET_KEYS = {
+    "train": {"total": ("Train/loss",), "drloc": ("Train/drloc_loss",), "visual": ("Train/visual_loss",), "verb": ("Train/verb/visual_loss",),
+              "noun": ("Train/noun/visual_loss",), "action": ("Train/visual_action_loss",), "visual_reg": ("Train/visual_reg_loss",),
+              "audio": ("Train/audio_loss",), "audio_reg": ("Train/audio_reg_loss",),
+              "positive": ("Train/visual_positive_loss", "Train/audio_positive_loss"),
+              "negative": ("Train/visual_negative_loss", "Train/audio_negative_loss")},
+    "val": {"total": ("Val/loss",), "visual": ("Val/visual/loss",), "verb": ("Val/visual/verb_loss",), "noun": ("Val/visual/noun_loss",),
+            "action": ("Val/visual/action_loss",), "visual_reg": ("Val/visual/reg_loss",), "audio": ("Val/audio/loss",),
+            "audio_reg": ("Val/audio/reg_loss",), "positive": ("Val/visual/positive_loss", "Val/audio/positive_loss"),
+            "negative": ("Val/visual/negative_loss", "Val/audio/negative_loss")},
+}
+
+
+def decode_det_state(words):
+    """the detection state block (int32 view, `_lib.DET_METER_STATE_WORDS` words, on the host) -> the dict `DetectionMeter.read()`
+    returns"""
+    w = np.ascontiguousarray(np.asarray(words).reshape(-1)).view(np.int32)
+    if w.size != L.DET_METER_STATE_WORDS:
+        raise ValueError("a detection meter state block holds %d words, got %d" % (L.DET_METER_STATE_WORDS, w.size))
+    q64, f64, f32 = w[:L.DET_METER_VAL].view(np.int64), w[:L.DET_METER_VAL].view(np.float64), w.view(np.float32)
+    out = {"updates": int(q64[L.DET_METER_UPDATES // 2]), "losses": {}, "sides": {}}
+    for s, name in enumerate(DET_SLOTS):
+        total, count = float(f64[(L.DET_METER_SUM + 4 * s) // 2]), int(q64[(L.DET_METER_COUNT + 4 * s) // 2])
+        out["losses"][name] = {"avg": total / count if count else 0.0, "val": float(f32[L.DET_METER_VAL + s]), "count": count,
+                               "sum": total}
+    for s, name in enumerate(DET_SIDES):
+        valid, pos = (int(q64[(L.DET_METER_RUN + 4 * s + 2 * k) // 2]) for k in range(2))
+        out["sides"][name] = {"valid": valid, "positives": pos, "batch_valid": int(w[L.DET_METER_LAST + 2 * s]),
+                              "batch_positives": int(w[L.DET_METER_LAST + 2 * s + 1]), "normaliser": float(f32[L.DET_METER_NORM + s])}
+    return out
+
+
+class DetectionMeter:
+    """The loss averages of a detection training or validation run, on the device: the reference's detection `TrainMeter`
+    (mode="train") and `InferenceMeter` (mode="val"), detection/time_interval_machine/utils/meters.py:29-315, :317-572.
+
+        meter = DetectionMeter("audio_visual", include_verb_noun=True)
+        # inside the (captured) iteration:
+        lv = detection_side_loss(..., stats=meter.side_stats("visual"))
+        la = detection_side_loss(..., stats=meter.side_stats("audio"))
+        loss = lv + lambda_audio * la + lambda_drloc * drloc
+        meter.update(loss, drloc)
+        # at print_freq, outside:
+        s = meter.stats(lr, iters)      # one copy of the block
+
+    The side losses leave their statistics in the meter's two fixed tensors (timhip_det_side_loss_fwd_stats: no second pass over
+    the logits); `update()` is ONE launch of one block (timhip_det_meter_update) that folds them and the two loss scalars into
+    the state block in the reference's order, sums in double, counts in int64.  Nothing synchronises; `read()` is one copy of
+    `_lib.DET_METER_STATE_WORDS` words.  A side whose loss did not run since the last update is read again as it stands: run every
+    side of `modality` before every update.
+
+    Every value is its own side's, divided by that side's normaliser.  With one modality these are the reference's numbers; with
+    two, the reference divides the visual per-head sums by the normaliser the audio side has advanced and hands the audio side's
+    positive / negative loss to the meter twice (det scripts/train.py:416-418, :325-326): accidents of variable reuse that are not
+    reproduced.  Positive and negative are taken among the rows with iou >= 0 (the reference's mask indexing raises when a row has
+    iou < 0).  Out of scope: timers, RAM / GPU probes, message strings, a cross-rank reduction."""
+
+    def __init__(self, modality="audio_visual", include_verb_noun=True, include_dr_loc=True, mode="train", device="cuda"):
+        if not torch.cuda.is_available():
+            raise L.TimHipError("DetectionMeter needs the MI355X (no CPU fallback)")
+        if mode not in ("train", "val"):
+            raise ValueError('mode is "train" or "val", not %r' % (mode,))
+        L.load()
+        self.device = torch.device(device)
+        self.modality, self.mode = modality, mode
+        self.sides = tuple(s for s in DET_SIDES if s in modality)
+        if not self.sides:
+            raise ValueError("modality %r names neither visual nor audio" % (modality,))
+        self.include_verb_noun = bool(include_verb_noun)
+        self.include_dr_loc = bool(include_dr_loc) and mode == "train"
+        self.state = torch.zeros((L.DET_METER_STATE_WORDS // 2,), dtype=torch.int64, device=self.device)     # 8-byte aligned words
+        self._stats = {s: torch.zeros((L.DET_SIDE_STATS_WORDS,), dtype=torch.float32, device=self.device) for s in self.sides}
+        self._sides = (ctypes.c_void_p * 2)(*[ptr(self._stats.get(s)) for s in DET_SIDES])
+        self.best_vis_loss = self.best_aud_loss = float("inf")
+        self.last_best_epoch = None
+
+    def side_stats(self, side):
+        """the fixed tensor to hand to `detection_side_loss(..., stats=)` for "visual" / "audio" """
+        if side not in self._stats:
+            raise ValueError("this meter (modality %r) has no %r side" % (self.modality, side))
+        return self._stats[side]
+
+    @staticmethod
+    def _scalar(t, what):
+        if t is None:
+            return None
+        require_gpu(t, ("DetectionMeter.update", "the detection meter runs"), what)
+        if t.numel() != 1:
+            raise ValueError("%s holds %d values, not one" % (what, t.numel()))
+        t = t.detach().reshape(1)
+        return t if t.dtype == torch.float32 else t.to(torch.float32)
+
+    def update(self, loss, drloc_loss=None):
+        """one iteration: one launch, nothing is read back.  loss / drloc_loss: 1-element device tensors (None counts as 0)"""
+        total, drloc = self._scalar(loss, "loss"), self._scalar(drloc_loss, "drloc_loss")
+        call("timhip_det_meter_update", ptr(self.state), ctypes.addressof(self._sides), 3 if self.include_verb_noun else 1, ptr(total),
+             ptr(drloc), _stream())
+
+    # ---- results -----------------------------------------------------------------------------------------------------------
+    def read(self):
+        """the block, through ONE device-to-host copy, as plain Python numbers:
+            {"updates", "losses": {slot: {"avg", "val", "count", "sum"}}, "sides": {side: {"valid", "positives", "batch_valid",
+             "batch_positives", "normaliser"}}};  slot in DET_SLOTS.  A slot that never counted reports 0."""
+        return decode_det_state(self.state.cpu().numpy())
+
+    def _slots(self):
+        use = ["total"] + (["drloc"] if self.include_dr_loc else [])
+        if "visual" in self.sides:
+            use += (["verb", "noun"] if self.include_verb_noun else []) + ["visual", "action", "visual_reg"]
+        if "audio" in self.sides:
+            use += ["audio", "audio_reg"]
+        return use + ["positive", "negative"]
+
+    def stats(self, lr=None, training_iterations=None):
+        """`read()` under the reference's key names: get_train_stats() (meters.py:139-179) in train mode, get_val_epoch_stats()
+        (:492-524) in val mode.  In train mode also "Train/normaliser" (the last side's), "Train/positives", "Train/negatives"
+        and "Train/positive_ratio" of the last batch, from the block's counters, summed over the sides."""
+        s = self.read()
+        out, keys = {}, _DET_KEYS[self.mode]
+        if lr is not None and self.mode == "train":
+            out["Train/lr"] = lr
+        if training_iterations is not None:
+            out["train_step" if self.mode == "train" else "val_step"] = training_iterations
+        for name in self._slots():
+            for i, key in enumerate(keys[name]):
+                if len(keys[name]) == 1 or DET_SIDES[i] in self.sides:
+                    out[key] = s["losses"][name]["avg"]
+        if self.mode == "train":
+            pos = sum(s["sides"][k]["batch_positives"] for k in self.sides)
+            neg = sum(s["sides"][k]["batch_valid"] for k in self.sides) - pos
+            out["Train/normaliser"] = s["sides"][self.sides[-1]]["normaliser"]
+            out["Train/positives"], out["Train/negatives"] = pos, neg
+            out["Train/positive_ratio"] = pos / (pos + neg) if pos + neg else 0.0
+        return out
+
+    def update_epoch(self, epoch):
+        """the InferenceMeter's best-loss bookkeeping (meters.py:425-444) on the host after one `read()`: (best_loss, is_best)
+        with best_loss the two best losses BEFORE this epoch and is_best "none" / "visual" / "audio" / "audio_visual".  As in
+        the reference an absent modality's average is 0.0, which is a best loss once."""
+        s = self.read()["losses"]
+        vis, aud = s["visual"]["avg"], s["audio"]["avg"]
+        is_best_visual, is_best_audio = vis < self.best_vis_loss, aud < self.best_aud_loss
+        best_loss = {"visual": self.best_vis_loss, "audio": self.best_aud_loss}
+        is_best = "none"
+        if is_best_visual:
+            is_best = "visual"
+            self.best_vis_loss = min(vis, self.best_vis_loss)
+            self.last_best_epoch = epoch
+        if is_best_audio:
+            is_best = "audio_" + is_best if "visual" in is_best else "audio"
+            self.best_aud_loss = min(aud, self.best_aud_loss)
+            self.last_best_epoch = epoch
+        return best_loss, is_best
+
+    def reset(self):
+        """zeroes the block; the best losses stay"""
+        self.state.zero_()
+
+    # ---- checkpoint --------------------------------------------------------------------------------------------------------
+    def state_dict(self):
+        return {"state": self.state.cpu(), "best_vis_loss": self.best_vis_loss, "best_aud_loss": self.best_aud_loss,
+                "last_best_epoch": self.last_best_epoch}
+
+    def load_state_dict(self, sd):
+        if tuple(sd["state"].shape) != tuple(self.state.shape):
+            raise ValueError("the checkpoint's state block has shape %s, this meter's %s" % (tuple(sd["state"].shape), tuple(self.state.shape)))
+        self.state.copy_(sd["state"])
+        self.best_vis_loss, self.best_aud_loss = float(sd["best_vis_loss"]), float(sd["best_aud_loss"])
+        self.last_best_epoch = sd["last_best_epoch"]

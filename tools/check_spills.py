@@ -54,6 +54,10 @@ BUDGET = {
     "recog.hip": [(r"rec_eid_kernel", 0), (r"rec_link_kernel", 0), (r"rec_accumulate_kernel", 0), (r"rec_finalize_kernel", 0),
                   (r"rec_counts_kernel", 0), (r"rec_combined_kernel", 0)],   # streaming: the logits once, the accumulator chunk once in and once out
     "meter.hip": [(r"meter_rank_kernel", 0), (r"meter_finish_kernel", 0)],   # streaming: a segment's 16 dwords per lane and 17 counters live in registers
+    # the detection side loss: streaming over the logits and targets once; the stats arm keeps two more accumulators per thread
+    "losses.hip": [(r"det_focal_fwd_stats_kernel", 0), (r"det_focal_fwd_kernel", 0), (r"det_rows_stats_kernel", 0), (r"det_rows_kernel", 0),
+                   (r"det_sum_stats_kernel", 0), (r"det_sum_ordered_kernel", 0), (r"det_finish_stats_kernel", 0)],
+    "det_meter.hip": [(r"det_meter_kernel", 0)],   # one thread's arithmetic on a block staged in LDS
     # one block per CU-sized LDS image (128 KiB of staged cells at Cv = 1024): 86 (forward) / 132-176 (backward) VGPRs of the 512 a
     # wave may have at that occupancy - nothing forces a spill, and scratch traffic would sit inside the MFMA loops
     "avga.hip": [(r"avga_kernel", 0), (r"avga_zero_kernel", 0), (r"avga_audio_kernel", 0)],   # (the last two: a fill and a cast)
