@@ -10,7 +10,10 @@ front of every replay.  Here both live inside the captured step:
     drloc_pos.draw()         one launch: the DRLoc sample positions and their normalised distance
     mix.draw(), mix.mix(...), encoder, cross entropies, DRLoc, backward, FusedAdamW      as before
 
-    python examples/train_graphed_device_data_synthetic.py [--steps 20] [--batch 8] [--precision fp16]
+    python examples/train_graphed_device_data_synthetic.py [--steps 20] [--batch 8] [--precision fp16] [--store-dtype fp32]
+
+--store-dtype fp16 | bf16 holds the feature stores in that type (half the bytes; batches stay fp32, every element the exact
+widening of the stored one).  With the type the model's --precision rounds its inputs to, the forward sees the same operands.
 
 prints window numbers, lam and loss per replay: they change every step, and a second run with the same --seed prints the same
 windows and lam.
@@ -33,6 +36,8 @@ from tim_amd.mixup import Mixup  # noqa: E402
 from tim_amd.optim import FusedAdamW  # noqa: E402
 from tim_amd.tim import TIM  # noqa: E402
 
+STORE_DTYPES = {"fp32": torch.float32, "fp16": torch.float16, "bf16": torch.bfloat16}
+
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
@@ -43,6 +48,7 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0, help="seed of the batch order, mixup and DRLoc draws")
     ap.add_argument("--rank", type=int, default=0, help="data parallel: this rank's shard of every epoch's order")
     ap.add_argument("--world", type=int, default=1)
+    ap.add_argument("--store-dtype", choices=sorted(STORE_DTYPES), default="fp32", help="element type of the feature stores in device memory")
     args = ap.parse_args(argv)
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
@@ -54,7 +60,7 @@ def main(argv=None):
     model.load_state_dict({k: torch.from_numpy(v) for k, v in synth.make_state_dict(cfg, seed=0).items()})
     model = model.to(dev).train()
     opt = FusedAdamW.for_model(model, lr=args.lr, weight_decay=1e-4, max_grad_norm=1.0)
-    ds = synthetic_dataset(cfg, 4, 64, nv, na, dev, seed=0)
+    ds = synthetic_dataset(cfg, 4, 64, nv, na, dev, seed=0, store_dtype=STORE_DTYPES[args.store_dtype])
     # every rank walks the SAME shuffled order (one seed) and takes its own share; mixup and DRLoc draw per rank
     smp = ds.sampler(args.batch, seed=args.seed, shuffle=True, rank=args.rank, world=args.world)
     mix = Mixup(args.batch, alpha=0.2, device=dev, seed=args.seed + args.rank)

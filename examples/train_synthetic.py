@@ -26,8 +26,9 @@ from tim_amd.data import DeviceWindowDataset  # noqa: E402
 from tim_amd.tim import TIM  # noqa: E402
 
 
-def synthetic_dataset(cfg, n_videos, n_windows, nv, na, dev, seed=0):
-    """in-memory tables in the reference dataset's format (see tests/golden/batch_inputs.py)"""
+def synthetic_dataset(cfg, n_videos, n_windows, nv, na, dev, seed=0, store_dtype=torch.float32):
+    """in-memory tables in the reference dataset's format (see tests/golden/batch_inputs.py); store_dtype: the element type the
+    feature stores are held in on the device"""
     rs = np.random.RandomState(seed)
     nf = cfg.num_feats
     vids = ["vid%02d" % i for i in range(n_videos)]
@@ -48,7 +49,8 @@ def synthetic_dataset(cfg, n_videos, n_windows, nv, na, dev, seed=0):
         windows.append({"video_id": vids[i % n_videos], "start_sec": start, "feat_indices": np.arange(first, first + 2 * nf, 2),
                         "v_queries": q(kv), "v_labels": vl.astype(np.int64), "v_action_ids": np.arange(kv), "v_narration_ids": [""] * kv,
                         "a_queries": q(ka), "a_labels": al.astype(np.int64), "a_action_ids": np.arange(ka), "a_narration_ids": [""] * ka})
-    return DeviceWindowDataset(windows, nf, nf * 0.4, nv, na, "audio_visual", vf, {v: ft for v in vids}, af, {v: ft for v in vids}, dev)
+    return DeviceWindowDataset(windows, nf, nf * 0.4, nv, na, "audio_visual", vf, {v: ft for v in vids}, af, {v: ft for v in vids}, dev,
+                               store_dtype=store_dtype)
 
 
 def main(argv=None):

@@ -1248,6 +1248,27 @@ typedef struct TimDetWindowBatch {
 } TimDetWindowBatch;
 int timhip_det_window_batch(const TimDetWindowBatch* desc, void* stream);
 
+/* 16-bit feature stores (additive to ABI 6).  The three feature movers above with the element type of the visual and of the
+ * audio store named beside their arguments: under these entries feats / v_feats / a_feats point at elements of that type (the
+ * descriptors keep their layout and their `const float*` fields; every other table and every output is what it is above).
+ *   TIMHIP_STORE_F32    the entries above: with fp32 for every store a call runs the same kernel and writes the same bits
+ *   TIMHIP_STORE_F16    IEEE binary16; the fp32 output element is the exact widening of the stored value, subnormals honoured
+ *                       (not flushed), +-0 and +-inf kept, a NaN stays a NaN
+ *   TIMHIP_STORE_BF16   the upper half of an fp32 word; the fp32 output element is the stored word shifted left by 16 bits
+ * A 16-bit row moves in 16-byte chunks of 8 elements, each becoming two 16-byte fp32 stores, where the width is a multiple of 8
+ * and source row and destination row are 16-byte aligned; element by element otherwise.  Times, segments, labels, ids, window
+ * start, video index, the rows with valid[b] == 0 and the reading of a window or augmentation word outside its table as 0 are
+ * the code of the entries above.  The store type of an absent modality (NULL feats) is checked against the enum and otherwise
+ * unused.  TIMHIP_EINVAL on a store type outside the enum, TIMHIP_EALIGN on a 16-bit store pointer off 2 bytes, and every refusal
+ * of the entry above (an fp32 store pointer off 4 bytes among them: the gather entry has no alignment refusal for fp32); a
+ * refused call launches nothing. */
+enum { TIMHIP_STORE_F32 = 0, TIMHIP_STORE_F16 = 1, TIMHIP_STORE_BF16 = 2 };
+int timhip_window_gather_st(const void* feats, int store, int C, int num_aug, const int64_t* video_row0,
+                            const int32_t* feat_indices, int num_feats, const int32_t* windows, int B,
+                            const int32_t* aug_indices, float* out, void* stream);
+int timhip_window_batch_st(const TimWindowBatch* desc, int v_store, int a_store, void* stream);
+int timhip_det_window_batch_st(const TimDetWindowBatch* desc, int v_store, int a_store, void* stream);
+
 /* DRLoc sample positions (reference helpers/losses/drloc.py:4-7) from a device counter of their own: one block reads the counter
  * (c), stores c + 1 and writes draw c.  pos_1, pos_2 int64 [n, m] in [0, l): (uint64(word) * l) >> 32, element i = row * m + col
  * reading words (x, y) of the Philox block with key = seed, site = SITE_DRLOC (10), counter ((c mod 2^40) << 24) | (i >> 1) when

@@ -25,6 +25,7 @@ MIXUP_ALPHA_MIN, MIXUP_ALPHA_MAX, MIXUP_MAX_TENSORS = 0.05, 16.0, 4   # include/
 SITE_SAMPLER, SITE_DRLOC = 9, 10   # sampler.hip: the batch order with its augmentation indices, the DRLoc positions (as SITE_MIXUP)
 SAMPLER_WRAP, SAMPLER_DROP, SAMPLER_MAX_AUG, DRLOC_MAX_SAMPLES = 0, 1, 1 << 24, 1 << 25   # include/timhip.h: TIMHIP_SAMPLER_*, TIMHIP_DRLOC_*
 SAMPLER_EPOCH_BITS = 23            # the epoch enters the permutation's Philox counter modulo 2^23
+STORE_F32, STORE_F16, STORE_BF16 = 0, 1, 2   # include/timhip.h: TIMHIP_STORE_* (the element type of a feature store)
 SITE_L_ATTN, SITE_L_DROP1, SITE_L_FFN, SITE_L_DROP2 = 0, 1, 2, 3
 
 
@@ -257,6 +258,9 @@ _SIGS = {
     "timhip_sampler_draw": (C.c_int, [u64, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
     "timhip_window_batch": (C.c_int, [C.POINTER(TimWindowBatch), vp]),
     "timhip_det_window_batch": (C.c_int, [C.POINTER(TimDetWindowBatch), vp]),
+    "timhip_window_gather_st": (C.c_int, [vp, i32, i32, i32, vp, vp, i32, vp, i32, vp, vp, vp]),
+    "timhip_window_batch_st": (C.c_int, [C.POINTER(TimWindowBatch), i32, i32, vp]),
+    "timhip_det_window_batch_st": (C.c_int, [C.POINTER(TimDetWindowBatch), i32, i32, vp]),
     "timhip_drloc_draw": (C.c_int, [u64, vp, i32, i32, i32, vp, vp, vp, vp]),
     "timhip_gemm_timing_start": (C.c_int, [i32, C.c_double]),
     "timhip_gemm_timing_stop": (C.c_int, [vp, vp, vp]),

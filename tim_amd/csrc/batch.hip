@@ -9,21 +9,34 @@
 
 namespace {
 
-__global__ __launch_bounds__(256) void window_gather_kernel(const float* __restrict__ feats, int C, int num_aug,
+// ST: the element type of the store (TIMHIP_STORE_*); a 16-bit row moves 8 elements to the 16-byte load, widened exactly
+template <int ST>
+__global__ __launch_bounds__(256) void window_gather_kernel(const void* __restrict__ feats, int C, int num_aug,
                                                             const long long* __restrict__ video_row0,
                                                             const int* __restrict__ feat_idx, int nf,
                                                             const int* __restrict__ win, const int* __restrict__ aug,
                                                             float* __restrict__ out) {
+  typedef StoreT<ST> S;
+  constexpr int E = S::CHUNK;
   const int r = blockIdx.x;            // b * nf + j
   const int b = r / nf, j = r % nf;
   const int w = win[b];
   const long long row = (video_row0[w] + feat_idx[(size_t)w * nf + j]) * num_aug + (aug ? aug[r] : 0);
-  const float* src = feats + (size_t)row * C;
+  const typename S::T* src = reinterpret_cast<const typename S::T*>(feats) + (size_t)row * C;
   float* dst = out + (size_t)r * C;
-  if ((C & 3) == 0 && (((uintptr_t)src | (uintptr_t)dst) & 15) == 0) {
-    for (int c = threadIdx.x * 4; c < C; c += 256 * 4) *reinterpret_cast<float4*>(dst + c) = *reinterpret_cast<const float4*>(src + c);
+  if ((C & (E - 1)) == 0 && (((uintptr_t)src | (uintptr_t)dst) & 15) == 0) {
+    if constexpr (ST == TIMHIP_STORE_F32) {
+      for (int c = threadIdx.x * 4; c < C; c += 256 * 4) *reinterpret_cast<float4*>(dst + c) = *reinterpret_cast<const float4*>(src + c);
+    } else {
+      for (int c = threadIdx.x * 8; c < C; c += 256 * 8) {
+        f32x4_t lo, hi;
+        widen8<ST>(*reinterpret_cast<const u32x4_t*>(src + c), lo, hi);
+        *reinterpret_cast<f32x4_t*>(dst + c) = lo;
+        *reinterpret_cast<f32x4_t*>(dst + c + 4) = hi;
+      }
+    }
   } else {
-    for (int c = threadIdx.x; c < C; c += 256) dst[c] = src[c];
+    for (int c = threadIdx.x; c < C; c += 256) dst[c] = S::widen(src[c]);
   }
 }
 
@@ -61,16 +74,25 @@ __global__ void window_times_kernel(const float* __restrict__ v_ft, int v_ld, co
 
 extern "C" {
 
+int timhip_window_gather_st(const void* feats, int store, int C, int num_aug, const int64_t* video_row0,
+                            const int32_t* feat_indices, int num_feats, const int32_t* windows, int B,
+                            const int32_t* aug_indices, float* out, void* stream) {
+  if (!feats || !video_row0 || !feat_indices || !windows || !out || C <= 0 || num_aug <= 0 || num_feats <= 0 || B < 0)
+    return TIMHIP_EINVAL;
+  if (!valid_store(store)) return TIMHIP_EINVAL;
+  if (store != TIMHIP_STORE_F32 && (((uintptr_t)feats) & 1)) return TIMHIP_EALIGN;
+  if (B == 0) return TIMHIP_OK;
+  DISPATCH_STORE(store, hipLaunchKernelGGL(window_gather_kernel<ST>, dim3(B * num_feats), dim3(256), 0, (hipStream_t)stream, feats, C,
+                                           num_aug, (const long long*)video_row0, feat_indices, num_feats, windows, aug_indices, out));
+  TIM_CHECK_LAUNCH();
+  return TIMHIP_OK;
+}
+
 int timhip_window_gather(const float* feats, int C, int num_aug, const int64_t* video_row0, const int32_t* feat_indices,
                          int num_feats, const int32_t* windows, int B, const int32_t* aug_indices, float* out,
                          void* stream) {
-  if (!feats || !video_row0 || !feat_indices || !windows || !out || C <= 0 || num_aug <= 0 || num_feats <= 0 || B < 0)
-    return TIMHIP_EINVAL;
-  if (B == 0) return TIMHIP_OK;
-  hipLaunchKernelGGL(window_gather_kernel, dim3(B * num_feats), dim3(256), 0, (hipStream_t)stream, feats, C, num_aug,
-                     (const long long*)video_row0, feat_indices, num_feats, windows, aug_indices, out);
-  TIM_CHECK_LAUNCH();
-  return TIMHIP_OK;
+  return timhip_window_gather_st(feats, TIMHIP_STORE_F32, C, num_aug, video_row0, feat_indices, num_feats, windows, B, aug_indices,
+                                 out, stream);
 }
 
 int timhip_window_times(const float* v_feat_times, int v_ld, const int64_t* v_row0, const float* a_feat_times, int a_ld,

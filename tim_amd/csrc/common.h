@@ -56,6 +56,44 @@ template <> struct OpT<f16_t> {
   static __device__ __forceinline__ f16_t from_f(float v) { return (f16_t)v; }
 };
 
+// feature-store element types (TIMHIP_STORE_*; batch.hip, sampler.hip): T = the stored element, CHUNK = elements of a 16-byte
+// chunk, widen = the exact fp32 value of a stored element (fp16: v_cvt_f32_f16, which honours fp16 subnormals in the default
+// kernel mode; bf16: the word moved to the upper half)
+template <int ST> struct StoreT;
+template <> struct StoreT<TIMHIP_STORE_F32> {
+  typedef float T;
+  static constexpr int CHUNK = 4;
+  static __device__ __forceinline__ float widen(float v) { return v; }
+};
+template <> struct StoreT<TIMHIP_STORE_F16> {
+  typedef uint16_t T;
+  static constexpr int CHUNK = 8;
+  static __device__ __forceinline__ float widen(uint16_t h) { return (float)__builtin_bit_cast(f16_t, h); }
+};
+template <> struct StoreT<TIMHIP_STORE_BF16> {
+  typedef uint16_t T;
+  static constexpr int CHUNK = 8;
+  static __device__ __forceinline__ float widen(uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
+};
+static inline bool valid_store(int st) { return st >= TIMHIP_STORE_F32 && st <= TIMHIP_STORE_BF16; }
+typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+// the eight elements of one 16-byte chunk of a 16-bit store (element 2 i in the low half of word i) as two fp32 quads
+template <int ST>
+__device__ __forceinline__ void widen8(u32x4_t w, f32x4_t& lo, f32x4_t& hi) {
+  typedef StoreT<ST> S;
+  lo[0] = S::widen((uint16_t)w[0]); lo[1] = S::widen((uint16_t)(w[0] >> 16));
+  lo[2] = S::widen((uint16_t)w[1]); lo[3] = S::widen((uint16_t)(w[1] >> 16));
+  hi[0] = S::widen((uint16_t)w[2]); hi[1] = S::widen((uint16_t)(w[2] >> 16));
+  hi[2] = S::widen((uint16_t)w[3]); hi[3] = S::widen((uint16_t)(w[3] >> 16));
+}
+// run the statement with the constant ST = the store type `st` (which must satisfy valid_store)
+#define DISPATCH_STORE(st, ...)                                                              \
+  do {                                                                                       \
+    if ((st) == TIMHIP_STORE_F16) { constexpr int ST = TIMHIP_STORE_F16; __VA_ARGS__; }      \
+    else if ((st) == TIMHIP_STORE_BF16) { constexpr int ST = TIMHIP_STORE_BF16; __VA_ARGS__; } \
+    else { constexpr int ST = TIMHIP_STORE_F32; __VA_ARGS__; }                               \
+  } while (0)
+
 // v_mfma_f32_32x32x16_{bf16,f16}: D[32x32] += A[32x16] B[16x32], 8 operand values per lane, fp32 accumulate
 template <typename HT> __device__ __forceinline__ f32x16_t mfma16(vec8<HT> a, vec8<HT> b, f32x16_t c);
 template <> __device__ __forceinline__ f32x16_t mfma16<bf16_t>(vec8<bf16_t> a, vec8<bf16_t> b, f32x16_t c) {

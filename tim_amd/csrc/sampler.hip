@@ -110,10 +110,14 @@ __device__ __forceinline__ int wb_window(const D& d, long long b) {
 // index chain (window -> row0, feat_indices, aug) is walked once per four loads and the four loads are in flight together
 constexpr int WB_UNROLL = 4, WB_SPAN = 64 * WB_UNROLL;   // chunks a wave covers (the four loads are written out below)
 
-template <class D>
-__device__ __forceinline__ void wb_feature_item(const D& d, const float* __restrict__ feats, const long long* __restrict__ row0,
+// ST: the element type of the store (TIMHIP_STORE_*).  A 16-bit store has 8 elements to the 16-byte chunk: a chunk becomes two
+// 16-byte fp32 stores, a wave covers 2048 elements, and the fast path wants a width that is a multiple of 8
+template <int ST, class D>
+__device__ __forceinline__ void wb_feature_item(const D& d, const void* __restrict__ feats, const long long* __restrict__ row0,
                                                 const int* __restrict__ aug, int num_aug, int C, float* __restrict__ out, long long row,
                                                 int group) {
+  typedef StoreT<ST> S;
+  constexpr int E = S::CHUNK;
   long long b;
   int j;
   wb_divmod(row, d.num_feats, b, j);
@@ -121,33 +125,49 @@ __device__ __forceinline__ void wb_feature_item(const D& d, const float* __restr
   int a = aug ? aug[row] : 0;
   a = (unsigned)a < (unsigned)num_aug ? a : 0;
   const long long srow = (row0[w] + d.feat_indices[(size_t)w * d.num_feats + j]) * num_aug + a;
-  const float* x = feats + (size_t)srow * C;
+  const typename S::T* x = reinterpret_cast<const typename S::T*>(feats) + (size_t)srow * C;
   float* o = out + (size_t)row * C;
-  const int chunks = (C + 3) >> 2, c0 = (group >> 6) * WB_SPAN + (group & 63);
-  if ((C & 3) == 0 && ((((uintptr_t)x) | ((uintptr_t)o)) & 15) == 0) {
+  const int chunks = (C + E - 1) / E, c0 = (group >> 6) * WB_SPAN + (group & 63);
+  if ((C & (E - 1)) == 0 && ((((uintptr_t)x) | ((uintptr_t)o)) & 15) == 0) {
     typedef float f32x4 __attribute__((ext_vector_type(4)));
-    const f32x4* xv = reinterpret_cast<const f32x4*>(x) + c0;
-    f32x4* ov = reinterpret_cast<f32x4*>(o) + c0;
     const bool p0 = c0 < chunks, p1 = c0 + 64 < chunks, p2 = c0 + 128 < chunks, p3 = c0 + 192 < chunks;
-    f32x4 v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f;
-    if (p0) v0 = xv[0];
-    if (p1) v1 = xv[64];
-    if (p2) v2 = xv[128];
-    if (p3) v3 = xv[192];
-    if (p0) ov[0] = v0;
-    if (p1) ov[64] = v1;
-    if (p2) ov[128] = v2;
-    if (p3) ov[192] = v3;
-  } else {   // a width that is no multiple of 4, or a row off 16-byte alignment
+    if constexpr (ST == TIMHIP_STORE_F32) {
+      const f32x4* xv = reinterpret_cast<const f32x4*>(x) + c0;
+      f32x4* ov = reinterpret_cast<f32x4*>(o) + c0;
+      f32x4 v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f;
+      if (p0) v0 = xv[0];
+      if (p1) v1 = xv[64];
+      if (p2) v2 = xv[128];
+      if (p3) v3 = xv[192];
+      if (p0) ov[0] = v0;
+      if (p1) ov[64] = v1;
+      if (p2) ov[128] = v2;
+      if (p3) ov[192] = v3;
+    } else {
+      const u32x4_t* xv = reinterpret_cast<const u32x4_t*>(x) + c0;
+      f32x4* ov = reinterpret_cast<f32x4*>(o) + 2 * c0;
+      u32x4_t v0 = 0u, v1 = 0u, v2 = 0u, v3 = 0u;
+      if (p0) v0 = xv[0];
+      if (p1) v1 = xv[64];
+      if (p2) v2 = xv[128];
+      if (p3) v3 = xv[192];
+      f32x4 lo, hi;
+      if (p0) { widen8<ST>(v0, lo, hi); ov[0] = lo; ov[1] = hi; }
+      if (p1) { widen8<ST>(v1, lo, hi); ov[128] = lo; ov[129] = hi; }
+      if (p2) { widen8<ST>(v2, lo, hi); ov[256] = lo; ov[257] = hi; }
+      if (p3) { widen8<ST>(v3, lo, hi); ov[384] = lo; ov[385] = hi; }
+    }
+  } else {   // a width that is no multiple of the chunk, or a row off 16-byte alignment
     for (int k = 0; k < WB_UNROLL; ++k) {
-      const int e0 = 4 * (c0 + 64 * k);
-      for (int e = e0; e < e0 + 4 && e < C; ++e) o[e] = x[e];
+      const int e0 = E * (c0 + 64 * k);
+      for (int e = e0; e < e0 + E && e < C; ++e) o[e] = S::widen(x[e]);
     }
   }
 }
 
 // flat work index over (section, row, item), grid-stride (a row's items are a multiple of 64 and the feature sections come
 // first: a wave never straddles two rows)
+template <int VS, int AS>
 __global__ __launch_bounds__(256) void window_batch_kernel(const WbArgs a) {
   const TimWindowBatch& d = a.d;
   const long long total = a.first[WB_SECTIONS], stride = (long long)gridDim.x * blockDim.x;
@@ -156,12 +176,12 @@ __global__ __launch_bounds__(256) void window_batch_kernel(const WbArgs a) {
       long long row;
       int chunk;
       wb_divmod(wi, a.groups_v, row, chunk);
-      wb_feature_item(d, d.v_feats, (const long long*)d.v_row0, d.v_aug, d.v_num_aug, d.Cv, d.visual, row, chunk);
+      wb_feature_item<VS>(d, d.v_feats, (const long long*)d.v_row0, d.v_aug, d.v_num_aug, d.Cv, d.visual, row, chunk);
     } else if (wi < a.first[WB_TIMES]) {
       long long row;
       int chunk;
       wb_divmod(wi - a.first[WB_AUDIO], a.groups_a, row, chunk);
-      wb_feature_item(d, d.a_feats, (const long long*)d.a_row0, d.a_aug, d.a_num_aug, d.Ca, d.audio, row, chunk);
+      wb_feature_item<AS>(d, d.a_feats, (const long long*)d.a_row0, d.a_aug, d.a_num_aug, d.Ca, d.audio, row, chunk);
     } else if (wi < a.first[WB_VLABELS]) {   // window_times_kernel (batch.hip), one (start, end) row per item
       long long b;
       int t;
@@ -225,6 +245,7 @@ __device__ __forceinline__ bool db_padded(const long long* lab) { return (lab[0]
 
 // the feature sections are window_batch_kernel's (wb_feature_item); then one (start, end) row, one ground-truth slot or one
 // batch row per item
+template <int VS, int AS>
 __global__ __launch_bounds__(256) void det_window_batch_kernel(const DbArgs a) {
   const TimDetWindowBatch& d = a.d;
   const long long total = a.first[DB_SECTIONS], stride = (long long)gridDim.x * blockDim.x;
@@ -233,12 +254,12 @@ __global__ __launch_bounds__(256) void det_window_batch_kernel(const DbArgs a) {
       long long row;
       int chunk;
       wb_divmod(wi, a.groups_v, row, chunk);
-      wb_feature_item(d, d.v_feats, (const long long*)d.v_row0, d.v_aug, d.v_num_aug, d.Cv, d.visual, row, chunk);
+      wb_feature_item<VS>(d, d.v_feats, (const long long*)d.v_row0, d.v_aug, d.v_num_aug, d.Cv, d.visual, row, chunk);
     } else if (wi < a.first[DB_TIMES]) {
       long long row;
       int chunk;
       wb_divmod(wi - a.first[DB_AUDIO], a.groups_a, row, chunk);
-      wb_feature_item(d, d.a_feats, (const long long*)d.a_row0, d.a_aug, d.a_num_aug, d.Ca, d.audio, row, chunk);
+      wb_feature_item<AS>(d, d.a_feats, (const long long*)d.a_row0, d.a_aug, d.a_num_aug, d.Ca, d.audio, row, chunk);
     } else if (wi < a.first[DB_VSEG]) {
       long long b;
       int t;
@@ -316,6 +337,27 @@ __global__ __launch_bounds__(256) void drloc_draw_kernel(uint64_t seed, unsigned
   }
 }
 
+// ---- host side of the two assembly entries: what depends on the element type of a store -----------------------------------
+// items of a feature row of width C: 64 per WB_SPAN chunks (16 bytes: 4 fp32 or 8 16-bit elements), the last span possibly
+// short - a multiple of 64, so a wave never straddles two rows
+int wb_groups(int C, int store) {
+  const int per = store == TIMHIP_STORE_F32 ? 4 : 8;
+  return ((C + per - 1) / per + WB_SPAN - 1) / WB_SPAN * 64;
+}
+
+// an fp32 store off 4 bytes, a 16-bit store off 2
+bool wb_store_misaligned(const void* p, int store) { return (((uintptr_t)p) & (store == TIMHIP_STORE_F32 ? 3 : 1)) != 0; }
+
+template <int VS>
+void wb_launch(int a_store, const WbArgs& a, int blocks, hipStream_t s) {
+  DISPATCH_STORE(a_store, hipLaunchKernelGGL(HIP_KERNEL_NAME(window_batch_kernel<VS, ST>), dim3(blocks), dim3(256), 0, s, a));
+}
+
+template <int VS>
+void db_launch(int a_store, const DbArgs& a, int blocks, hipStream_t s) {
+  DISPATCH_STORE(a_store, hipLaunchKernelGGL(HIP_KERNEL_NAME(det_window_batch_kernel<VS, ST>), dim3(blocks), dim3(256), 0, s, a));
+}
+
 }  // namespace
 
 extern "C" {
@@ -350,8 +392,8 @@ int timhip_sampler_draw(uint64_t seed, uint64_t* counter, int num_windows, int w
   return TIMHIP_OK;
 }
 
-int timhip_window_batch(const TimWindowBatch* desc, void* stream) {
-  if (!desc) return TIMHIP_EINVAL;
+int timhip_window_batch_st(const TimWindowBatch* desc, int v_store, int a_store, void* stream) {
+  if (!desc || !valid_store(v_store) || !valid_store(a_store)) return TIMHIP_EINVAL;
   WbArgs a;
   a.d = *desc;
   const TimWindowBatch& d = a.d;
@@ -363,9 +405,10 @@ int timhip_window_batch(const TimWindowBatch* desc, void* stream) {
   if ((!has_v && d.v_feat_times) || (!has_a && d.a_feat_times)) return TIMHIP_EINVAL;
   if (d.max_v > 0 && (!d.v_queries || !d.v_labels || !d.v_ids || !d.verb || !d.noun || !d.action || !d.v_action_ids)) return TIMHIP_EINVAL;
   if (d.max_a > 0 && (!d.a_queries || !d.a_labels || !d.a_ids || !d.class_id || !d.a_action_ids)) return TIMHIP_EINVAL;
-  if ((((uintptr_t)d.visual) | ((uintptr_t)d.audio) | ((uintptr_t)d.times) | ((uintptr_t)d.v_feats) | ((uintptr_t)d.a_feats)) & 3) return TIMHIP_EALIGN;
-  a.groups_v = has_v ? ((d.Cv + 3) / 4 + 255) / 256 * 64 : 64;   // (wb_feature_item: 256 chunks per wave)
-  a.groups_a = has_a ? ((d.Ca + 3) / 4 + 255) / 256 * 64 : 64;
+  if ((((uintptr_t)d.visual) | ((uintptr_t)d.audio) | ((uintptr_t)d.times)) & 3) return TIMHIP_EALIGN;
+  if (wb_store_misaligned(d.v_feats, v_store) || wb_store_misaligned(d.a_feats, a_store)) return TIMHIP_EALIGN;
+  a.groups_v = has_v ? wb_groups(d.Cv, v_store) : 64;
+  a.groups_a = has_a ? wb_groups(d.Ca, a_store) : 64;
   a.T = (has_v ? d.num_feats : 0) + (has_a ? d.num_feats : 0) + d.max_v + d.max_a;
   const long long rows = (long long)d.B * d.num_feats;
   if (rows > (1ll << 40) / (a.groups_v > a.groups_a ? a.groups_v : a.groups_a)) return TIMHIP_EUNSUPPORTED;   // (the flat index stays far inside 63 bits)
@@ -386,13 +429,17 @@ int timhip_window_batch(const TimWindowBatch* desc, void* stream) {
   // byte-bound: 256 CUs x 8 blocks of 256 threads and a grid-stride loop over the rest
   const long long want = (total + 255) / 256;
   const int blocks = (int)(want > 2048 ? 2048 : want);
-  hipLaunchKernelGGL(window_batch_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
+  DISPATCH_STORE(v_store, wb_launch<ST>(a_store, a, blocks, (hipStream_t)stream));
   TIM_CHECK_LAUNCH();
   return TIMHIP_OK;
 }
 
-int timhip_det_window_batch(const TimDetWindowBatch* desc, void* stream) {
-  if (!desc) return TIMHIP_EINVAL;
+int timhip_window_batch(const TimWindowBatch* desc, void* stream) {
+  return timhip_window_batch_st(desc, TIMHIP_STORE_F32, TIMHIP_STORE_F32, stream);
+}
+
+int timhip_det_window_batch_st(const TimDetWindowBatch* desc, int v_store, int a_store, void* stream) {
+  if (!desc || !valid_store(v_store) || !valid_store(a_store)) return TIMHIP_EINVAL;
   DbArgs a;
   a.d = *desc;
   const TimDetWindowBatch& d = a.d;
@@ -408,13 +455,14 @@ int timhip_det_window_batch(const TimDetWindowBatch* desc, void* stream) {
   if ((!has_v && d.v_feat_times) || (!has_a && d.a_feat_times)) return TIMHIP_EINVAL;
   if (d.max_v > 0 && (!d.v_segments || !d.v_labels || !d.v_gt_segments || !d.verb || !d.noun || !d.action)) return TIMHIP_EINVAL;
   if (d.max_a > 0 && (!d.a_segments || !d.a_labels || !d.a_gt_segments || !d.class_id)) return TIMHIP_EINVAL;
-  if ((((uintptr_t)d.visual) | ((uintptr_t)d.audio) | ((uintptr_t)d.times) | ((uintptr_t)d.v_feats) | ((uintptr_t)d.a_feats) |
+  if ((((uintptr_t)d.visual) | ((uintptr_t)d.audio) | ((uintptr_t)d.times) |
        ((uintptr_t)d.v_feat_times) | ((uintptr_t)d.a_feat_times) | ((uintptr_t)d.start_sec) | ((uintptr_t)d.v_segments) |
        ((uintptr_t)d.a_segments) | ((uintptr_t)d.v_gt_segments) | ((uintptr_t)d.a_gt_segments)) & 3)
     return TIMHIP_EALIGN;
+  if (wb_store_misaligned(d.v_feats, v_store) || wb_store_misaligned(d.a_feats, a_store)) return TIMHIP_EALIGN;
   if ((((uintptr_t)d.window_start_sec) | ((uintptr_t)d.window_start)) & 7) return TIMHIP_EALIGN;
-  a.groups_v = has_v ? ((d.Cv + 3) / 4 + 255) / 256 * 64 : 64;   // (wb_feature_item: 256 chunks per wave)
-  a.groups_a = has_a ? ((d.Ca + 3) / 4 + 255) / 256 * 64 : 64;
+  a.groups_v = has_v ? wb_groups(d.Cv, v_store) : 64;
+  a.groups_a = has_a ? wb_groups(d.Ca, a_store) : 64;
   a.T = (has_v ? d.num_feats : 0) + (has_a ? d.num_feats : 0);
   const long long rows = (long long)d.B * d.num_feats;
   if (rows > (1ll << 40) / (a.groups_v > a.groups_a ? a.groups_v : a.groups_a)) return TIMHIP_EUNSUPPORTED;   // (as timhip_window_batch)
@@ -434,9 +482,13 @@ int timhip_det_window_batch(const TimDetWindowBatch* desc, void* stream) {
   a.first[DB_SECTIONS] = total;
   const long long want = (total + 255) / 256;
   const int blocks = (int)(want > 2048 ? 2048 : want);
-  hipLaunchKernelGGL(det_window_batch_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
+  DISPATCH_STORE(v_store, db_launch<ST>(a_store, a, blocks, (hipStream_t)stream));
   TIM_CHECK_LAUNCH();
   return TIMHIP_OK;
+}
+
+int timhip_det_window_batch(const TimDetWindowBatch* desc, void* stream) {
+  return timhip_det_window_batch_st(desc, TIMHIP_STORE_F32, TIMHIP_STORE_F32, stream);
 }
 
 int timhip_drloc_draw(uint64_t seed, uint64_t* counter, int n, int m, int l, int64_t* pos_1, int64_t* pos_2, float* deltax,

@@ -12,6 +12,12 @@ reference, already on the device.  No CPU path: the kernels run or the call rais
 `batch()` takes host indices and allocates its outputs, so it cannot sit inside a captured step.  `ds.sampler(batch_size, ...)`
 returns a `WindowSampler` whose order lives on the device: `next_batch()` is two launches (`timhip_sampler_draw`,
 `timhip_window_batch`) into tensors of fixed address, eager or replayed with the same bits.
+
+`store_dtype` (fp32 by default; `torch.float16`, `torch.bfloat16`, or one per modality) is the element type the feature stores
+are held in.  The model's 16-bit modes round every input row to their operand type in front of the embedders, so a store kept
+in that type loses nothing the forward would not lose one launch later, at half the bytes.  Batches stay fp32: a stored
+element comes out as its exact widening (`timhip_window_gather_st`, `timhip_window_batch_st`).  A finite value that the storage
+type cannot hold is refused at construction, never stored as inf.
 """
 import ctypes as C
 
@@ -22,12 +28,56 @@ from ._lib import call, ptr
 from .functional import _stream
 
 
+STORE_CODES = {torch.float32: L.STORE_F32, torch.float16: L.STORE_F16, torch.bfloat16: L.STORE_BF16}   # TIMHIP_STORE_*
+
+
+def store_dtypes(store_dtype):
+    """-> {"visual": dtype, "audio": dtype} of a `store_dtype` argument: one of torch.float32 / float16 / bfloat16 for both
+    modalities, or a dict {"visual": ..., "audio": ...} (a modality it leaves out is fp32).  Anything else: ValueError."""
+    if isinstance(store_dtype, dict):
+        if not set(store_dtype) <= {"visual", "audio"}:
+            raise ValueError('store_dtype: a dict names "visual" and / or "audio", got %r' % (sorted(map(str, store_dtype)),))
+        out = {m: store_dtype.get(m, torch.float32) for m in ("visual", "audio")}
+    else:
+        out = {"visual": store_dtype, "audio": store_dtype}
+    for m, dt in out.items():
+        if not isinstance(dt, torch.dtype) or dt not in STORE_CODES:
+            raise ValueError("store_dtype: %s store of %r, not one of torch.float32, torch.float16, torch.bfloat16" % (m, dt))
+    return out
+
+
+def round_to_store(feats, dtype, modality="", video=""):
+    """One video's feature array as a CPU tensor of the storage type.  An array already of that type comes back as it is, bit
+    for bit; anything else is rounded once, to nearest even, by `.to(dtype)` (fp32: the `.float()` the fp32 store always did).
+    A finite value that rounding to a 16-bit type turns into inf is a ValueError that names the modality, the video and the
+    count: an overflow is refused, not stored.  Non-finite inputs pass through as they are.  Needs no GPU."""
+    f = torch.as_tensor(feats)
+    if f.dtype == dtype:
+        return f
+    if dtype == torch.float32:
+        return f.float()
+    r = f.to(dtype)
+    finite_in = torch.isfinite(f) if f.is_floating_point() else torch.ones_like(r, dtype=torch.bool)
+    lost = int((finite_in & ~torch.isfinite(r)).sum())
+    if lost:
+        raise ValueError("%s features of video %s: %d finite value%s beyond the range of %s"
+                         % (modality or "the", video, lost, "" if lost == 1 else "s", str(dtype).replace("torch.", "")))
+    return r
+
+
+def store_code(store):
+    """TIMHIP_STORE_* of a store dict (one without "dtype" - a hand-built fp32 store - is fp32)"""
+    return STORE_CODES[store.get("dtype", torch.float32)]
+
+
 class DeviceWindowDataset:
     def __init__(self, windows, num_feats, window_size, max_visual_actions, max_audio_actions, model_modality="audio_visual",
-                 v_feats=None, v_feat_times=None, a_feats=None, a_feat_times=None, device="cuda"):
+                 v_feats=None, v_feat_times=None, a_feats=None, a_feat_times=None, device="cuda", store_dtype=torch.float32):
         """Arguments are the attributes the reference dataset holds after its constructor: `windows` (list of dicts,
         sliding_window.py:262-277), `v_feats`/`a_feats` {video_id: [N_feat, num_aug, C]}, `v_feat_times`/`a_feat_times`
-        {video_id: [N_feat, >=2]}, `num_feats`, `window_size`, `max_visual_actions`, `max_audio_actions`."""
+        {video_id: [N_feat, >=2]}, `num_feats`, `window_size`, `max_visual_actions`, `max_audio_actions`.  `store_dtype`: the
+        element type of the feature stores (`store_dtypes`); feature times stay fp32."""
+        self.store_dtype = store_dtypes(store_dtype)
         if not torch.cuda.is_available():
             raise L.TimHipError("DeviceWindowDataset needs the MI355X (no CPU fallback)")
         L.load()
@@ -38,8 +88,8 @@ class DeviceWindowDataset:
         self.has_v, self.has_a = "visual" in model_modality, "audio" in model_modality
         W = len(windows)
         vids = sorted({w["video_id"] for w in windows})
-        self.v = self._store(v_feats, v_feat_times, vids) if self.has_v else None
-        self.a = self._store(a_feats, a_feat_times, vids) if self.has_a else None
+        self.v = self._store(v_feats, v_feat_times, vids, self.store_dtype["visual"], "visual") if self.has_v else None
+        self.a = self._store(a_feats, a_feat_times, vids, self.store_dtype["audio"], "audio") if self.has_a else None
         dev, mv, ma = self.device, self.max_visual_actions, self.max_audio_actions
         fi = torch.stack([torch.as_tensor(w["feat_indices"]).to(torch.int32).reshape(-1) for w in windows])
         if fi.shape[1] != self.num_feats:
@@ -70,14 +120,17 @@ class DeviceWindowDataset:
         self.num_windows = W
 
     @classmethod
-    def from_reference(cls, ds, device="cuda"):
+    def from_reference(cls, ds, device="cuda", store_dtype=torch.float32):
         """from a constructed reference `SlidingWindowDataset` (or anything exposing the same attributes)"""
         return cls(ds.windows, ds.num_feats, ds.window_size, ds.max_visual_actions, ds.max_audio_actions, ds.model_modality,
-                   ds.v_feats, ds.v_feat_times, ds.a_feats, ds.a_feat_times, device)
+                   ds.v_feats, ds.v_feat_times, ds.a_feats, ds.a_feat_times, device, store_dtype=store_dtype)
 
-    def _store(self, feats, feat_times, vids):
+    def _store(self, feats, feat_times, vids, dtype=torch.float32, modality=""):
+        """-> {"row0", "num_aug", "C", "feats" (in the storage type), "times" (fp32), "dtype"}"""
         if feats is None or feat_times is None:
             raise ValueError("features and feature times are required for every modality of model_modality")
+        if dtype != torch.float32:
+            return DeviceWindowDataset._store16(self, feats, feat_times, vids, dtype, modality)
         row0, off, fl, tl = {}, 0, [], []
         num_aug, C = None, None
         for v in vids:
@@ -91,10 +144,36 @@ class DeviceWindowDataset:
             fl.append(f.float().reshape(-1, C))
             tl.append(t[:, :2])
         return {"row0": row0, "num_aug": num_aug, "C": C, "feats": torch.cat(fl).to(self.device).contiguous(),
-                "times": torch.cat(tl).to(self.device).contiguous()}
+                "times": torch.cat(tl).to(self.device).contiguous(), "dtype": torch.float32}
+
+    def _store16(self, feats, feat_times, vids, dtype, modality):
+        """A 16-bit store, video by video into ONE preallocated device tensor: neither the host nor the device ever holds a
+        second copy of the set (the host holds one video in the storage type at a time, and nothing for a video that is already
+        in it)."""
+        row0, off, tl = {}, 0, []
+        num_aug, C = None, None
+        for v in vids:                                        # shapes first: the size of the allocation
+            shape, t = tuple(feats[v].shape), torch.as_tensor(feat_times[v]).float()
+            if num_aug is None:
+                num_aug, C = shape[1], shape[2]
+            if len(shape) != 3 or shape[1] != num_aug or shape[2] != C or t.shape[0] != shape[0]:
+                raise ValueError("inconsistent feature arrays for video %s" % v)
+            row0[v] = off
+            off += shape[0]
+            tl.append(t[:, :2])
+        store = torch.empty((off * (num_aug or 0), C or 0), dtype=dtype, device=self.device)
+        for v in vids:
+            r = round_to_store(feats[v], dtype, modality, v).reshape(-1, C)
+            store[row0[v] * num_aug:row0[v] * num_aug + r.shape[0]].copy_(r)
+        return {"row0": row0, "num_aug": num_aug, "C": C, "feats": store, "times": torch.cat(tl).to(self.device).contiguous(),
+                "dtype": dtype}
 
     def __len__(self):
         return self.num_windows
+
+    def store_bytes(self):
+        """bytes the feature stores occupy in device memory (the features of the present modalities; not their times)"""
+        return sum(st["feats"].numel() * st["feats"].element_size() for st in (self.v, self.a) if st is not None)
 
     def batch(self, indices, v_aug_indices=None, a_aug_indices=None):
         """= default_collate([dataset[i] for i in indices]) of the reference (sliding_window.py:341-421), on the device.
@@ -109,8 +188,12 @@ class DeviceWindowDataset:
                 aug = torch.randint(0, store["num_aug"], (B, nf), device=dev, dtype=torch.int32)
             aug = torch.as_tensor(aug).to(device=dev, dtype=torch.int32).contiguous()
             out = torch.empty((B, nf, store["C"]), dtype=torch.float32, device=dev)
-            call("timhip_window_gather", ptr(store["feats"]), store["C"], store["num_aug"], ptr(row0), ptr(self.feat_indices),
-                 nf, ptr(win), B, ptr(aug), ptr(out), st)
+            if store_code(store) == L.STORE_F32:
+                call("timhip_window_gather", ptr(store["feats"]), store["C"], store["num_aug"], ptr(row0), ptr(self.feat_indices),
+                     nf, ptr(win), B, ptr(aug), ptr(out), st)
+            else:                                             # a 16-bit store: every element widened exactly
+                call("timhip_window_gather_st", ptr(store["feats"]), store_code(store), store["C"], store["num_aug"], ptr(row0),
+                     ptr(self.feat_indices), nf, ptr(win), B, ptr(aug), ptr(out), st)
             return out
 
         v_data = gather(self.v, self.v_row0, v_aug_indices) if self.has_v else torch.empty((B, 0), device=dev)
@@ -148,6 +231,13 @@ class DeviceWindowDataset:
     def sampler(self, batch_size, seed=0, shuffle=True, rank=0, world=1, last="wrap"):
         """A `WindowSampler` over this dataset: batches drawn and assembled on the device, capturable."""
         return WindowSampler(self, batch_size, seed=seed, shuffle=shuffle, rank=rank, world=world, last=last)
+
+
+def _batch_stores(ds):
+    """None when every feature store of the dataset is fp32 (the fp32 entries serve it), else the (visual, audio) TIMHIP_STORE_*
+    arguments of the `_st` entries"""
+    codes = tuple(store_code(st) if st is not None else L.STORE_F32 for st in (ds.v, ds.a))
+    return None if codes == (L.STORE_F32, L.STORE_F32) else codes
 
 
 class _DeviceOrder:
@@ -257,6 +347,7 @@ class WindowSampler(_DeviceOrder):
                          "num_v_queries": torch.full((B,), mv, dtype=torch.int64), "num_a_queries": torch.full((B,), ma, dtype=torch.int64),
                          "window": self.window, "valid": self.valid}
         self._desc = None
+        self._stores = _batch_stores(ds)
 
     def _descriptor(self):
         ds, lb, md = self.dataset, self.label, self.metadata
@@ -286,5 +377,8 @@ class WindowSampler(_DeviceOrder):
         with torch.cuda.device(self.device):
             st = _stream()
             self._draw(st)
-            call("timhip_window_batch", C.byref(self._desc), st)
+            if self._stores is None:
+                call("timhip_window_batch", C.byref(self._desc), st)
+            else:
+                call("timhip_window_batch_st", C.byref(self._desc), self._stores[0], self._stores[1], st)
         return self.visual, self.audio, self.times, self.label, self.metadata

@@ -16,7 +16,7 @@ import torch
 
 from . import _lib as L
 from ._lib import call, ptr
-from .data import DeviceWindowDataset, _DeviceOrder
+from .data import DeviceWindowDataset, _DeviceOrder, _batch_stores, store_dtypes
 from .functional import _stream
 
 
@@ -30,12 +30,14 @@ def action_column(dataset_name="epic", include_verb_noun=True, verb_only=True):
 class DeviceDetectionDataset:
     def __init__(self, windows, num_feats, window_size, max_visual_actions, max_audio_actions, model_modality="audio_visual",
                  v_feats=None, v_feat_times=None, a_feats=None, a_feat_times=None, dataset_name="epic", include_verb_noun=True,
-                 verb_only=True, device="cuda"):
+                 verb_only=True, device="cuda", store_dtype=torch.float32):
         """Arguments are the attributes the reference dataset holds after its constructor: `windows` (list of dicts with
         video_id, start_sec, feat_indices, v_gt_segments / a_gt_segments [n, 2] in seconds, v_labels / a_labels [n, 4];
         sliding_window.py:225-282), `v_feats`/`a_feats` {video_id: [N_feat, num_aug, C]}, `v_feat_times`/`a_feat_times`
         {video_id: [N_feat, >=2]}, `num_feats`, `window_size`, `max_visual_actions`, `max_audio_actions`, `dataset_name`,
-        `include_verb_noun`, `verb_only`.  A window with more actions than its maximum is a ValueError."""
+        `include_verb_noun`, `verb_only`.  A window with more actions than its maximum is a ValueError.  `store_dtype`: the
+        element type of the feature stores, as in `tim_amd.data.DeviceWindowDataset` (fp32, fp16 or bf16, or one per modality)."""
+        self.store_dtype = store_dtypes(store_dtype)
         if not torch.cuda.is_available():
             raise L.TimHipError("DeviceDetectionDataset needs the MI355X (no CPU fallback)")
         L.load()
@@ -51,9 +53,9 @@ class DeviceDetectionDataset:
         W = len(windows)
         self.video_ids = sorted({w["video_id"] for w in windows})
         index = {v: i for i, v in enumerate(self.video_ids)}
-        store = lambda f, t: DeviceWindowDataset._store(self, f, t, self.video_ids)   # noqa: E731  (it reads self.device only)
-        self.v = store(v_feats, v_feat_times) if self.has_v else None
-        self.a = store(a_feats, a_feat_times) if self.has_a else None
+        store = lambda f, t, m: DeviceWindowDataset._store(self, f, t, self.video_ids, self.store_dtype[m], m)   # noqa: E731  (it reads self.device only)
+        self.v = store(v_feats, v_feat_times, "visual") if self.has_v else None
+        self.a = store(a_feats, a_feat_times, "audio") if self.has_a else None
         dev, mv, ma = self.device, self.max_visual_actions, self.max_audio_actions
         fi = torch.stack([torch.as_tensor(w["feat_indices"]).to(torch.int32).reshape(-1) for w in windows]) if W else torch.zeros((0, self.num_feats))
         if fi.shape[1] != self.num_feats:
@@ -83,13 +85,24 @@ class DeviceDetectionDataset:
         self.num_windows = W
 
     @classmethod
-    def from_reference(cls, ds, device="cuda"):
+    def from_reference(cls, ds, device="cuda", store_dtype=torch.float32):
         """from a constructed reference detection `SlidingWindowDataset` (or anything exposing the same attributes)"""
         return cls(ds.windows, ds.num_feats, ds.window_size, ds.max_visual_actions, ds.max_audio_actions, ds.model_modality,
-                   ds.v_feats, ds.v_feat_times, ds.a_feats, ds.a_feat_times, ds.dataset_name, ds.include_verb_noun, ds.verb_only, device)
+                   ds.v_feats, ds.v_feat_times, ds.a_feats, ds.a_feat_times, ds.dataset_name, ds.include_verb_noun, ds.verb_only, device,
+                   store_dtype=store_dtype)
 
     def __len__(self):
         return self.num_windows
+
+    store_bytes = DeviceWindowDataset.store_bytes
+
+    def _assemble(self, desc, st):
+        """one assembly launch: the fp32 entry, or the `_st` entry when a feature store is 16-bit"""
+        stores = _batch_stores(self)
+        if stores is None:
+            call("timhip_det_window_batch", C.byref(desc), st)
+        else:
+            call("timhip_det_window_batch_st", C.byref(desc), stores[0], stores[1], st)
 
     def video_ids_of(self, windows):
         """The video-id strings (host data) of a list or CPU tensor of window numbers: the `video_id` entry of a collated batch."""
@@ -155,7 +168,7 @@ class DeviceDetectionDataset:
         a_aug = aug(self.a, a_aug_indices) if self.has_a else None
         out = self._outputs(B, lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev))
         with torch.cuda.device(dev):
-            call("timhip_det_window_batch", C.byref(self._descriptor(B, win, valid, v_aug, a_aug, out)), _stream())
+            self._assemble(self._descriptor(B, win, valid, v_aug, a_aug, out), _stream())
         visual, audio, times, label, window_start, video_index = out
         metadata = {"window_start": window_start, "window_size": torch.full((B,), self.window_size, dtype=torch.float64, device=dev),
                     "video_id": [self.video_ids[self.window_video[i]] for i in idx], "video_index": video_index}
@@ -213,5 +226,5 @@ class DetectionWindowSampler(_DeviceOrder):
         with torch.cuda.device(self.device):
             st = _stream()
             self._draw(st)
-            call("timhip_det_window_batch", C.byref(self._desc), st)
+            self.dataset._assemble(self._desc, st)
         return self.visual, self.audio, self.times, self.label, self.metadata

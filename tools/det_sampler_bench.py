@@ -2,7 +2,7 @@
 """Detection batch assembly at the C4 training shape: the device-side sampler against the host-fed form (needs the MI355X; one
 JSON line per batch size).
 
-    python tools/det_sampler_bench.py [--windows 16] [--rounds 7] [--iters 200] [--store-gb 4]
+    python tools/det_sampler_bench.py [--windows 16] [--rounds 7] [--iters 200] [--store-gb 4] [--store-dtype fp32|fp16|bf16]
 
 The batch of bench.py's `c4_train` iteration: 16 windows, visual only, visual [B, 50, 2048] fp32 gathered from a feature store,
 times [B, 50, 2], 6 ground-truth segments per window with verb / noun / action, window start and video index.  Forms,
@@ -16,12 +16,17 @@ median and the spread (min, max) of the rounds are reported:
               clamp, the padding mask), then the copy_ into the static inputs of a captured step; eager only
     draw      timhip_sampler_draw alone; "batch" = device - draw is the assembly launch alone, reported against the bytes it moves
               (one read and one write of every gathered feature element)
+    device16  (--store-dtype fp16 | bf16) `device` over the same tables with the feature store held in that type
+              (timhip_det_window_batch_st: half the bytes read, the same fp32 bytes written), in the same rounds as `device`,
+              whose fp32 path is unchanged and is what the 16-bit figure is compared against; "batch16" = device16 - draw.  The
+              size --store-gb names is that of the fp32 store.  No pass mark on the ratio.
 
 Every call of every form draws NEW windows, so with a store much larger than the 256 MB last-level cache (--store-gb, default 4)
 the gathered rows come from HBM.  The outputs (6.6 MB at 16 windows) are rewritten by every call and stay cache-resident: the
 bytes/s figure is a rate through that hierarchy, not an HBM stream rate.  No pass mark: the numbers go to docs/measurement_log.md.
 """
 import argparse
+import copy
 import json
 import os
 import statistics
@@ -35,6 +40,14 @@ from tim_amd._lib import ptr  # noqa: E402
 from tim_amd.det_data import DeviceDetectionDataset  # noqa: E402
 
 NF, CV, NGT, NUM_AUG = 50, 2048, 6, 1
+STORE_DTYPES = {"fp32": None, "fp16": torch.float16, "bf16": torch.bfloat16}
+
+
+def narrow_store(ds, dtype):
+    """the same dataset with its feature store held in `dtype`, rounded once (every other table is shared)"""
+    out = copy.copy(ds)
+    out.v = dict(ds.v, feats=ds.v["feats"].to(dtype), dtype=dtype)
+    return out
 
 
 def timed(fn, iters):
@@ -80,7 +93,7 @@ def synthetic_store(dev, store_gb, seed=0):
     ds.video_ids = ["vid%02d" % i for i in range(n_vid)]
     t = (torch.arange(rows, device=dev) % per) * 0.2
     ds.v = {"row0": {}, "num_aug": NUM_AUG, "C": CV, "feats": torch.randn((rows * NUM_AUG, CV), device=dev, generator=g),
-            "times": torch.stack([t, t + 1.0], 1).float().contiguous()}
+            "times": torch.stack([t, t + 1.0], 1).float().contiguous(), "dtype": torch.float32}
     ds.a = None
     video = torch.randint(0, n_vid, (W,), device=dev, generator=g)
     first = torch.randint(0, per - 2 * NF, (W,), device=dev, generator=g)
@@ -122,14 +135,18 @@ def main(argv=None):
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--store-gb", type=float, default=4.0)
+    ap.add_argument("--store-dtype", choices=sorted(STORE_DTYPES), default="fp32", help="also time the sampler over a store held in this 16-bit type")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         sys.exit("tools/det_sampler_bench.py needs the GPU: a time taken anywhere else says nothing")
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     ds, store_gib = synthetic_store(dev, args.store_gb)
+    dt16 = STORE_DTYPES[args.store_dtype]
+    ds16 = narrow_store(ds, dt16) if dt16 is not None else None
     for B in args.windows:
         smp, ksmp = ds.sampler(B, seed=1), ds.sampler(B, seed=1)
+        smp16 = ds16.sampler(B, seed=1) if ds16 is not None else None
         host = torch.Generator().manual_seed(B)
         static = {"visual": torch.empty_like(smp.visual), "times": torch.empty_like(smp.times), "window_start": torch.empty_like(smp.metadata["window_start"]),
                   "video_index": torch.empty_like(smp.metadata["video_index"])}
@@ -159,6 +176,13 @@ def main(argv=None):
         same = {k: bool(torch.equal(a, b)) for k, (a, b) in pairs.items()}
         same["times_max_abs_diff"] = float((times - smp.times).abs().max())
         forms = {"device": smp.next_batch, "draw": draw_only}
+        if smp16 is not None:                           # same numbers: the fp32 batch rounded to the store type, widened
+            smp16.next_batch()
+            torch.cuda.synchronize()
+            assert torch.equal(smp16.window, smp.window) and torch.equal(smp16.times, smp.times)
+            assert torch.equal(smp16.visual, smp.visual.to(dt16).float())
+            assert all(torch.equal(smp16.label[k], smp.label[k]) for k in smp.label)
+            forms["device16"] = smp16.next_batch
         graphs = {n: graphed(f) for n, f in forms.items()}
         res = {"%s_%s" % (n, m): [] for n in forms for m in ("replay", "eager")}
         res["host_eager"] = []
@@ -178,6 +202,12 @@ def main(argv=None):
         # (a difference of two launch-bound times of a few us is noise: no rate from it)
         out["batch_read_write_GBps"] = round(moved / (out["batch_replay_us"] * 1e-6) / 1e9, 1) if out["batch_replay_us"] >= 5.0 else None
         out["replay_vs_host_speedup"] = round(out["host_eager_us"] / out["device_replay_us"], 2)
+        if smp16 is not None:
+            b16 = [d - w for d, w in zip(res["device16_replay"], res["draw_replay"])]
+            out["store_dtype"], out["store16_GiB"] = args.store_dtype, round(ds16.store_bytes() / 2 ** 30, 2)
+            out["batch16_replay_us"], out["batch16_replay_us_min_max"] = round(statistics.median(b16), 2), [round(min(b16), 2), round(max(b16), 2)]
+            out["batch16_over_batch"] = round(out["batch16_replay_us"] / out["batch_replay_us"], 3) if out["batch_replay_us"] >= 5.0 else None
+            out["device16_over_device_replay"] = round(out["device16_replay_us"] / out["device_replay_us"], 3)
         print(json.dumps(out), flush=True)
 
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Batch assembly at C2a shapes: the device-side sampler against the host-fed form (needs the MI355X; one JSON line per batch size).
 
-    python tools/sampler_bench.py [--windows 64 8] [--rounds 7] [--iters 200] [--store-gb 4]
+    python tools/sampler_bench.py [--windows 64 8] [--rounds 7] [--iters 200] [--store-gb 4] [--store-dtype fp32|fp16|bf16]
 
 The batch of a C2a training iteration: visual [B, 50, 1024] and audio [B, 50, 2304] fp32 gathered from a feature store, times
 [B, 125, 2], 15 + 10 queries with their labels and ids.  Forms, alternating for `rounds` rounds of `iters` calls each (device
@@ -14,6 +14,10 @@ events around the calls, after a warm-up of the same calls); the median and the 
     kernels   timhip_sampler_draw + the three kernels batch() runs (timhip_window_gather x 2, timhip_window_times) reading the
               sampler's device words: the like-for-like floor of the fused launch, which moves the same bytes plus the labels
     draw      timhip_sampler_draw alone; "batch" = device - draw and "three" = kernels - draw are the assembly launches alone
+    device16  (--store-dtype fp16 | bf16) `device` over the same tables with the feature stores held in that type
+              (timhip_window_batch_st: half the bytes read, the same fp32 bytes written), in the same rounds as `device`, whose
+              fp32 path is unchanged and is what the 16-bit figure is compared against; "batch16" = device16 - draw.  The size
+              --store-gb names is that of the fp32 stores.  No pass mark on the ratio.
 
 Every call of every form draws NEW windows, so with a store much larger than the 256 MB last-level cache (--store-gb, default 4)
 the gathered rows come from HBM; --store-gb 0 runs the 64-window toy of the examples, whose 11 MB store stays in that cache.  The
@@ -21,6 +25,7 @@ outputs (43 MB at 64 windows) are rewritten by every call and stay cache-residen
 and one write of every gathered element and is a rate through that hierarchy, not an HBM stream rate.
 """
 import argparse
+import copy
 import json
 import os
 import statistics
@@ -34,6 +39,15 @@ from tim_amd._lib import ptr  # noqa: E402
 from tim_amd.data import DeviceWindowDataset  # noqa: E402
 
 NF, CV, CA, NV, NA = 50, 1024, 2304, 15, 10
+STORE_DTYPES = {"fp32": None, "fp16": torch.float16, "bf16": torch.bfloat16}
+
+
+def narrow_store(ds, dtype):
+    """the same dataset with its feature stores held in `dtype`, rounded once (every other table is shared)"""
+    out = copy.copy(ds)
+    out.v = dict(ds.v, feats=ds.v["feats"].to(dtype), dtype=dtype) if ds.v is not None else None
+    out.a = dict(ds.a, feats=ds.a["feats"].to(dtype), dtype=dtype) if ds.a is not None else None
+    return out
 
 
 def timed(fn, iters):
@@ -75,8 +89,9 @@ def synthetic_store(dev, store_gb, seed=0):
     ds.device, ds.num_feats, ds.window_size = dev, NF, NF * 0.4
     ds.max_visual_actions, ds.max_audio_actions, ds.model_modality, ds.has_v, ds.has_a = NV, NA, "audio_visual", True, True
     ft = torch.stack([torch.arange(rows, device=dev) * 0.2, torch.arange(rows, device=dev) * 0.2 + 1.0], 1).float().contiguous()
-    ds.v = {"row0": {}, "num_aug": 1, "C": CV, "feats": torch.randn((rows, CV), device=dev, generator=g), "times": ft}
-    ds.a = {"row0": {}, "num_aug": 1, "C": CA, "feats": torch.randn((rows, CA), device=dev, generator=g), "times": ft.clone()}
+    ds.v = {"row0": {}, "num_aug": 1, "C": CV, "feats": torch.randn((rows, CV), device=dev, generator=g), "times": ft, "dtype": torch.float32}
+    ds.a = {"row0": {}, "num_aug": 1, "C": CA, "feats": torch.randn((rows, CA), device=dev, generator=g), "times": ft.clone(),
+            "dtype": torch.float32}
     first = torch.randint(0, rows - 2 * NF, (W,), device=dev, generator=g)
     ds.feat_indices = (first[:, None] + torch.arange(0, 2 * NF, 2, device=dev)[None]).to(torch.int32).contiguous()
     ds.start_sec = (first * 0.2).float()
@@ -99,14 +114,18 @@ def main(argv=None):
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--store-gb", type=float, default=4.0)
+    ap.add_argument("--store-dtype", choices=sorted(STORE_DTYPES), default="fp32", help="also time the sampler over stores held in this 16-bit type")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         sys.exit("tools/sampler_bench.py needs the GPU: a time taken anywhere else says nothing")
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     ds, store_gib = synthetic_store(dev, args.store_gb)
+    dt16 = STORE_DTYPES[args.store_dtype]
+    ds16 = narrow_store(ds, dt16) if dt16 is not None else None
     for B in args.windows:
         smp, ksmp = ds.sampler(B, seed=1), ds.sampler(B, seed=1)
+        smp16 = ds16.sampler(B, seed=1) if ds16 is not None else None
         host = torch.Generator().manual_seed(B)
         T = 2 * NF + NV + NA
         static = {"visual": torch.empty((B, NF, CV), device=dev), "audio": torch.empty((B, NF, CA), device=dev), "times": torch.empty((B, T, 2), device=dev)}
@@ -140,6 +159,12 @@ def main(argv=None):
         torch.cuda.synchronize()
         assert torch.equal(smp.window, ksmp.window) and all(torch.equal(kout[k], getattr(smp, k)) for k in kout)
         forms = {"device": smp.next_batch, "kernels": parent_kernels, "draw": draw_only}
+        if smp16 is not None:                           # same numbers: the fp32 batch rounded to the store type, widened
+            smp16.next_batch()
+            torch.cuda.synchronize()
+            assert torch.equal(smp16.window, smp.window) and torch.equal(smp16.times, smp.times)
+            assert all(torch.equal(getattr(smp16, k), getattr(smp, k).to(dt16).float()) for k in ("visual", "audio"))
+            forms["device16"] = smp16.next_batch
         graphs = {n: graphed(f) for n, f in forms.items()}
         res = {"%s_%s" % (n, m): [] for n in forms for m in ("replay", "eager")}
         res["parent_eager"] = []
@@ -164,6 +189,12 @@ def main(argv=None):
         # (a difference of two launch-bound times of a few us is noise: no rate from it)
         out["batch_read_write_GBps"] = round(moved / (out["batch_replay_us"] * 1e-6) / 1e9, 1) if out["batch_replay_us"] >= 5.0 else None
         out["replay_vs_parent_speedup"] = round(out["parent_eager_us"] / out["device_replay_us"], 2)
+        if smp16 is not None:
+            b16 = [d - w for d, w in zip(res["device16_replay"], res["draw_replay"])]
+            out["store_dtype"], out["store16_GiB"] = args.store_dtype, round(ds16.store_bytes() / 2 ** 30, 2)
+            out["batch16_replay_us"], out["batch16_replay_us_min_max"] = round(statistics.median(b16), 2), [round(min(b16), 2), round(max(b16), 2)]
+            out["batch16_over_batch"] = round(out["batch16_replay_us"] / out["batch_replay_us"], 3) if out["batch_replay_us"] >= 5.0 else None
+            out["device16_over_device_replay"] = round(out["device16_replay_us"] / out["device_replay_us"], 3)
         print(json.dumps(out), flush=True)
 
 
