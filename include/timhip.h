@@ -410,6 +410,24 @@ int timhip_attention_query_fwd(const TimDesc* d, const void* qkv_q, const void* 
  * TIMHIP_EUNSUPPORTED).  Checked before any launch: NULL d / qkv / w, a bad descriptor, p_drop != 0, s0 outside [0, S),
  * ld < F + 1 - TIMHIP_EINVAL; w not float-aligned (qkv not element-aligned) - TIMHIP_EALIGN. */
 int timhip_attention_weights(const TimDesc* d, const void* qkv, int s0, int per_head, float* w, int ld, void* stream);
+/* The attention weights of query rows against keys kept elsewhere: timhip_attention_weights for the rows and the key source of
+ * timhip_attention_query_fwd.  d, qkv_q, kv, ldkv, wrows, W, widx: as there (B = G groups, S = Q rows per group, F = keys per
+ * window; only the K columns of the cache are read).  w[g Q + i, j] (fp32, row pitch ld >= F + 1 floats; columns past F are not
+ * written), 0 <= j <= F: the mean over the heads, in ascending head order, of softmax_j(scale q . k_key(j)), key(j) = key j of
+ * window widx[g] for j < F, column F the row's own key.  per_head != 0: no mean, w is [G, H, Q, ld].  The kernels are
+ * timhip_attention_weights' own bodies with another key source (lane pair per row on the matrix cores for the head widths and
+ * key-block counts timhip_attention_fwd covers, under the alignment timhip_attention_query_fwd asks of its matrix-core route;
+ * a wave per row in fp32 arithmetic for every other shape, the fp32-storage modes and TIMHIP_DESC_ATTN_FP32), so on equal q and
+ * K values the rows equal timhip_attention_weights' query rows (s0 = F) bit for bit - on every row whose largest raw score m
+ * has |m scale log2(e)| < 2^30; rows beyond that (raw scores near the largest finite bf16 / fp32 value, where the rounding error
+ * of that product is no exponent exp2 can take and timhip_attention_weights is not finite) use exp2((score - m) scale log2(e))
+ * and stay finite.  No atomics: a row's bits depend on neither
+ * G, nor the row's place in a block, nor the other groups of the launch.  A widx[g] outside [0, W): nothing is read through it
+ * and columns 0 .. F of the group's rows are quiet NaNs.  Checked before any launch: NULL d / qkv_q / kv / w, a bad descriptor,
+ * p_drop != 0, W <= 0, NULL widx with G != W, ld < F + 1, ldkv < 2E, wrows < F - TIMHIP_EINVAL; F > 192 - TIMHIP_EUNSUPPORTED; w
+ * not float-aligned, qkv_q / kv not element-aligned - TIMHIP_EALIGN. */
+int timhip_attention_query_weights(const TimDesc* d, const void* qkv_q, const void* kv, int ldkv, int wrows, int W,
+                                   const int* widx, int per_head, float* w, int ld, void* stream);
 /* ABI 6: keep-bits of the attention dropout of `nlayers` encoder layers in ONE launch, written into the layers' saved blocks
  * (saved[l] = the block timhip_layer_fwd of layer l will fill; field TIMHIP_SAVED_ATTN_KEEP_BITS: per (window, head, token row)
  * two 64-bit words, word g bit 4 c + t = key 8 c + 4 g + t kept, keys 0 .. 127 - the order in which the MFMA attention
@@ -561,6 +579,17 @@ size_t timhip_stack_query_workspace_bytes(const TimDesc* d, int nlayers);
 int timhip_stack_query(const TimDesc* d, int nlayers, const TimLayerParams* layers, const void* cache, int W, const int* widx,
                        const float* xq_in, const void* xq_in_T, float* xq_out, void* xq_out_T, void* workspace,
                        size_t workspace_bytes, void* stream);
+/* timhip_stack_query that also writes attention maps: behind layer l's launches, while that layer's in-projection of the query
+ * rows (q | own k | own v) is live in the arena, timhip_attention_query_weights against cache block l into maps[l] - [G Q, ld]
+ * fp32, or [G, H, Q, ld] with per_head != 0.  maps: a HOST array of nlayers device pointers, read during the call only; NULL
+ * entries are skipped.  xq_out / xq_out_T are timhip_stack_query's bit for bit (the same launches in the same order; the weights
+ * kernels only read).  The arena is timhip_stack_query's, the maps are the caller's buffers.  Launches only, one stream, no
+ * events, no host read of device memory: capturable as a linear graph.  timhip_stack_query's refusals, and maps == NULL,
+ * ld < F + 1: TIMHIP_EINVAL; a map that is not float-aligned: TIMHIP_EALIGN - all before the first launch. */
+size_t timhip_stack_query_maps_workspace_bytes(const TimDesc* d, int nlayers);
+int timhip_stack_query_maps(const TimDesc* d, int nlayers, const TimLayerParams* layers, const void* cache, int W, const int* widx,
+                            const float* xq_in, const void* xq_in_T, float* xq_out, void* xq_out_T, float* const* maps,
+                            int per_head, int ld, void* workspace, size_t workspace_bytes, void* stream);
 /* dx_out: gradient w.r.t. the layer output (fp32 [M,E]).  dx_in: gradient w.r.t. the
  * layer input (fp32 [M,E]).  Parameter gradients are accumulated (+=) into *g.
  * This is timhip_layer_bwd_split (below: the form tim_amd calls) with dx_out_add = dx_in_add = NULL. */

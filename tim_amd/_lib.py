@@ -186,6 +186,10 @@ _SIGS = {
     "timhip_stack_query_workspace_bytes": (sz, [C.POINTER(TimDesc), i32]),
     "timhip_stack_query": (C.c_int, [C.POINTER(TimDesc), i32, C.POINTER(TimLayerParams), vp, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
     "timhip_attention_weights": (C.c_int, [C.POINTER(TimDesc), vp, i32, i32, vp, i32, vp]),
+    "timhip_attention_query_weights": (C.c_int, [C.POINTER(TimDesc), vp, vp, i32, i32, i32, vp, i32, vp, i32, vp]),
+    "timhip_stack_query_maps_workspace_bytes": (sz, [C.POINTER(TimDesc), i32]),
+    "timhip_stack_query_maps": (C.c_int, [C.POINTER(TimDesc), i32, C.POINTER(TimLayerParams), vp, i32, vp, vp, vp, vp, vp,
+                                          C.POINTER(vp), i32, i32, vp, sz, vp]),
     "timhip_attention_bwd": (C.c_int, [C.POINTER(TimDesc), vp, vp, vp, vp, vp, vp, sz, vp]),
     "timhip_attention_bwd_workspace_bytes": (sz, [C.POINTER(TimDesc)]),
     "timhip_attention_bwd_keep_bits": (C.c_int, [C.POINTER(TimDesc), vp, vp, vp, vp, vp, vp, sz, vp, vp]),

@@ -6,7 +6,10 @@ leaves a row F + 1 non-zeros at most - the F feature tokens and the token itself
 columns 0 .. F - 1 the feature tokens, column F the token's own key (exact 0 for feature rows, whose own key is one of the F).
 `model.attention_maps(...)` runs the evaluation forward through `timhip_stack_infer_maps`: the same stack walk as
 `model(inputs, "encoder", ...)` under `eval()` / `no_grad()` - bit-identical outputs - with one weights kernel per requested layer
-(csrc/attn_maps.hip) while that layer's qkv is live in the arena."""
+(csrc/attn_maps.hip) while that layer's qkv is live in the arena.
+`model.query_attention_maps(cache, ...)` is the same for a `query.WindowCache`: `query_windows`' walk over the query rows alone
+through `timhip_stack_query_maps`, the weights kernel reading layer l's keys from the cache through the window index - the maps'
+first axis is then the query group, their feature columns those of the group's own window."""
 import ctypes as C
 
 import torch
@@ -51,7 +54,8 @@ def resolve_rows(rows, F):
 
 class AttentionMaps:
     """The maps of one call.  `layers`: the layer indices, ascending; `weights[l]`: fp32 [B, S - s0, F + 1]; `F`, `S`, `s0`: the
-    layout (row i = token s0 + i)."""
+    layout (row i = token s0 + i).  Maps of a `WindowCache` (`query_attention_maps`): B = the query groups, s0 = F, S = F + the
+    queries per group; with per_head=True there `weights[l]` is [G, H, S - s0, F + 1] and every view keeps the head axis."""
 
     def __init__(self, layers, weights, F, S, s0, heads=(), num_feats=None):
         self.layers = list(layers)
@@ -60,8 +64,9 @@ class AttentionMaps:
         self._heads = {h[0]: (h[2], h[3]) for h in heads}     # output slot -> (first token row, rows): EncoderPlan.heads
         self._nf = num_feats                                  # feature tokens per modality of an audio-visual model, or None
         for w in self.weights.values():
-            if w.dim() != 3 or w.shape[1] != self.S - self.s0 or w.shape[2] != self.F + 1:
+            if w.dim() not in (3, 4) or w.shape[-2] != self.S - self.s0 or w.shape[-1] != self.F + 1:
                 raise ValueError("a map is [B, S - s0, F + 1] = [B, %d, %d], not %s" % (self.S - self.s0, self.F + 1, tuple(w.shape)))
+        self.per_head = any(w.dim() == 4 for w in self.weights.values())
 
     def _w(self, layer):
         if layer is None:
@@ -74,13 +79,13 @@ class AttentionMaps:
         """[B, S - s0, S] as the reference lays its rows out: feature columns copied, the self column on the diagonal, zeros
         elsewhere"""
         w = self._w(layer)
-        B, n, F, S, s0 = w.shape[0], self.S - self.s0, self.F, self.S, self.s0
-        dense = w.new_zeros((B, n, S))
-        dense[:, :, :F] = w[:, :, :F]
+        n, F, S, s0 = self.S - self.s0, self.F, self.S, self.s0
+        dense = w.new_zeros(tuple(w.shape[:-2]) + (n, S))
+        dense[..., :F] = w[..., :F]
         first = max(F, s0)                                    # query rows: token s sits in row s - s0 and owns column s
         if first < S:
             tok = torch.arange(first, S, device=w.device)
-            dense[:, tok - s0, tok] = w[:, first - s0:, F]
+            dense[..., tok - s0, tok] = w[..., first - s0:, F]
         return dense
 
     def for_head(self, name, layer=None):
@@ -90,14 +95,14 @@ class AttentionMaps:
         start, n = self._heads[name]
         if start < self.s0:
             raise ValueError("rows of head %r start at token %d, the maps at token %d" % (name, start, self.s0))
-        return self._w(layer)[:, start - self.s0:start - self.s0 + n]
+        return self._w(layer)[..., start - self.s0:start - self.s0 + n, :]
 
     def split_modalities(self, layer=None):
         """(visual, audio): the two halves of the feature columns of an audio-visual model, [B, S - s0, num_feats] each"""
         if self._nf is None:
             raise ValueError("split_modalities: the model has one input modality")
         w = self._w(layer)
-        return w[:, :, :self._nf], w[:, :, self._nf:self.F]
+        return w[..., :self._nf], w[..., self._nf:self.F]
 
 
 class MapRequest:
@@ -142,3 +147,46 @@ class MapRequest:
         cfg = model.cfg
         nf = cfg.num_feats if cfg.input_modality == "audio_visual" else None
         self.result = AttentionMaps(self.layers, bufs, q.F, q.S, self.s0, heads=q.plan.heads, num_feats=nf)
+
+
+class QueryMapRequest:
+    """What one `query_attention_maps` call asks of `query.query`, and its result: the maps of the query rows of G groups against
+    a `WindowCache`, [G, Q, F + 1] (per_head: [G, H, Q, F + 1]) for every layer asked for"""
+
+    def __init__(self, model, layers, per_head=False, out=None):
+        if model.training:
+            raise ValueError("query_attention_maps is an evaluation call: model.eval() first (no dropout, no backward through a "
+                             "window cache)")
+        self.layers = resolve_layers(layers, model.cfg.num_layers)
+        self.per_head = bool(per_head)
+        self.out = out
+        self.result = None
+
+    def _buffers(self, G, Q, F, H, dev):
+        n, shape = len(self.layers), ((G, H, Q, F + 1) if self.per_head else (G, Q, F + 1))
+        out = self.out
+        if out is None:
+            return list(torch.empty((n,) + shape, dtype=torch.float32, device=dev).unbind(0))
+        if isinstance(out, AttentionMaps):
+            if out.layers != self.layers:
+                raise ValueError("out: maps of layers %r, this call asks for %r" % (out.layers, self.layers))
+            out = [out.weights[l] for l in self.layers]
+        bufs = list(out)
+        if len(bufs) != n:
+            raise ValueError("out: %d buffers for %d layers" % (len(bufs), n))
+        for t in bufs:
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != dev \
+                    or not t.is_contiguous():
+                raise ValueError("out: every buffer is a contiguous fp32 %s tensor on %s" % (shape, dev))
+        return bufs
+
+    def run(self, model, q, plan, desc, nlayers, layers, cache, widx, x0_f, x0_t, xL_f, xL_t, ws, ws_bytes):
+        """timhip_stack_query with the maps of the requested layers (NULL for every other layer)"""
+        cfg = model.cfg
+        bufs = self._buffers(q.B, q.S, cache.F, cfg.nhead, q.dev)
+        by_layer = dict(zip(self.layers, bufs))
+        maps = (C.c_void_p * nlayers)(*[ptr(by_layer[l]) if l in by_layer else None for l in range(nlayers)])
+        call("timhip_stack_query_maps", C.byref(desc), nlayers, layers, ptr(cache.kv), cache.W, ptr(widx), ptr(x0_f), ptr(x0_t),
+             ptr(xL_f), ptr(xL_t), maps, int(self.per_head), cache.F + 1, ptr(ws), ws_bytes, q.st)
+        nf = cfg.num_feats if cfg.input_modality == "audio_visual" else None
+        self.result = AttentionMaps(self.layers, bufs, cache.F, cache.F + q.S, cache.F, heads=plan.full.heads, num_feats=nf)

@@ -595,9 +595,12 @@ size_t timhip_stack_query_workspace_bytes(const TimDesc* d, int nlayers) {
   return (d && check_query_desc(*d) == TIMHIP_OK) ? infer_layout(*d, 0).total : 0;
 }
 
-int timhip_stack_query(const TimDesc* dp, int nlayers, const TimLayerParams* layers, const void* cache, int W, const int* widx,
-                       const float* xq_in, const void* xq_in_T, float* xq_out, void* xq_out_T, void* workspace,
-                       size_t workspace_bytes, void* stream) {
+// The one body of timhip_stack_query and timhip_stack_query_maps.  maps (HOST array of nlayers device pointers, or NULL): behind
+// layer l's launches - the in-projection of the query rows is live in the arena until layer l + 1's - the weights kernel writes
+// maps[l] from those rows and the K columns of cache block l.
+static int stack_query_body(const TimDesc* dp, int nlayers, const TimLayerParams* layers, const void* cache, int W, const int* widx,
+                            const float* xq_in, const void* xq_in_T, float* xq_out, void* xq_out_T, float* const* maps,
+                            int per_head, int ld, void* workspace, size_t workspace_bytes, void* stream) {
   if (!dp || !layers || nlayers <= 0 || !cache || !xq_in || !xq_in_T || !xq_out_T || !workspace) return TIMHIP_EINVAL;
   TimDesc d = *dp;
   int rc = check_query_desc(d);
@@ -605,6 +608,11 @@ int timhip_stack_query(const TimDesc* dp, int nlayers, const TimLayerParams* lay
   if (d.p_drop != 0.f || W <= 0 || (!widx && d.B != W)) return TIMHIP_EINVAL;
   if (d.F > 192) return TIMHIP_EUNSUPPORTED;   // (the attention kernels' key limit; refused here, before the first launch)
   if (((uintptr_t)cache & 15) != 0) return TIMHIP_EALIGN;
+  if (maps) {   // refused before the first launch, like everything above
+    if (ld < d.F + 1) return TIMHIP_EINVAL;
+    for (int l = 0; l < nlayers; ++l)
+      if (((uintptr_t)maps[l] & 3) != 0) return TIMHIP_EALIGN;
+  }
   const InferLayout L = infer_layout(d, 0);
   if (workspace_bytes < L.total) return TIMHIP_EWORKSPACE;
   hipStream_t s = (hipStream_t)stream;
@@ -621,8 +629,28 @@ int timhip_stack_query(const TimDesc* dp, int nlayers, const TimLayerParams* lay
                              l ? layers[l - 1].n2_w : nullptr, l ? layers[l - 1].n2_b : nullptr,
                              l == 0 ? xq_in_T : (const void*)L.xt.at(ws), last ? xq_out : nullptr,
                              last ? xq_out_T : (void*)L.xt.at(ws), bufs, 0, s))) return rc;
+    if (maps && maps[l] &&
+        (rc = tim_attention_query_weights(d, bufs.qkv, bufs.kv, bufs.ldkv, bufs.wrows, W, widx, per_head, maps[l], ld, s))) return rc;
   }
   return TIMHIP_OK;
+}
+
+int timhip_stack_query(const TimDesc* dp, int nlayers, const TimLayerParams* layers, const void* cache, int W, const int* widx,
+                       const float* xq_in, const void* xq_in_T, float* xq_out, void* xq_out_T, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+  return stack_query_body(dp, nlayers, layers, cache, W, widx, xq_in, xq_in_T, xq_out, xq_out_T, nullptr, 0, 0, workspace,
+                          workspace_bytes, stream);
+}
+
+// (the maps are the caller's buffers: the arena is timhip_stack_query's)
+size_t timhip_stack_query_maps_workspace_bytes(const TimDesc* d, int nlayers) { return timhip_stack_query_workspace_bytes(d, nlayers); }
+
+int timhip_stack_query_maps(const TimDesc* dp, int nlayers, const TimLayerParams* layers, const void* cache, int W, const int* widx,
+                            const float* xq_in, const void* xq_in_T, float* xq_out, void* xq_out_T, float* const* maps,
+                            int per_head, int ld, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!maps) return TIMHIP_EINVAL;
+  return stack_query_body(dp, nlayers, layers, cache, W, widx, xq_in, xq_in_T, xq_out, xq_out_T, maps, per_head, ld, workspace,
+                          workspace_bytes, stream);
 }
 
 size_t timhip_layer_ln_partial_bytes(const TimDesc* d) { return d ? 2 * tim_layernorm_bwd_ws(d->B * d->S, d->E) : 0; }

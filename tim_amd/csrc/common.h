@@ -504,6 +504,10 @@ int tim_attention_weights(const TimDesc& d, const void* qkv, int s0, int per_hea
 // of a cache - kv: K of row 0 of window 0, V E elements behind it, row pitch ldkv, wrows rows per window, W windows
 int tim_attention_query_fwd(const TimDesc& d, const void* qkv_q, const void* kv, int ldkv, int wrows, int W, const int* widx, void* o,
                             hipStream_t s);
+// attn_maps.hip: the attention weights of those rows (tim_attention_weights' bodies, keys through the window index): w[g S + i, 0 .. F]
+// fp32, row pitch ld; per_head: [G, H, S, ld]
+int tim_attention_query_weights(const TimDesc& d, const void* qkv_q, const void* kv, int ldkv, int wrows, int W, const int* widx,
+                                int per_head, float* w, int ld, hipStream_t s);
 
 // operand storage: bf16 for TIMHIP_PREC_BF16, fp16 for TIMHIP_PREC_F16, fp32 for TIMHIP_PREC_FP32 and TIMHIP_PREC_BF16X3
 static inline bool h16_storage(int precision) { return precision == TIMHIP_PREC_BF16 || precision == TIMHIP_PREC_F16; }

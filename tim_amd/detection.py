@@ -192,6 +192,19 @@ class TIM(_TIMBase):
         """Segments [G, Nq, 2] in window coordinates against the cached windows -> (cls_scores, reg_scores) as `forward_inference`
         returns them (they feed `DetectionCollector` unchanged).  None: the model's own inference pyramid, for each modality in
         `data_modality`.  window_index, validate, errors: as the recognition model's `query_windows`."""
+        return self._query_windows(cache, v_queries, a_queries, window_index, validate, None)
+
+    def query_attention_maps(self, cache, v_queries=None, a_queries=None, window_index=None, layers="last", per_head=False,
+                             out=None, validate=True):
+        """-> (outputs, maps): `outputs` is `query_windows(cache, v_queries, a_queries, window_index, validate)`'s return value bit
+        for bit; `maps` the attention weights of the layers asked for, [G, Q, F + 1] - one row per query, visual queries first and
+        then audio (None: the model's own pyramid), over the feature tokens of the group's own window and the query's own key.
+        layers, per_head, out: as the recognition model's `query_attention_maps`."""
+        from .attn_maps import QueryMapRequest
+        req = QueryMapRequest(self, layers, per_head, out)
+        return self._query_windows(cache, v_queries, a_queries, window_index, validate, req), req.result
+
+    def _query_windows(self, cache, v_queries, a_queries, window_index, validate, maps):
         from . import query
         query._need_eval(self, "query_windows")
         query.check_cache(self, cache)
@@ -228,7 +241,7 @@ class TIM(_TIMBase):
         _require_gpu(cache.kv, "query_windows")
         with torch.no_grad():
             te_q = self._time_mlp(torch.concat(parts, dim=1).contiguous())
-        o = query.query(self, cache, te_q, nv, na, widx, validate=False)   # (the index was judged above)
+        o = query.query(self, cache, te_q, nv, na, widx, validate=False, maps=maps)   # (the index was judged above)
         return (o.get("verb"), o.get("noun"), o.get("action"), o.get("audio")), (o.get("reg_visual"), o.get("reg_audio"))
 
     def forward_encoder(self, inputs, feature_times, target, label_queries=False):

@@ -156,9 +156,10 @@ def check_query_encodings(model, te_q, nv, na):
                          % (te_q.shape[1], nv + na))
 
 
-def query(model, cache, te_q, nv, na, window_index=None, validate=True):
+def query(model, cache, te_q, nv, na, window_index=None, validate=True, maps=None):
     """all layers on the query rows of G groups against `cache` -> the encoder's outputs by slot (dict; no `feats`).
-    te_q: [G, nv + na, d] time encodings of the queries, visual first."""
+    te_q: [G, nv + na, d] time encodings of the queries, visual first.  maps (an attn_maps.QueryMapRequest:
+    `model.query_attention_maps`): the same walk through timhip_stack_query_maps, which also writes the requested layers' maps."""
     _need_eval(model, "query_windows")
     check_cache(model, cache)
     check_query_encodings(model, te_q, nv, na)
@@ -181,8 +182,11 @@ def query(model, cache, te_q, nv, na, window_index=None, validate=True):
         xL_t = torch.empty((q.M, q.E), dtype=rt.op_dtype, device=q.dev)
         ws_bytes = L.load().timhip_stack_query_workspace_bytes(C.byref(desc), Lyr)
         ws = model._workspace(ws_bytes, q.dev, slot="query")
-        L.call("timhip_stack_query", C.byref(desc), Lyr, layers, L.ptr(cache.kv), cache.W, L.ptr(widx), L.ptr(x0_f), L.ptr(x0_t),
-               L.ptr(xL_f), L.ptr(xL_t), L.ptr(ws), ws_bytes, q.st)
+        if maps is not None:
+            maps.run(model, q, plan, desc, Lyr, layers, cache, widx, x0_f, x0_t, xL_f, xL_t, ws, ws_bytes)
+        else:
+            L.call("timhip_stack_query", C.byref(desc), Lyr, layers, L.ptr(cache.kv), cache.W, L.ptr(widx), L.ptr(x0_f), L.ptr(x0_t),
+                   L.ptr(xL_f), L.ptr(xL_t), L.ptr(ws), ws_bytes, q.st)
         outs = {}
         Fn._heads_fwd(q, P, xL_f, xL_t, outs)
         Fn._reg_heads_fwd(q, P, xL_t, outs)

@@ -559,6 +559,23 @@ class TIM(nn.Module):
         o = query.query(self, cache, query_time_encodings, int(num_v_queries or 0), int(num_a_queries or 0), window_index, validate)
         return (o.get("verb"), o.get("noun"), o.get("action"), o.get("audio"))
 
+    def query_attention_maps(self, cache, query_time_encodings, num_v_queries, num_a_queries, window_index=None, layers="last",
+                             per_head=False, out=None, validate=True):
+        """-> (outputs, maps): `outputs` is what `query_windows(cache, query_time_encodings, num_v_queries, num_a_queries,
+        window_index, validate)` returns, bit for bit (the same launches; the weights kernels only read); `maps` an
+        `attn_maps.AttentionMaps` whose first axis is the query group: for every layer asked for the weights [G, Q, F + 1] of the
+        group's queries over the F feature tokens of ITS window (columns 0 .. F - 1) and the query's own key (column F); s0 = F,
+        `for_head`, `split_modalities` and `to_dense` as for `attention_maps(..., rows="queries")`.  layers: "last", "all" or a
+        list of layer indices; per_head: [G, H, Q, F + 1], no mean over the heads; out: the `AttentionMaps` of an earlier call
+        with the same arguments and groups (or its list of buffers) to write into - fixed addresses for a captured graph.
+        `query_windows`' conditions and errors apply."""
+        from . import query
+        from .attn_maps import QueryMapRequest
+        req = QueryMapRequest(self, layers, per_head, out)
+        o = query.query(self, cache, query_time_encodings, int(num_v_queries or 0), int(num_a_queries or 0), window_index, validate,
+                        maps=req)
+        return (o.get("verb"), o.get("noun"), o.get("action"), o.get("audio")), req.result
+
     def _time_mlp(self, times):
         m = self.time_mlp
         return TimeMlpFn.apply(self.rt, times, m[0].weight, m[0].bias, m[2].weight, m[2].bias, m[4].weight,

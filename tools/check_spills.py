@@ -39,6 +39,7 @@ BUDGET = {
     "attention_query.hip": [(r"attn_query_mfma", 0)],   # attn_fwd_mfma's body on query rows (attention.h): the same registers
     # the attention-weights kernels: the scores of a head and the running head mean both live in registers (202 VGPRs at head width
     # 128, F = 100; 229 at five key blocks) - scratch traffic would sit inside the loop over the heads
+    # (their QRY = true instances - keys read through a window index, timhip_attention_query_weights - match the same two patterns)
     "attn_maps.hip": [(r"attn_w_mfma", 0), (r"attn_w_generic", 0)],
     # the fp16 fused backward (C2a / C3 / C4), with the kernel's own draws and with the keep-bits of round 6
     "attention_bwd2.hip": [(r"attn_bwd_rowsIDF16_Li128ELi4ELb1E", 0), (r"attn_bwd_rowsIDF16[_b]Li128ELi4ELb1ELb1ELb1E", 0),
