@@ -55,7 +55,10 @@ def __getattr__(name):  # lazy: importing the package must not require torch on 
     if name == "DrlocPositions":
         from .losses import DrlocPositions
         return DrlocPositions
-    if name in ("optim", "mixup"):
+    if name == "CosineWarmupSchedule":
+        from .schedule import CosineWarmupSchedule
+        return CosineWarmupSchedule
+    if name in ("optim", "mixup", "schedule"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

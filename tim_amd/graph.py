@@ -65,11 +65,15 @@ class GraphedStep:
     """Capture `fn()` - a closure over static input tensors - once and replay it.
 
     fn      callable without arguments running forward + backward (+ anything else that is capturable) of `model`
-    warmup  eager runs on a side stream before capture (allocator warm-up, weight copies, gradient buckets)
+    warmup  eager runs on a side stream before capture (allocator warm-up, weight copies, gradient buckets).  They are real
+            steps: with an optimizer inside `fn` they update the weights and advance its step count, the sampler, mixup - and a
+            `tim_amd.schedule.CosineWarmupSchedule` attached to it, whose counter stands at `warmup` when the first replay runs
+            (`sched.set_step(0)` after construction starts the curve at the first replay instead)
     count_nodes  keep the captured hipGraph until it has been walked: `kernel_nodes` / `nodes` = the launches of one step,
             counted (hipGraphGetNodes + hipGraphNodeGetType), not assumed (bench.py's `launches_per_step`)
     optimizer  a `tim_amd.optim.FusedAdamW` whose `step()` `fn` calls inside the capture: its learning rate is pushed to the
-            device before every replay (a scheduler's host-side write takes effect), the non-finite words of the captured
+            device before every replay (a scheduler's host-side write takes effect; with a CosineWarmupSchedule attached it is
+            that schedule's rate of the coming replay, which counts one iteration), the non-finite words of the captured
             backward passes decide on the device whether a replayed update is skipped, and the captured update writes the
             operand copies, so the cast at the head of the captured step is recorded only for what the update does not cover
     """

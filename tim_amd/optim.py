@@ -71,7 +71,11 @@ class FusedAdamW(torch.optim.Optimizer):
 
     One step count per parameter group (torch keeps one per parameter; they differ only when a parameter sat out some steps
     without a gradient, which `state_dict()` cannot express here: every parameter reports its group's count).
-    `last_grad_norm`, `skipped_steps`, `found_inf` are device tensors: reading them is the caller's synchronisation."""
+    `last_grad_norm`, `skipped_steps`, `found_inf` are device tensors: reading them is the caller's synchronisation.
+
+    The learning rate is the host number `group["lr"]`, copied into the state block when it changed (before an eager step, and by
+    `GraphedStep` before every replay) - unless a `tim_amd.schedule.CosineWarmupSchedule` is attached: then the same two places
+    write the schedule's rate of that iteration, every step counts one iteration, and `group["lr"]` is not read."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None, runtime=None,
                  amsgrad=False, maximize=False):
@@ -100,6 +104,8 @@ class FusedAdamW(torch.optim.Optimizer):
         self._cpu_stats = None
         self.extra_flags = []    # 1-element 32-bit tensors: a non-zero word skips the step (a caller's own non-finite watch)
         self._capture_since = 0  # GraphedStep: first of the runtime's captured flag blocks that belongs to the capture in progress
+        self._schedule = None    # a tim_amd.schedule.CosineWarmupSchedule: its rates go to the LR words, `group["lr"]` is not pushed
+        self._replay_pushes = False   # a GraphedStep pushes the schedule's rate before every replay (before_capture was called)
 
     @classmethod
     def for_model(cls, model, **kw):
@@ -114,6 +120,11 @@ class FusedAdamW(torch.optim.Optimizer):
             return self._cpu_stats[word]
         row = self._blocks[0]
         return row.view(torch.int32)[word] if as_int else row[word]
+
+    @property
+    def device_lr(self):
+        """the LR words of the state blocks, one per group: the rates the latest GPU step read (None before the first)"""
+        return None if self._blocks is None else self._blocks[:, L.OPT_LR]
 
     @property
     def last_grad_norm(self):
@@ -193,11 +204,13 @@ class FusedAdamW(torch.optim.Optimizer):
 
     def _step_cpu(self, live):
         groups = []
+        sch = self._schedule
+        lrs = None if sch is None else sch._next_rates()    # (the attached schedule's rates; a skipped step counts too, as in the reference)
         for gi, (grp, ps) in enumerate(zip(self.param_groups, live)):
             mv = [self._moments(p) for p in ps]
             groups.append({"params": ps, "grads": [p.grad for p in ps], "exp_avg": [a for a, _ in mv], "exp_avg_sq": [b for _, b in mv],
-                           "lr": grp["lr"], "betas": grp["betas"], "eps": grp["eps"], "weight_decay": grp["weight_decay"],
-                           "state": self._steps[gi]})
+                           "lr": grp["lr"] if lrs is None else lrs[gi], "betas": grp["betas"], "eps": grp["eps"],
+                           "weight_decay": grp["weight_decay"], "state": self._steps[gi]})
         flagged = any(bool(f.view(torch.int32).ne(0).any()) for f in self.extra_flags)
         norm, coef, bad = reference_step(groups, self.param_groups[0]["max_grad_norm"], found_inf=flagged)
         self._cpu_stats = {L.OPT_NORM: norm.float(), L.OPT_COEF: coef.float(), L.OPT_FOUND_INF: torch.tensor(int(bad), dtype=torch.int32),
@@ -236,11 +249,16 @@ class FusedAdamW(torch.optim.Optimizer):
         partials = torch.empty(max(1, n_part), dtype=torch.float64, device=dev)
         return {"groups": tables, "n_part": n_part, "partials": partials}
 
-    def _push_lr(self):
-        """host `group["lr"]` -> the state blocks' LR words when it changed (a scheduler's write); no synchronisation"""
+    def _push_lr(self, lrs=None):
+        """host `group["lr"]` -> the state blocks' LR words when it changed (a scheduler's write); no synchronisation.
+        With a schedule attached the LR words are the schedule's: `group["lr"]` is not pushed on any path, only the rates the
+        schedule hands over (`lrs`)."""
         if self._blocks is None:
             return
-        lrs = [float(g["lr"]) for g in self.param_groups]
+        if lrs is None:
+            if self._schedule is not None:
+                return
+            lrs = [float(g["lr"]) for g in self.param_groups]
         if lrs != self._lr_pushed:
             for gi, lr in enumerate(lrs):
                 if self._lr_pushed is None or self._lr_pushed[gi] != lr:
@@ -277,7 +295,14 @@ class FusedAdamW(torch.optim.Optimizer):
                 words[gi, L.OPT_STEP], words[gi, L.OPT_SKIPPED] = st["step"], st["skipped"]
             self._blocks = words.to(dev).view(torch.float32)
             self._lr_pushed = None
-        if not capturing:    # (a captured fill would freeze the rate: GraphedStep pushes it before every replay)
+        if self._schedule is not None:
+            if not capturing:
+                self._push_lr(self._schedule._next_rates())
+            elif not self._replay_pushes:
+                raise RuntimeError("FusedAdamW: a step with a CosineWarmupSchedule attached is captured through "
+                                   "tim_amd.graph.GraphedStep(..., optimizer=opt), which writes the rate before every replay; a "
+                                   "bare capture would replay the rate it was captured with")
+        elif not capturing:    # (a captured fill would freeze the rate: GraphedStep pushes it before every replay)
             self._push_lr()
         copies = self._copies_of(dev)
         sig = tuple((p.data_ptr(), p.grad.data_ptr()) + tuple(t.data_ptr() for t in copies.get(p.data_ptr(), (0,))[1:])
@@ -328,6 +353,7 @@ class FusedAdamW(torch.optim.Optimizer):
         feed the captured update."""
         self._capture_since = since
         self._push_lr()
+        self._replay_pushes = True
         rt = self.rt
         if rt is None:
             return
@@ -337,9 +363,10 @@ class FusedAdamW(torch.optim.Optimizer):
         rt.copies.invalidate(keep=covered)
 
     def before_replay(self):
-        """the learning rate a scheduler wrote since the last replay, and a refresh of copies somebody invalidated between
+        """the learning rate a host scheduler wrote since the last replay - with a CosineWarmupSchedule attached, the rate of the
+        coming replay, which is counted here - and a refresh of copies somebody invalidated between
         replays (`load_state_dict`, `invalidate_weights()`): the captured step itself no longer casts them"""
-        self._push_lr()
+        self._push_lr(None if self._schedule is None else self._schedule._next_rates())
         rt = self.rt
         if rt is None or self._tables is None:
             return
