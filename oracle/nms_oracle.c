@@ -40,9 +40,12 @@ int64_t nms_1d_oracle(const float* segs, const int64_t* order, int64_t n, float 
 }
 
 /* nms_cpu.cpp:69-170.  dets [n,3] receives (x1, x2, score-at-selection) of the selected segments in selection order,
- * inds [n] their original indices; returns the number selected.  method: 0 vanilla, 1 linear, 2 gaussian. */
-int64_t softnms_1d_oracle(const float* segs, const float* scores, int64_t n, float iou_threshold, float sigma,
-                          float min_score, int method, float* dets, int64_t* inds) {
+ * inds [n] their original indices; returns the number selected.  method: 0 vanilla, 1 linear, 2 gaussian.
+ * exp_rn: 0 = the gaussian weight is glibc's expf (the reference's arithmetic on this host); 1 = exp() evaluated in double and
+ * rounded to float, which is what tim_amd/csrc/nms.hip computes.  pruned_per_step (nullable, [n]): entry i receives the number
+ * of elements selection step i pruned (entries at and beyond the returned count stay untouched). */
+static int64_t softnms_1d_impl(const float* segs, const float* scores, int64_t n, float iou_threshold, float sigma,
+                               float min_score, int method, int exp_rn, float* dets, int64_t* inds, int64_t* pruned_per_step) {
   if (n == 0) return 0;
   float* x1 = (float*)malloc(sizeof(float) * (size_t)n);
   float* x2 = (float*)malloc(sizeof(float) * (size_t)n);
@@ -67,6 +70,7 @@ int64_t softnms_1d_oracle(const float* segs, const float* scores, int64_t n, flo
     x1[max_pos] = x1[i]; x2[max_pos] = x2[i]; sc[max_pos] = sc[i]; areas[max_pos] = areas[i]; inds[max_pos] = inds[i];
     x1[i] = ix1; x2[i] = ix2; sc[i] = iscore; areas[i] = iarea; inds[i] = iind;
     int64_t pos = i + 1;
+    const int64_t before = nsegs;
     while (pos < nsegs) {
       const float xx1 = fmaxf(ix1, x1[pos]), xx2 = fminf(ix2, x2[pos]);
       const float inter = fmaxf(0.f, xx2 - xx1);
@@ -74,7 +78,10 @@ int64_t softnms_1d_oracle(const float* segs, const float* scores, int64_t n, flo
       float weight = 1.f;
       if (method == 0) { if (ovr >= iou_threshold) weight = 0.f; }
       else if (method == 1) { if (ovr >= iou_threshold) weight = 1.f - ovr; }
-      else if (method == 2) { weight = expf(-(ovr * ovr) / sigma); }
+      else if (method == 2) {
+        const float x = -(ovr * ovr) / sigma;
+        weight = exp_rn ? (float)exp((double)x) : expf(x);
+      }
       sc[pos] *= weight;
       if (sc[pos] < min_score) {
         x1[pos] = x1[nsegs - 1]; x2[pos] = x2[nsegs - 1]; sc[pos] = sc[nsegs - 1]; areas[pos] = areas[nsegs - 1];
@@ -84,7 +91,31 @@ int64_t softnms_1d_oracle(const float* segs, const float* scores, int64_t n, flo
       }
       pos = pos + 1;
     }
+    if (pruned_per_step) pruned_per_step[i] = before - nsegs;
   }
   free(x1); free(x2); free(sc); free(areas);
   return nsegs;
+}
+
+/* The entry every caller has used so far keeps its nine arguments: a caller built against them passes no tenth one. */
+int64_t softnms_1d_oracle(const float* segs, const float* scores, int64_t n, float iou_threshold, float sigma,
+                          float min_score, int method, float* dets, int64_t* inds) {
+  return softnms_1d_impl(segs, scores, n, iou_threshold, sigma, min_score, method, 0, dets, inds, NULL);
+}
+
+/* the same routine with the gaussian weight as (float)exp((double)x): the arithmetic of the HIP kernel, stated on the CPU */
+int64_t softnms_1d_oracle_rn(const float* segs, const float* scores, int64_t n, float iou_threshold, float sigma,
+                             float min_score, int method, float* dets, int64_t* inds) {
+  return softnms_1d_impl(segs, scores, n, iou_threshold, sigma, min_score, method, 1, dets, inds, NULL);
+}
+
+/* both of them with the nullable pruned_per_step [n] as a tenth argument */
+int64_t softnms_1d_oracle_pruned(const float* segs, const float* scores, int64_t n, float iou_threshold, float sigma,
+                                 float min_score, int method, float* dets, int64_t* inds, int64_t* pruned_per_step) {
+  return softnms_1d_impl(segs, scores, n, iou_threshold, sigma, min_score, method, 0, dets, inds, pruned_per_step);
+}
+
+int64_t softnms_1d_oracle_rn_pruned(const float* segs, const float* scores, int64_t n, float iou_threshold, float sigma,
+                                    float min_score, int method, float* dets, int64_t* inds, int64_t* pruned_per_step) {
+  return softnms_1d_impl(segs, scores, n, iou_threshold, sigma, min_score, method, 1, dets, inds, pruned_per_step);
 }

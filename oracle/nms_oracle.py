@@ -20,9 +20,11 @@ def _load():
         _lib = C.CDLL(so)
         _lib.nms_1d_oracle.restype = C.c_int64
         _lib.nms_1d_oracle.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p]
-        _lib.softnms_1d_oracle.restype = C.c_int64
-        _lib.softnms_1d_oracle.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int,
-                                           C.c_void_p, C.c_void_p]
+        nine = [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p]
+        for fn in (_lib.softnms_1d_oracle, _lib.softnms_1d_oracle_rn):
+            fn.restype, fn.argtypes = C.c_int64, nine
+        for fn in (_lib.softnms_1d_oracle_pruned, _lib.softnms_1d_oracle_rn_pruned):      # + the nullable pruned_per_step
+            fn.restype, fn.argtypes = C.c_int64, nine + [C.c_void_p]
     return _lib
 
 
@@ -39,15 +41,25 @@ def nms_1d(segs, scores, iou_threshold, order=None):
     return keep[:m]
 
 
-def softnms_1d(segs, scores, iou_threshold, sigma, min_score, method):
-    """nms_cpu.cpp:69-170 -> (inds [m], dets [m,3])"""
+def softnms_1d(segs, scores, iou_threshold, sigma, min_score, method, exp="glibc", return_pruned=False):
+    """nms_cpu.cpp:69-170 -> (inds [m], dets [m,3]).  exp: "glibc" = the gaussian weight is expf (the reference's arithmetic on
+    this host), "rn" = exp() in double rounded to float (the arithmetic of tim_amd/csrc/nms.hip); methods 0 and 1 evaluate no
+    exponential and are the same in both.  return_pruned: also return pruned [m] (int64), the number of elements each selection
+    step pruned."""
     segs = np.ascontiguousarray(segs, dtype=np.float32)
     scores = np.ascontiguousarray(scores, dtype=np.float32)
     n = segs.shape[0]
     dets = np.zeros((n, 3), dtype=np.float32)
     inds = np.empty(n, dtype=np.int64)
-    m = _load().softnms_1d_oracle(segs.ctypes.data, scores.ctypes.data, n, float(iou_threshold), float(sigma),
-                                  float(min_score), int(method), dets.ctypes.data, inds.ctypes.data)
+    pruned = np.zeros(n, dtype=np.int64) if return_pruned else None
+    args = (segs.ctypes.data, scores.ctypes.data, n, float(iou_threshold), float(sigma), float(min_score), int(method),
+            dets.ctypes.data, inds.ctypes.data)
+    if return_pruned:
+        fn = {"glibc": _load().softnms_1d_oracle_pruned, "rn": _load().softnms_1d_oracle_rn_pruned}[exp]
+        m = fn(*args, pruned.ctypes.data)
+        return inds[:m], dets[:m], pruned[:m]
+    fn = {"glibc": _load().softnms_1d_oracle, "rn": _load().softnms_1d_oracle_rn}[exp]
+    m = fn(*args)
     return inds[:m], dets[:m]
 
 

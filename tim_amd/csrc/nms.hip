@@ -5,15 +5,19 @@
 // Parallelism: the groups (one per video x class) are independent -> one wavefront per group (8 for groups of more
 // than 1024 segments, 16 beyond 4096), thousands in flight.
 // Inside a group soft-NMS is a sequential selection (pick the current maximum, decay the rest, prune), so the wave runs
-// the outer loop and its 64 lanes share each inner pass (arg-max, decay, compaction).  The result is BIT-IDENTICAL to
-// the CPU routine, including its order-dependent details:
+// the outer loop and its 64 lanes share each inner pass (arg-max, decay, compaction).  The SELECTION (indices, their order, the
+// segment columns, the counts) is identical to the CPU routine's, and with methods 0 and 1 so are the scores, bit for bit; the
+// order-dependent details it reproduces:
 //   * arg-max keeps the FIRST maximum of the current array order (strict `<` in nms_cpu.cpp:100-106);
 //   * pruning swaps the dead element with the current last one and re-examines the slot (nms_cpu.cpp:150-160), which
 //     permutes the array; the same permutation is produced in parallel: a dead slot among the first (i+1+alive) positions
 //     receives the k-th alive element counted from the end, k = the slot's rank among such dead slots.
-//   * float arithmetic in the same order.  The gaussian weight is exp() evaluated in double and rounded to float: glibc's
-//     expf (max error 0.502 ulp) and this agree except for arguments within ~0.002 ulp of a rounding boundary, whereas the
-//     1-ulp device expf differs in ~15 % of calls and, compounded over hundreds of decay steps, flips near-tied selections.
+//   * float arithmetic in the same order.  The gaussian weight (method 2) is exp() evaluated in double and rounded to float.
+//     That is NOT glibc's expf (max error 0.502 ulp) bit for bit: the scores are bit-equal to the CPU routine restated with
+//     (float)exp((double)x) (oracle/nms_oracle.c, softnms_1d_oracle_rn), and that restatement is within 8 ulp, 9.4e-7 relative,
+//     of the expf one over the test inputs, the difference compounding over the decay steps, with the same selection in every
+//     one of them (tests/test_nms_oracle.py, tests/helpers.py NMS_GLIBC_RTOL, docs/measurement_log.md 7s).  The 1-ulp device
+//     expf differs in ~15 % of calls and, compounded over hundreds of decay steps, flips near-tied selections: do not go back.
 // Working arrays live in LDS when the group fits (four size classes, one launch each) and in a global scratch otherwise.
 #include <algorithm>
 #include "common.h"
@@ -38,7 +42,7 @@ __device__ __forceinline__ float seg_weight(float ix1, float ix2, float iarea, f
   float w = 1.f;
   if (method == 0) { if (ovr >= iou_thr) w = 0.f; }
   else if (method == 1) { if (ovr >= iou_thr) w = 1.f - ovr; }
-  else { w = (float)exp((double)(-(ovr * ovr) / sigma)); }   // see the header comment: correctly rounded like glibc's expf
+  else { w = (float)exp((double)(-(ovr * ovr) / sigma)); }   // see the header comment: the oracle's "rn" mode, bit for bit
   return w;
 }
 

@@ -40,15 +40,8 @@ def grouped_nms(segs, scores, keys, iou_threshold, min_score, sigma=0.5, method=
     off = torch.zeros(G + 1, dtype=torch.int32, device=segs.device)
     off[1:] = torch.cumsum(counts, 0).to(torch.int32)
     off_host = off.cpu()
-    cnt = torch.empty(G, dtype=torch.int32, device=segs.device)
-    st = _stream()
     if nms == "soft":
-        dets = torch.empty((n, 3), dtype=torch.float32, device=segs.device)
-        inds = torch.empty(n, dtype=torch.int32, device=segs.device)
-        wsb = L.load().timhip_softnms_1d_workspace_bytes(n, G)
-        ws = torch.empty(wsb, dtype=torch.uint8, device=segs.device)
-        call("timhip_softnms_1d", ptr(segs), ptr(scores), ptr(off), off_host.data_ptr(), G, float(iou_threshold),
-             float(sigma), float(min_score), int(method), ptr(dets), ptr(inds), ptr(cnt), ptr(ws), wsb, st)
+        dets, _, cnt = _grouped_softnms_raw(segs, scores, off, off_host, iou_threshold, sigma, min_score, method)
         rows = _kept_rows(off, cnt, n)
         d = dets[rows]
         return d[:, :2].contiguous(), d[:, 2].contiguous(), keys[rows]
@@ -59,12 +52,29 @@ def grouped_nms(segs, scores, keys, iou_threshold, min_score, sigma=0.5, method=
     rel = (o - off[:-1].long()[gid[o]]).to(torch.int32).contiguous()
     keep = torch.empty(n, dtype=torch.int32, device=segs.device)
     removed = torch.empty(n, dtype=torch.uint8, device=segs.device)
-    call("timhip_nms_1d", ptr(segs), ptr(rel), ptr(off), G, float(iou_threshold), ptr(removed), ptr(keep), ptr(cnt), st)
+    cnt = torch.empty(G, dtype=torch.int32, device=segs.device)
+    call("timhip_nms_1d", ptr(segs), ptr(rel), ptr(off), G, float(iou_threshold), ptr(removed), ptr(keep), ptr(cnt), _stream())
     if max_seg_num > 0:
         cnt = torch.clamp(cnt, max=int(max_seg_num))
     rows = _kept_rows(off, cnt, n)
     src = keep[rows].long() + off[:-1].long()[gid[rows]]
     return segs[src], scores[src], keys[src]
+
+
+def _grouped_softnms_raw(segs, scores, off, off_host, iou_threshold, sigma, min_score, method):
+    """One timhip_softnms_1d call on rows already grouped (device float32 `segs` [n,2] and `scores` [n], contiguous; `off`
+    [G+1] int32 on the device and `off_host` its host copy).  Returns the kernel's outputs untrimmed: dets [n,3] (x1, x2, score at
+    selection), inds [n] int32 (the selection's row relative to its group's first row) and count [G] int32; of group g only the
+    first count[g] rows from off[g] on are written."""
+    n, G = segs.shape[0], off.numel() - 1
+    dets = torch.empty((n, 3), dtype=torch.float32, device=segs.device)
+    inds = torch.empty(n, dtype=torch.int32, device=segs.device)
+    cnt = torch.empty(G, dtype=torch.int32, device=segs.device)
+    wsb = L.load().timhip_softnms_1d_workspace_bytes(n, G)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=segs.device)
+    call("timhip_softnms_1d", ptr(segs), ptr(scores), ptr(off), off_host.data_ptr(), G, float(iou_threshold),
+         float(sigma), float(min_score), int(method), ptr(dets), ptr(inds), ptr(cnt), ptr(ws), wsb, _stream())
+    return dets, inds, cnt
 
 
 def _kept_rows(off, cnt, n):
