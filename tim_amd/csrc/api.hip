@@ -228,6 +228,7 @@ void read_knobs(TimKnobs& k) {
   k.gemm_p8 = env_int("TIMHIP_GEMM_P8", k.gemm_p8);
   k.ln_pair = env_int("TIMHIP_LN_PAIR", k.ln_pair);
   k.epi_pair = env_int("TIMHIP_EPI_PAIR", k.epi_pair);
+  k.epi_g2_pk = env_int("TIMHIP_EPI_G2_PK", k.epi_g2_pk);
   k.attn_split_min = env_int("TIMHIP_ATTN_SPLIT_MIN", k.attn_split_min);
   if (k.attn_split_min < 1) k.attn_split_min = 1;
 }

@@ -322,6 +322,29 @@ __device__ __forceinline__ void gelu_both_f(float x, float& gl, float& dg) {
   dg = fmaf(x * kInvSqrt2Pi, e, ph);
 }
 
+// gelu_both_f on two elements at once: per component the SAME IEEE operations in the same order (every fused multiply-add is
+// explicit in both forms, the exponential is the v_exp_f32 of h * log2(e) that __expf issues), written on 2-vectors so that all
+// but |x|, the copysign, v_rcp_f32 and v_exp_f32 issue as v_pk_{fma,mul,add}_f32 - half the vector instructions per element
+typedef float f32x2_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f32x2_t pk_fma(f32x2_t a, f32x2_t b, f32x2_t c) { return __builtin_elementwise_fma(a, b, c); }
+__device__ __forceinline__ f32x2_t pk_set(float v) { return f32x2_t{v, v}; }
+__device__ __forceinline__ void gelu_both_f2(f32x2_t x, f32x2_t& gl, f32x2_t& dg) {
+  const float kInvSqrt2Pi = 0.3989422804014327f, kLog2e = 1.44269504088896340736f;
+  const f32x2_t z = f32x2_t{fabsf(x[0]), fabsf(x[1])} * 0.70710678118654752440f;
+  const f32x2_t den = pk_fma(pk_set(0.3275911f), z, pk_set(1.0f));
+  const f32x2_t t = {__builtin_amdgcn_rcpf(den[0]), __builtin_amdgcn_rcpf(den[1])};
+  const f32x2_t h = ((x * -0.5f) * x) * kLog2e;
+  const f32x2_t e = {__builtin_amdgcn_exp2f(h[0]), __builtin_amdgcn_exp2f(h[1])};
+  f32x2_t p = pk_fma(pk_set(1.061405429f), t, pk_set(-1.453152027f));
+  p = pk_fma(p, t, pk_set(1.421413741f));
+  p = pk_fma(p, t, pk_set(-0.284496736f));
+  p = pk_fma(p, t, pk_set(0.254829592f));
+  const f32x2_t r = pk_fma(-p * t, e, pk_set(1.0f));
+  const f32x2_t ph = (f32x2_t{copysignf(r[0], x[0]), copysignf(r[1], x[1])} + 1.0f) * 0.5f;   // Phi(x)
+  gl = x * ph;
+  dg = pk_fma(x * kInvSqrt2Pi, e, ph);
+}
+
 #include "tim_knobs.h"   // TimKnobs, tim_knobs(): the launchers' A/B knobs
 
 // Non-finite watch of the fp16 gradient path.  `out_scale` (where a kernel takes one) points at word 1 of the block

@@ -112,8 +112,9 @@ constexpr bool epi_uses_dropout(int EPI) {
          EPI == TIMHIP_EPI_GELU_DROP_G2;
 }
 
-// 4 consecutive columns n..n+3 of row m
-template <int EPI, typename T>
+// 4 consecutive columns n..n+3 of row m.  DRAW = false: an instance whose launcher guarantees keep-bits (e.mask) wherever
+// e.thr != 0 carries no Philox code
+template <int EPI, typename T, bool DRAW = true>
 __device__ __forceinline__ void epi_quad(const EpiDev& e, int m, int n, int N, float v0, float v1,
                                          float v2, float v3, bool has_pre = false,
                                          float4 pre = make_float4(0.f, 0.f, 0.f, 0.f), bool has_b = false,
@@ -129,7 +130,7 @@ __device__ __forceinline__ void epi_quad(const EpiDev& e, int m, int n, int N, f
       k0 = kpre.x; k1 = kpre.y; k2 = kpre.z; k3 = kpre.w;
     } else if (e.mask)
       drop_mask4_bits((uint32_t)e.mask[(size_t)m * e.ldmask + (n >> 3)] >> (n & 4), e.scale, k0, k1, k2, k3);
-    else
+    else if constexpr (DRAW)
       drop_mask4(e.seed, e.site, ((uint64_t)m * (uint64_t)N + (uint64_t)n) >> 2, e.thr, e.scale, k0, k1, k2, k3);
   }
   if (e.vec && n + 3 < N) {
@@ -263,7 +264,7 @@ __device__ __forceinline__ float4 epi_math4(float4 v, float4 a, float4 k) {
 }
 // 8 consecutive columns n..n+7 of row m for the epilogues that write bf16: ONE 16-byte store (and 16-byte aux load)
 // per lane instead of two 8-byte ones.  Caller guarantees e.vec8 and n + 7 < N.
-template <int EPI, typename HT>
+template <int EPI, typename HT, bool DRAW = true>
 __device__ __forceinline__ void epi_oct(const EpiDev& e, int m, int n, int N, float4 lo, float4 hi, uint32_t byte,
                                         bool has_pre = false, vec8<HT> pre = vec8<HT>{}, bool has_b = false,
                                         float4 pb0 = make_float4(0.f, 0.f, 0.f, 0.f),
@@ -273,7 +274,7 @@ __device__ __forceinline__ void epi_oct(const EpiDev& e, int m, int n, int N, fl
     if (e.mask) {   // byte = e.mask[m * ldmask + n / 8], fetched by the caller ahead of the stores (n % 8 == 0 here)
       drop_mask4_bits(byte, e.scale, klo.x, klo.y, klo.z, klo.w);
       drop_mask4_bits(byte >> 4, e.scale, khi.x, khi.y, khi.z, khi.w);
-    } else {
+    } else if constexpr (DRAW) {
       const uint64_t q = ((uint64_t)m * (uint64_t)N + (uint64_t)n) >> 2;
       drop_mask4(e.seed, e.site, q, e.thr, e.scale, klo.x, klo.y, klo.z, klo.w);
       drop_mask4(e.seed, e.site, q + 1, e.thr, e.scale, khi.x, khi.y, khi.z, khi.w);

@@ -46,13 +46,87 @@ __device__ __forceinline__ void pp_wait_lds() { asm volatile("s_waitcnt lgkmcnt(
 // PFD: how many row blocks ahead the fp32 residual (+ LayerNorm statistics) is fetched.  TMW = everything before the first
 // store (8-wave kernel, 256 VGPRs per wave); 2 = a two-deep ring refilled after each block's stores (12-wave kernel, 168 VGPRs).
 struct PpNoSync { __device__ __forceinline__ void operator()() const {} };
+
+// GELU_DROP_G2 on a wave tile that lies wholly inside M x N, 16-byte stores allowed, dropout by keep-bits (e.mask) or none
+// (e.thr == 0): pp_epilogue's G2PK form (TIMHIP_EPI_G2_PK).  What pp_epilogue -> epi_oct decide per oct is decided before the
+// call; the 2 TMW octs of a lane then run straight through, two elements per vector instruction (gelu_both_f2).  The same bits:
+//   bias     none: + (-0), which returns every x, both zeros included, as it is (+ (+0) would turn -0 into +0)
+//   keep     bit ? scale : +0 as (scale's word) AND (the bit spread over 32 bits: one v_bfe_i32); no dropout: scale = 1, all bits
+//            set - the product with 1 that epi_oct performs there as well.  Never a select of the product: g * 0 keeps g's sign
+//   order    per element the operations of epi_oct in its order; out1 stored before out0, the same cache policy
+template <typename HT, int TMW, typename AFTER>
+__device__ __forceinline__ void pp_epilogue_g2pk(const EpiDev& e, const f32x4_t (&acc)[PP_TNW][TMW], int mw0, int nw0, float* ep,
+                                                 int lane, AFTER after) {
+  constexpr int EP_LD = 64 + 4, RBS = 16;
+  const float asc = e.acc_scale ? *e.acc_scale : 1.f;
+  const int frow = lane & 15, fq = lane >> 4;
+  const int row = lane >> 3, ch = lane & 7, n = nw0 + ch * 8;   // this lane's octs: rows row, row + 8 of a row block, columns n .. n + 7
+  const bool keep = e.thr != 0u;
+  const uint32_t sbits = __float_as_uint(keep ? e.scale : 1.f);
+  uint32_t mbyte[TMW][2];
+  const uint8_t* mp = e.mask + (size_t)(mw0 + row) * e.ldmask + (n >> 3);
+  static_for<TMW>([&](auto jc) {
+    constexpr int j = decltype(jc)::value;
+#pragma unroll
+    for (int it = 0; it < 2; ++it) mbyte[j][it] = keep ? (uint32_t)mp[(size_t)(j * RBS + it * 8) * e.ldmask] : 0xffu;
+  });
+  f32x2_t b[4] = {pk_set(-0.f), pk_set(-0.f), pk_set(-0.f), pk_set(-0.f)};
+  if (e.bias) {
+    const float4 b0 = *reinterpret_cast<const float4*>(e.bias + n), b1 = *reinterpret_cast<const float4*>(e.bias + n + 4);
+    b[0] = f32x2_t{b0.x, b0.y}; b[1] = f32x2_t{b0.z, b0.w}; b[2] = f32x2_t{b1.x, b1.y}; b[3] = f32x2_t{b1.z, b1.w};
+  }
+  HT* const p0 = (HT*)e.out0 + (size_t)(mw0 + row) * e.ld0 + n;
+  HT* const p1 = (HT*)e.out1 + (size_t)(mw0 + row) * e.ld1 + n;
+  const float* const src = ep + row * EP_LD + ch * 8;
+  static_for<TMW>([&](auto jc) {
+    constexpr int j = decltype(jc)::value;
+#pragma unroll
+    for (int i = 0; i < PP_TNW; ++i) *reinterpret_cast<f32x4_t*>(ep + frow * EP_LD + i * 16 + 4 * fq) = acc[i][j] * asc;
+    pp_wait_lds();
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+      const f32x4_t lo = *reinterpret_cast<const f32x4_t*>(src + it * 8 * EP_LD);
+      const f32x4_t hi = *reinterpret_cast<const f32x4_t*>(src + it * 8 * EP_LD + 4);
+      const f32x2_t x[4] = {f32x2_t{lo[0], lo[1]} + b[0], f32x2_t{lo[2], lo[3]} + b[1], f32x2_t{hi[0], hi[1]} + b[2],
+                            f32x2_t{hi[2], hi[3]} + b[3]};
+      const uint32_t by = mbyte[j][it];
+      vec8<HT> o0, o1;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        f32x2_t g, d;
+        gelu_both_f2(x[q], g, d);
+        const f32x2_t k = {__uint_as_float(sbits & (uint32_t)((int32_t)(by << (31 - 2 * q)) >> 31)),
+                           __uint_as_float(sbits & (uint32_t)((int32_t)(by << (30 - 2 * q)) >> 31))};
+        d = d * k;
+        g = g * k;
+        o1[2 * q] = (HT)d[0]; o1[2 * q + 1] = (HT)d[1];
+        o0[2 * q] = (HT)g[0]; o0[2 * q + 1] = (HT)g[1];
+      }
+      HT* const q1 = p1 + (size_t)(j * RBS + it * 8) * e.ld1;
+      HT* const q0 = p0 + (size_t)(j * RBS + it * 8) * e.ld0;
+      if constexpr ((TIMHIP_NT_MASK & 2) != 0) __builtin_nontemporal_store(o1, reinterpret_cast<vec8<HT>*>(q1));
+      else *reinterpret_cast<vec8<HT>*>(q1) = o1;
+      if constexpr ((TIMHIP_NT_MASK & 1) != 0) __builtin_nontemporal_store(o0, reinterpret_cast<vec8<HT>*>(q0));
+      else *reinterpret_cast<vec8<HT>*>(q0) = o0;
+    }
+    pp_wait_lds();   // reads done before the next row block overwrites the region
+    after();
+  });
+}
+
 // AFTER: called after every 16-row block (the dual-group kernel keeps its barrier cadence there; default: nothing)
 // PFA (round 6): the same ring depth for the 16-bit aux rows (default: all row blocks before the first store, as before)
-template <typename HT, int EPI, int TMW, int PFD = TMW, typename AFTER = PpNoSync, int PFA = TMW>
+// G2PK (GELU_DROP_G2 only; the launcher guarantees e.mask wherever e.thr != 0): whole wave tiles take pp_epilogue_g2pk, the edge
+// tiles the code below without its Philox fallback
+template <typename HT, int EPI, int TMW, int PFD = TMW, typename AFTER = PpNoSync, int PFA = TMW, bool G2PK = false>
 __device__ __forceinline__ void pp_epilogue(const EpiDev& e, const f32x4_t (&acc)[PP_TNW][TMW], int mw0, int nw0, int M, int N,
                                             float* ep, int lane, AFTER after = AFTER{}) {
   constexpr int EP_COLS = 64, EP_LD = EP_COLS + 4, CPR = EP_COLS / 4, OPR = EP_COLS / 8, RBS = 16;
   constexpr int NITQ = RBS * CPR / 64, NITO = RBS * OPR / 64;     // 4 quads / 2 octs per lane per row block
+  static_assert(!G2PK || EPI == TIMHIP_EPI_GELU_DROP_G2, "G2PK is a form of the GELU_DROP_G2 epilogue");
+  if constexpr (G2PK) {
+    if (e.vec8 && mw0 + RBS * TMW <= M && nw0 + EP_COLS <= N) return pp_epilogue_g2pk<HT, TMW>(e, acc, mw0, nw0, ep, lane, after);
+  }
   const float asc = e.acc_scale ? *e.acc_scale : 1.f;
   const int frow = lane & 15, fq = lane >> 4;
 
@@ -154,10 +228,10 @@ __device__ __forceinline__ void pp_epilogue(const EpiDev& e, const f32x4_t (&acc
         const float4 hi = *reinterpret_cast<const float4*>(ep + row * EP_LD + ch * 8 + 4);
         const int m = mw0 + j * RBS + row, n = nw0 + ch * 8;
         if (m < M && n + 7 < N) {
-          epi_oct<EPI, HT>(e, m, n, N, lo, hi, mbyte[j][it], pre_aux, abuf[j % PFA][PRE_AUX ? it : 0], pre_b8, bias8[0], bias8[1]);
+          epi_oct<EPI, HT, !G2PK>(e, m, n, N, lo, hi, mbyte[j][it], pre_aux, abuf[j % PFA][PRE_AUX ? it : 0], pre_b8, bias8[0], bias8[1]);
         } else if (m < M) {
-          if (n < N) epi_quad<EPI, HT>(e, m, n, N, lo.x, lo.y, lo.z, lo.w);
-          if (n + 4 < N) epi_quad<EPI, HT>(e, m, n + 4, N, hi.x, hi.y, hi.z, hi.w);
+          if (n < N) epi_quad<EPI, HT, !G2PK>(e, m, n, N, lo.x, lo.y, lo.z, lo.w);
+          if (n + 4 < N) epi_quad<EPI, HT, !G2PK>(e, m, n + 4, N, hi.x, hi.y, hi.z, hi.w);
         }
       }
     } else {
@@ -173,7 +247,7 @@ __device__ __forceinline__ void pp_epilogue(const EpiDev& e, const f32x4_t (&acc
         const float4 v = *reinterpret_cast<const float4*>(ep + row * EP_LD + ch * 4);
         const int m = mw0 + j * RBS + row, n = nw0 + ch * 4;
         if (m < M && n < N)
-          epi_quad<EPI, HT>(e, m, n, N, v.x, v.y, v.z, v.w, pre_res && n + 3 < N, rbuf[j % PFD][PRE_RES ? it : 0], pre_b4 && n + 3 < N,
+          epi_quad<EPI, HT, !G2PK>(e, m, n, N, v.x, v.y, v.z, v.w, pre_res && n + 3 < N, rbuf[j % PFD][PRE_RES ? it : 0], pre_b4 && n + 3 < N,
                             bias4, pre_ln && pre_gb && n + 3 < N, sbuf[j % PFD][PRE_RES ? it : 0], lng, lnb, hk, kf);
       };
       if (has_k) {
@@ -973,7 +1047,7 @@ __device__ __forceinline__ void p8_mainloop2(const HT* __restrict__ A, const HT*
   if constexpr (G == 0) pp_barrier();   // as many barriers as group 1
 }
 
-template <typename HT, int EPI, int TM, int VAR = 0>
+template <typename HT, int EPI, int TM, int VAR = 0, bool G2PK = false>
 __global__ __launch_bounds__(512) void gemm_nt_p8_kernel(const HT* __restrict__ A, int lda, const HT* __restrict__ B, int ldb,
                                                          int M, int N, int K, EpiDev e) {
   constexpr int BM = 32 * TM, A_BYTES = BM * PP_ROWB;
@@ -1030,18 +1104,24 @@ __global__ __launch_bounds__(512) void gemm_nt_p8_kernel(const HT* __restrict__ 
   }
   __syncthreads();   // every wave is done with the buffers: they become the epilogue's transposition space
   float* ep = reinterpret_cast<float*>(lds) + wave * (16 * 68);
-  pp_epilogue<HT, EPI, TM, 2, PpNoSync, 2>(e, acc, m0 + wr * 16 * TM, n0 + wc * 64, M, N, ep, lane);
+  pp_epilogue<HT, EPI, TM, 2, PpNoSync, 2, G2PK>(e, acc, m0 + wr * 16 * TM, n0 + wc * 64, M, N, ep, lane);
 }
 
 // the eight-phase kernel, launched as the plan says (gemm_plan.h: GEMM_P8)
-template <typename HT, int EPI, int TM>
+// G2PK: the GELU_DROP_G2 instances whose whole wave tiles take pp_epilogue_g2pk (TIMHIP_EPI_G2_PK, default 1).  They carry no
+// Philox code, so a launch that draws its own keep factors (p > 0 without keep-bits) stays on the other instances - as does
+// every launch at TIMHIP_EPI_G2_PK=0; those carry nothing of the pair form
+template <typename HT, int EPI, int TM, bool G2PK = false>
 void launch_p8(const GemmPlan& p, const void* A, int lda, const void* B, int ldb, int M, int N, int K, const EpiDev& e, hipStream_t s) {
+  if constexpr (EPI == TIMHIP_EPI_GELU_DROP_G2 && !G2PK) {
+    if (tim_knobs().epi_g2_pk != 0 && (e.thr == 0u || e.mask != nullptr)) return launch_p8<HT, EPI, TM, true>(p, A, lda, B, ldb, M, N, K, e, s);
+  }
   const size_t shmem = p.lds_bytes;
   const dim3 grid(p.grid_x);
   static PerDeviceOnce attr_set;
   if (attr_set.first()) {
-    (void)hipFuncSetAttribute((const void*)gemm_nt_p8_kernel<HT, EPI, TM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-    (void)hipFuncSetAttribute((const void*)gemm_nt_p8_kernel<HT, EPI, TM, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+    (void)hipFuncSetAttribute((const void*)gemm_nt_p8_kernel<HT, EPI, TM, 0, G2PK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+    (void)hipFuncSetAttribute((const void*)gemm_nt_p8_kernel<HT, EPI, TM, 4, G2PK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
   }
 #ifdef TIMHIP_P8_VARIANTS   // experiment arms (tools/p8_ab.py with TIMHIP_GEMM_P8_VAR): plain-store fp16 instances only
   if constexpr (EPI == TIMHIP_EPI_STORE_T && sizeof(HT) == 2 && __is_same(HT, f16_t)) {
@@ -1054,9 +1134,9 @@ void launch_p8(const GemmPlan& p, const void* A, int lda, const void* B, int ldb
   }
 #endif
   if (p.phases == 2)
-    hipLaunchKernelGGL((gemm_nt_p8_kernel<HT, EPI, TM, 4>), grid, dim3(p.block), shmem, s, (const HT*)A, lda, (const HT*)B, ldb, M, N, K, e);
+    hipLaunchKernelGGL((gemm_nt_p8_kernel<HT, EPI, TM, 4, G2PK>), grid, dim3(p.block), shmem, s, (const HT*)A, lda, (const HT*)B, ldb, M, N, K, e);
   else
-    hipLaunchKernelGGL((gemm_nt_p8_kernel<HT, EPI, TM>), grid, dim3(p.block), shmem, s, (const HT*)A, lda, (const HT*)B, ldb, M, N, K, e);
+    hipLaunchKernelGGL((gemm_nt_p8_kernel<HT, EPI, TM, 0, G2PK>), grid, dim3(p.block), shmem, s, (const HT*)A, lda, (const HT*)B, ldb, M, N, K, e);
 }
 
 // ---- residual + LayerNorm fused into the epilogue (gemm_nt_ldln_kernel, round 3) ---------------------------
