@@ -229,6 +229,7 @@ void read_knobs(TimKnobs& k) {
   k.ln_pair = env_int("TIMHIP_LN_PAIR", k.ln_pair);
   k.epi_pair = env_int("TIMHIP_EPI_PAIR", k.epi_pair);
   k.epi_g2_pk = env_int("TIMHIP_EPI_G2_PK", k.epi_g2_pk);
+  k.epi_wt = env_int("TIMHIP_EPI_WT", k.epi_wt);
   k.attn_split_min = env_int("TIMHIP_ATTN_SPLIT_MIN", k.attn_split_min);
   if (k.attn_split_min < 1) k.attn_split_min = 1;
 }

@@ -190,6 +190,7 @@ struct TimSeed {
   const unsigned long long* salt;
   __host__ __device__ TimSeed() : base(0), salt(nullptr) {}
   __host__ TimSeed(uint64_t s) : base(s), salt(tim_salt_ptr) {}
+  // (gemm_pp.hip: pp_epilogue_wt_res forms the same sum from a scalar load of *salt - change the two together)
   __device__ __forceinline__ operator uint64_t() const { return salt ? base + (uint64_t)*salt : base; }
 };
 

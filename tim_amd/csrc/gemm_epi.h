@@ -112,6 +112,13 @@ constexpr bool epi_uses_dropout(int EPI) {
          EPI == TIMHIP_EPI_GELU_DROP_G2;
 }
 
+// One element of the dropout + residual epilogue, in its two steps: the LayerNorm of a pre-norm residual value, and the residual
+// plus the kept product.  The same two functions for epi_quad and for the whole-tile form (gemm_pp.hip: pp_epilogue_wt_res), so
+// that the compiler contracts the sums into the same fused multiply-adds in both places.  (Two, not one with a flag: epi_quad
+// takes the first step under its e.ln_stats branch, and its code must stay what it was.)
+__device__ __forceinline__ float ln_res_elem(float r, float mean, float rstd, float g, float be) { return (r - mean) * rstd * g + be; }
+__device__ __forceinline__ float drop_res_elem(float r, float v, float k) { return r + v * k; }
+
 // 4 consecutive columns n..n+3 of row m.  DRAW = false: an instance whose launcher guarantees keep-bits (e.mask) wherever
 // e.thr != 0 carries no Philox code
 template <int EPI, typename T, bool DRAW = true>
@@ -174,10 +181,11 @@ __device__ __forceinline__ void epi_quad(const EpiDev& e, int m, int n, int N, f
           g = *reinterpret_cast<const float4*>(e.ln_w + n);
           be = *reinterpret_cast<const float4*>(e.ln_b + n);
         }
-        r.x = (r.x - st.x) * st.y * g.x + be.x; r.y = (r.y - st.x) * st.y * g.y + be.y;
-        r.z = (r.z - st.x) * st.y * g.z + be.z; r.w = (r.w - st.x) * st.y * g.w + be.w;
+        r.x = ln_res_elem(r.x, st.x, st.y, g.x, be.x); r.y = ln_res_elem(r.y, st.x, st.y, g.y, be.y);
+        r.z = ln_res_elem(r.z, st.x, st.y, g.z, be.z); r.w = ln_res_elem(r.w, st.x, st.y, g.w, be.w);
       }
-      nt_store4<float>((float*)e.out0 + i0, r.x + v0 * k0, r.y + v1 * k1, r.z + v2 * k2, r.w + v3 * k3);
+      nt_store4<float>((float*)e.out0 + i0, drop_res_elem(r.x, v0, k0), drop_res_elem(r.y, v1, k1), drop_res_elem(r.z, v2, k2),
+                       drop_res_elem(r.w, v3, k3));
     } else if (EPI == TIMHIP_EPI_ADD_F32) {
       float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
       if (has_pre) r = pre;

@@ -114,18 +114,134 @@ __device__ __forceinline__ void pp_epilogue_g2pk(const EpiDev& e, const f32x4_t 
   });
 }
 
+// Whole-wave-tile form (pp_epilogue's WT flag, TIMHIP_EPI_WT) of the dropout + residual epilogue, whose stores the per-quad code
+// serialises: epi_quad keeps a fallback load under an exec mask beside every operand the caller may have fetched, and every
+// Philox draw converts e.seed, which reads the dropout salt from memory - a full s_waitcnt vmcnt(0) ends up in front of EVERY
+// store (vmcnt counts stores too: a wave's stores complete one at a time, and the residual ring's refill is drained with them).
+// Here everything pp_epilogue -> epi_quad decide per quad is decided once per wave (by pp_epilogue, before the call); what
+// follows is straight-line code with wave-uniform branches only, whose waits the compiler can count.  The same bits: the same
+// operations in the same order (ln_res_elem, drop_res_elem), no bias as + (-0) (returns every x, both zeros included, as it
+// is), the same cache policy per stream.  (The same form of the eight-phase kernel's STORE_T epilogue was built and measured:
+// 68.9 - 69.1 against 66.7 - 70.4 us per launch, no gain beyond the spread - docs/measurement_log.md - and was taken out.)
+
+// DROP_RES_F32 on a wave tile that lies wholly inside M x N, 16-byte accesses allowed, a residual given, and the dropout one of
+// none (e.thr == 0) or Philox on lane pairs (pp_epilogue's has_k: the same counters, words and DPP exchange).  Bias, LayerNorm
+// statistics and affine parameters are read unconditionally or are wave-uniformly absent (then 0 / 1 / -0: (r - 0) * 1 * 1 +
+// (-0) is r, bit for bit).  The residual ring is refilled where pp_epilogue refills it - behind a row block's stores - but the
+// next block's stores now wait for what they need by count, so the refill stays in flight across them.
+template <typename HT, int TMW, int PFD, typename AFTER>
+__device__ __forceinline__ void pp_epilogue_wt_res(const EpiDev& e, const f32x4_t (&acc)[PP_TNW][TMW], int mw0, int nw0, int N, float* ep,
+                                                   int lane, AFTER after) {
+  constexpr int EP_LD = 64 + 4, RBS = 16, NITQ = 4;
+  typedef float f4_t __attribute__((ext_vector_type(4)));
+  const float asc = e.acc_scale ? *e.acc_scale : 1.f;
+  const int frow = lane & 15, fq = lane >> 4;
+  const int row = lane >> 4, ch = lane & 15, n = nw0 + ch * 4;   // this lane's quads: rows row + 4 it of a row block, columns n .. n + 3
+  const bool has_ln = e.ln_stats != nullptr, drop = e.thr != 0u;
+  const float* const rp = e.res + (size_t)(mw0 + row) * e.ldres + n;
+  f4_t rbuf[PFD][NITQ];
+  float2 sbuf[PFD][NITQ];
+  auto fetch = [&](auto jc) {   // row block j -> ring entry j % PFD
+    constexpr int j = decltype(jc)::value;
+#pragma unroll
+    for (int it = 0; it < NITQ; ++it) rbuf[j % PFD][it] = __builtin_nontemporal_load(reinterpret_cast<const f4_t*>(rp + (size_t)(j * RBS + it * 4) * e.ldres));
+    if (has_ln) {
+#pragma unroll
+      for (int it = 0; it < NITQ; ++it) sbuf[j % PFD][it] = *reinterpret_cast<const float2*>(e.ln_stats + 2 * (size_t)(mw0 + row + j * RBS + it * 4));
+    }
+  };
+#pragma unroll
+  for (int q = 0; q < PFD; ++q)
+#pragma unroll
+    for (int it = 0; it < NITQ; ++it) sbuf[q][it] = make_float2(0.f, 1.f);
+  static_for<(PFD < TMW ? PFD : TMW)>([&](auto jc) { fetch(jc); });
+  // per-lane constants (the lane's columns are the same in every row block) behind the ring's first entries, as in pp_epilogue:
+  // in front of them they cost the 168-register instance a spilled quad.  The first row block therefore waits for everything
+  // above; every later one by count.  The seed is read here, once: TimSeed adds a device word (*salt) at every conversion, a
+  // load the compiler cannot move across a store - read per pair it put a full wait in front of each store pair
+  float4 b = make_float4(-0.f, -0.f, -0.f, -0.f), lng = make_float4(1.f, 1.f, 1.f, 1.f), lnb = b;
+  if (e.bias) b = *reinterpret_cast<const float4*>(e.bias + n);
+  if (has_ln) { lng = *reinterpret_cast<const float4*>(e.ln_w + n); lnb = *reinterpret_cast<const float4*>(e.ln_b + n); }
+  // Inline assembly, because plain C++ was tried and is not the same thing here: `seed = e.seed` (and the same through
+  // readfirstlane) compiles to global_load_dwordx2 through a zero-offset vector register into a vector register pair - behind
+  // the main loop's LDS-DMA the compiler does not prove the word unclobbered and emits no scalar load by itself - at the point
+  // where every register of the 168 is live.  The sum below must stay what TimSeed's conversion returns (common.h)
+  uint64_t seed = 0;
+  if (drop) {
+    seed = e.seed.base;
+    if (e.seed.salt) {
+      uint64_t salt;
+      asm volatile("s_load_dwordx2 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(salt) : "s"(e.seed.salt) : "memory");
+      seed += salt;
+    }
+  }
+  float* const p0 = (float*)e.out0 + (size_t)(mw0 + row) * e.ld0 + n;
+  const float* const src = ep + row * EP_LD + ch * 4;
+  const bool odd = (lane & 1) != 0;
+  const float ksc = drop ? e.scale : 1.f;
+
+  static_for<TMW>([&](auto jc) {
+    constexpr int j = decltype(jc)::value;
+#pragma unroll
+    for (int i = 0; i < PP_TNW; ++i) *reinterpret_cast<f32x4_t*>(ep + frow * EP_LD + i * 16 + 4 * fq) = acc[i][j] * asc;
+    pp_wait_lds();
+#pragma unroll
+    for (int it = 0; it < NITQ; it += 2) {   // (one pair's eight factors live at a time, as in pp_epilogue)
+      // the pair's Philox words stay words until their quad needs its factors (four registers, not eight); without dropout
+      // all ones against e.thr = 0: every factor is ksc = 1, the product with 1 that epi_quad performs there as well
+      uint32_t w[2][2] = {{~0u, ~0u}, {~0u, ~0u}};
+      if (drop) {
+        const int idx = (it + (lane & 1)) * 64 + (lane & ~1);
+        const long long m_ = mw0 + j * RBS + idx / 16, n_ = nw0 + (idx % 16) * 4;
+        const Philox4 r = philox4x32_7(seed, e.site, (uint64_t)(m_ * (long long)N + n_) >> 3);
+        const uint32_t sa = odd ? r.x : r.z, sb = odd ? r.y : r.w;
+        const uint32_t pa = (uint32_t)__builtin_amdgcn_mov_dpp((int)sa, 0xB1, 0xF, 0xF, true);   // quad_perm [1, 0, 3, 2]
+        const uint32_t pb = (uint32_t)__builtin_amdgcn_mov_dpp((int)sb, 0xB1, 0xF, 0xF, true);
+        w[0][0] = odd ? pa : r.x; w[0][1] = odd ? pb : r.y;
+        w[1][0] = odd ? r.z : pa; w[1][1] = odd ? r.w : pb;
+      }
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        float4 v = *reinterpret_cast<const float4*>(src + (it + h) * 4 * EP_LD);
+        v.x += b.x; v.y += b.y; v.z += b.z; v.w += b.w;
+        const f4_t r = rbuf[j % PFD][it + h];
+        const float2 st = sbuf[j % PFD][it + h];
+        float4 k;
+        drop_mask4_words(w[h][0], w[h][1], e.thr, ksc, k.x, k.y, k.z, k.w);
+        nt_store4<float>(p0 + (size_t)(j * RBS + (it + h) * 4) * e.ld0,
+                         drop_res_elem(ln_res_elem(r[0], st.x, st.y, lng.x, lnb.x), v.x, k.x),
+                         drop_res_elem(ln_res_elem(r[1], st.x, st.y, lng.y, lnb.y), v.y, k.y),
+                         drop_res_elem(ln_res_elem(r[2], st.x, st.y, lng.z, lnb.z), v.z, k.z),
+                         drop_res_elem(ln_res_elem(r[3], st.x, st.y, lng.w, lnb.w), v.w, k.w));
+      }
+    }
+    if constexpr (j + PFD < TMW) fetch(std::integral_constant<int, j + PFD>{});   // refill this block's ring entry
+    pp_wait_lds();   // reads done before the next row block overwrites the region
+    after();
+  });
+}
+
 // AFTER: called after every 16-row block (the dual-group kernel keeps its barrier cadence there; default: nothing)
 // PFA (round 6): the same ring depth for the 16-bit aux rows (default: all row blocks before the first store, as before)
 // G2PK (GELU_DROP_G2 only; the launcher guarantees e.mask wherever e.thr != 0): whole wave tiles take pp_epilogue_g2pk, the edge
 // tiles the code below without its Philox fallback
-template <typename HT, int EPI, int TMW, int PFD = TMW, typename AFTER = PpNoSync, int PFA = TMW, bool G2PK = false>
+// WT (DROP_RES_F32 only): whole wave tiles that meet the form's conditions - all of them wave-uniform - take
+// pp_epilogue_wt_res; edge tiles and every other launch (keep-bits in e.mask, N % 8 != 0 under Philox,
+// TIMHIP_EPI_PAIR=0, no residual, operands that do not allow 16-byte accesses) the code below, unchanged
+template <typename HT, int EPI, int TMW, int PFD = TMW, typename AFTER = PpNoSync, int PFA = TMW, bool G2PK = false, bool WT = false>
 __device__ __forceinline__ void pp_epilogue(const EpiDev& e, const f32x4_t (&acc)[PP_TNW][TMW], int mw0, int nw0, int M, int N,
                                             float* ep, int lane, AFTER after = AFTER{}) {
   constexpr int EP_COLS = 64, EP_LD = EP_COLS + 4, CPR = EP_COLS / 4, OPR = EP_COLS / 8, RBS = 16;
   constexpr int NITQ = RBS * CPR / 64, NITO = RBS * OPR / 64;     // 4 quads / 2 octs per lane per row block
   static_assert(!G2PK || EPI == TIMHIP_EPI_GELU_DROP_G2, "G2PK is a form of the GELU_DROP_G2 epilogue");
+  static_assert(!WT || EPI == TIMHIP_EPI_DROP_RES_F32, "WT is a form of the DROP_RES_F32 epilogue");
   if constexpr (G2PK) {
     if (e.vec8 && mw0 + RBS * TMW <= M && nw0 + EP_COLS <= N) return pp_epilogue_g2pk<HT, TMW>(e, acc, mw0, nw0, ep, lane, after);
+  }
+  if constexpr (WT && EPI == TIMHIP_EPI_DROP_RES_F32) {
+    if (e.vec && e.res != nullptr && mw0 + RBS * TMW <= M && nw0 + EP_COLS <= N &&
+        (e.thr == 0u || (!e.mask && (N & 7) == 0 && e.pair)))
+      return pp_epilogue_wt_res<HT, TMW, PFD>(e, acc, mw0, nw0, N, ep, lane, after);
   }
   const float asc = e.acc_scale ? *e.acc_scale : 1.f;
   const int frow = lane & 15, fq = lane >> 4;
@@ -725,7 +841,7 @@ __device__ __forceinline__ void pl_load(const HT* __restrict__ A, int lda, const
   pp_barrier();            // b_2nk+1
 }
 
-template <typename HT, int EPI, int TMW, bool ONEBAR = false>
+template <typename HT, int EPI, int TMW, bool ONEBAR = false, bool WT = false>
 __global__ __launch_bounds__(768) void gemm_nt_ld_kernel(const HT* __restrict__ A, int lda, const HT* __restrict__ B, int ldb,
                                                          int M, int N, int K, EpiDev e, int pf_dist, int pf_mode) {
   constexpr int BM = 32 * TMW;
@@ -776,7 +892,7 @@ __global__ __launch_bounds__(768) void gemm_nt_ld_kernel(const HT* __restrict__ 
   else pl_consume<HT, TMW, 1, ONEBAR>(nk, lds, a_frag, b_frag, c0, c1, acc, pf);
   __syncthreads();   // every wave is done with the stage ring: it becomes the epilogue's transposition space
   float* ep = reinterpret_cast<float*>(lds) + wave * (16 * 68);
-  pp_epilogue<HT, EPI, TMW, 2>(e, acc, m0 + wm * 16 * TMW, n0 + wn * 64, M, N, ep, lane);
+  pp_epilogue<HT, EPI, TMW, 2, PpNoSync, TMW, false, WT>(e, acc, m0 + wm * 16 * TMW, n0 + wn * 64, M, N, ep, lane);
 }
 
 // tpb > 1 (round 3, the shapes of two or three rounds of tiles): a block walks tpb consecutive column tiles of its row panel
@@ -1513,6 +1629,18 @@ void launch_pp(const GemmPlan& p, const void* A, int lda, const void* B, int ldb
     (void)hipFuncSetAttribute((const void*)gemm_nt_ldp_kernel<HT, EPI, TMW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
   }
   const dim3 grid(p.grid_x), block(p.block);
+  // WT: the 160-row DROP_RES_F32 instance whose whole wave tiles take pp_epilogue_wt_res (TIMHIP_EPI_WT, default 1; 0: the
+  // instance without the form)
+  if constexpr (EPI == TIMHIP_EPI_DROP_RES_F32 && TMW == 5) {
+    if (p.family == GEMM_LD && tim_knobs().epi_wt != 0) {
+      static PerDeviceOnce attr_wt;
+      if (attr_wt.first())
+        (void)hipFuncSetAttribute((const void*)gemm_nt_ld_kernel<HT, EPI, TMW, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
+      hipLaunchKernelGGL((gemm_nt_ld_kernel<HT, EPI, TMW, false, true>), grid, block, p.lds_bytes, s, (const HT*)A, lda, (const HT*)B, ldb, M, N, K, e,
+                         p.pf_dist, p.pf_mode);
+      return;
+    }
+  }
   if (p.family == GEMM_LDP)
     hipLaunchKernelGGL((gemm_nt_ldp_kernel<HT, EPI, TMW>), grid, block, p.lds_bytes, s, (const HT*)A, lda, (const HT*)B, ldb, M, N, K, e,
                        p.pf_dist, p.pf_mode, p.tpb);

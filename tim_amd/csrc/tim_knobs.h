@@ -41,5 +41,6 @@ struct TimKnobs {
   int gemm_p8 = 1;        // TIMHIP_GEMM_P8      eight-phase 256 / 320 x 256 tiles for the multi-round NT shapes: 0 off, 1 by shape (default), 2 + the mulaux epilogue, 8 / 10 forced
   int attn_bwd_co = 1;    // TIMHIP_ATTN_BWD_CO  0: the key-split fused attention backward as ONE 8-wave block per CU with a phase 2 at the end (default 1: two co-resident 4-wave blocks per CU, dK / dV accumulated per row sweep)
   int epi_g2_pk = 1;      // TIMHIP_EPI_G2_PK    0: the eight-phase NT kernel's gelu + gelu' epilogue one quad at a time through epi_oct (default 1: whole wave tiles with keep-bits or p = 0 take the branch-free pair form, gemm_pp.hip: pp_epilogue_g2pk - the same bits)
+  int epi_wt = 1;         // TIMHIP_EPI_WT       0: the 160-row loader-wave NT kernel's DROP_RES_F32 epilogue one quad at a time through epi_quad (default 1: whole wave tiles take the straight-line form whose stores stream, gemm_pp.hip: pp_epilogue_wt_res - the same bits)
 };
 const TimKnobs& tim_knobs();
